@@ -12,7 +12,10 @@ decoder forward, loss, BPTT, Adam, weight re-pack [+ gradient all-reduce]) on sy
 
 Rank 0 prints ONE JSON line.  After the timed region rank 0 runs ONE more, instrumented step (HIP events
 around every conv / attention launch inside the step, lxo_timing_*) from which the roofline entries are computed,
-then the secondary measurements (none of them touches `value`).
+then the secondary measurements (none of them touches `value`).  --dump-outputs DIR writes what the LAST timed step computed
+(loss, weights, gradient: dump_outputs) before any of that runs.  The inputs are seeded and the timed engine runs the bf16 mode without
+float atomics (Engine(deterministic=True); LXO_DETERMINISTIC=0 times the atomic mode instead), so every run with the same arguments
+computes the same arrays bit for bit and two builds can be compared array by array.
 """
 import argparse
 import json
@@ -69,6 +72,38 @@ def cpu_baseline(seconds_budget=20.0):
     return {"value": round(B / dt, 4), "unit": "img/s", "cores": cores, "kind": "port",
             "sample": "oracle/ref_model.py train_step (torch-CPU f32), %d steps of batch %d, 128x512, V=500, T=%d"
                       % (n, B, f.shape[1])}
+
+
+DUMP_PARAM_KEEP = 10 << 20       # --dump-outputs: weight entries written (40 MiB; the headline model has 8.6 M)
+DUMP_GRAD_KEEP = 4 << 20         # ... gradient entries (16 MiB): with the loss, under 64 MB in all
+
+
+def _fixed_sample(a, keep, seed):
+    """The flat array a, or -- when it has more than `keep` entries -- the entries at `keep` indices drawn (ascending) by a
+    PCG64 generator seeded with `seed`: the same length gives the same indices in every run and every build."""
+    a = a.reshape(-1)
+    if a.size <= keep:
+        return a
+    idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(a.size, keep, replace=False))
+    return a[idx]
+
+
+def dump_outputs(path, eng, stats):
+    """--dump-outputs DIR: what the timed path (Engine.train_step) computed in its LAST timed step, as its caller reads it back:
+      loss.npy        float64 [1]  token-mean cross entropy of the step's batch (train_step's return value with sync_loss=True)
+      loss_stats.npy  float64 [2]  {summed cross entropy, tokens} behind it (summed over the ranks)
+      params.npy      float32      the weights after the step's Adam update, flat in Engine.get_params() order
+      grads.npy       float32      the step's gradient, same order
+    params / grads are whole up to DUMP_PARAM_KEEP / DUMP_GRAD_KEEP entries, else a fixed seeded sample (_fixed_sample, seeds 1 / 2)."""
+    os.makedirs(path, exist_ok=True)
+    s = stats.detach().cpu().numpy().astype(np.float64).reshape(-1)[:2]
+    arrays = {"loss": np.array([s[0] / s[1]], np.float64), "loss_stats": s,
+              "params": _fixed_sample(eng.params.detach().cpu().numpy().astype(np.float32), DUMP_PARAM_KEEP, 1),
+              "grads": _fixed_sample(eng.grads.detach().cpu().numpy().astype(np.float32), DUMP_GRAD_KEEP, 2)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": sorted(n + ".npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "n_params": int(eng.n_params)}
 
 
 def free_port():
@@ -332,18 +367,21 @@ def secondary(args, eng_train, torch, dev, B, H, W, V):
     out["decode_beam5_trained_to_end"] = {"ms_per_batch": round(dt * 1e3, 2), "steps": int(bids.shape[1]), "tokens_per_s": round(ntok / dt, 0),
                                           "batch": B, "beam": 5}
     # ---- bf16 deterministic mode (lxo_shape.deterministic: every reduction ordered, bit-identical runs): what it costs on the headline workload ----
-    try:
-        engd = Engine(V, dtype="bf16", device=dev, seed=0, deterministic=True)
-        imgs, forms = synthetic.make_set(B, H, W, V, 30, 101, seed=1234)
-        imgd = torch.from_numpy(pad_batch_images(imgs)).to(dev)
-        fd, ld = pad_batch_formulas(forms, V - 2, V - 1)
-        fd_d = torch.from_numpy(fd).to(dev)
-        dtd = timed(lambda: engd.train_step(imgd, fd_d, ld, 1e-3, sync_loss=False), 10, warm=3)
-        out["deterministic_bf16"] = {"ms_per_step": round(dtd * 1e3, 3), "img_per_s": round(B / dtd, 1), "chains": bool(engd.chain_used and engd.chain_used_bwd),
-                                     "note": "the headline workload with Engine(deterministic=True): conv and dense weight gradients through per-range slabs + an ordered pass, bias sums / d_beta / loss / conv1 through ordered per-workgroup slots (no float atomics: two runs agree bit for bit, tests/test_gpu_determinism.py); tools/det_ab.py alternates the two modes in one process (profiles/r05_det_ab_two_streams.txt: +0.7 %; with one stream +1.9 %)"}
-        del engd
-    except Exception as e:
-        out["deterministic_bf16"] = {"error": repr(e)}
+    # ---- and the library's default bf16 mode with float atomics beside it (what the headline ran before it moved to the ordered mode) ----
+    for key, det, note in (
+            ("deterministic_bf16", True, "the headline workload with Engine(deterministic=True): conv and dense weight gradients through per-range slabs + an ordered pass, bias sums / d_beta / loss / conv1 through ordered per-workgroup slots (no float atomics: two runs agree bit for bit, tests/test_gpu_determinism.py); tools/det_ab.py alternates the two modes in one process (profiles/r05_det_ab_two_streams.txt: +0.7 %; with one stream +1.9 %)"),
+            ("atomic_bf16", False, "the headline workload with Engine(deterministic=False), the library's default: weight gradients, bias sums, d_beta, loss and conv1 summed with float atomics, so two runs differ by summation order (the headline times the ordered mode unless LXO_DETERMINISTIC=0)")):
+        try:
+            engd = Engine(V, dtype="bf16", device=dev, seed=0, deterministic=det)
+            imgs, forms = synthetic.make_set(B, H, W, V, 30, 101, seed=1234)
+            imgd = torch.from_numpy(pad_batch_images(imgs)).to(dev)
+            fd, ld = pad_batch_formulas(forms, V - 2, V - 1)
+            fd_d = torch.from_numpy(fd).to(dev)
+            dtd = timed(lambda: engd.train_step(imgd, fd_d, ld, 1e-3, sync_loss=False), 10, warm=3)
+            out[key] = {"ms_per_step": round(dtd * 1e3, 3), "img_per_s": round(B / dtd, 1), "chains": bool(engd.chain_used and engd.chain_used_bwd), "note": note}
+            del engd
+        except Exception as e:
+            out[key] = {"error": repr(e)}
     # ---- data parallel at world size 1 on this GPU: the N > 1 code path (token-count all-reduce on its stream, gradient buckets on the side
     #      stream through lxo_allreduce_bucket on a one-rank RCCL communicator, chain guard behind the exchange) and what it costs ----
     try:
@@ -542,7 +580,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip configs[1] / T=151 / decode measurements")
     ap.add_argument("--no-pmc", action="store_true", help="skip the two in-run rocprofv3 --pmc passes (HBM traffic of the roofline kernels)")
     ap.add_argument("--sim", action="store_true", help="TEST ONLY: CPU tensors, gloo, the hipsim build of the kernels, tiny shapes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, weights, gradient) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dtype != "bf16" and not args.sim:
         ap.error("bench.py measures the bf16 path (the metric's dtype); f32 is the parity mode exercised by tests/")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -599,7 +641,10 @@ def main():
             if os.environ.get("LXO_DP_BF16") == "1":
                 dist.grad_dtype = torch.bfloat16                 # opt-in: gradients cross xGMI as bf16 (17 MB instead of 34.5 MB)
         B, H, W, V = args.batch, args.height, args.width, args.vocab
-        eng = Engine(V, dtype=args.dtype, device=dev, seed=0)
+        # the ordered-reduction bf16 mode (lxo_shape.deterministic): no float atomics, so the same arguments give the same weights, gradient
+        # and loss in every run (--dump-outputs); with float atomics the summation order -- and after a few Adam steps the weights -- differ
+        # from run to run.  LXO_DETERMINISTIC=0 times the atomic mode; secondary.atomic_bf16 times it beside the headline in any case.
+        eng = Engine(V, dtype=args.dtype, device=dev, seed=0, deterministic=os.environ.get("LXO_DETERMINISTIC", "1") != "0")
         imgs, forms = synthetic.make_set(B, H, W, V, 30, 101, seed=1234 + rank)
     img = torch.from_numpy(pad_batch_images(imgs)).to(dev)
     f, l = pad_batch_formulas(forms, V - 2, V - 1)
@@ -653,6 +698,14 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce_max(tt)
         dt = float(tt.item())
+    dumped = None
+    if args.dump_outputs:
+        # before the instrumented step below, which would overwrite the loss region, the weights and the gradient
+        stats = eng.region("loss")[:2].clone()
+        if dist is not None:
+            dist.all_reduce(stats)                               # every rank: the global statistics, as train_step(sync_loss=True) returns them
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, eng, stats)
     ms = dt / args.steps * 1e3
     value = B * world / (dt / args.steps)
 
@@ -664,7 +717,10 @@ def main():
             "config": {"workload": "configs[2]: full encoder+attention+decoder training step, batch %d/GPU, %dx%d, vocab %d, "
                                    "T=%d (lengths U{30..100}), Adam" % (B, H, W, V, T),
                        "global_batch": B * world, "parallelism": "dp%d" % world},
+            "deterministic": bool(eng.deterministic),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if dp_info is not None:
             out["data_parallel"] = dict(dp_info, rank_cpu_pinning=(pinned if not args.sim else None))
         if args.sim:
