@@ -289,6 +289,14 @@ int lxo_greedy_decode(const lxo_shape* s, const float* params, const void* wpack
  * its tf.py_func hook (attention_mechanism.py:96-105) for visualize_attention.py. */
 int lxo_greedy_decode_attn(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                            int id_end, int max_iter, int32_t* ids_out, float* alpha_out, int* steps_out, void* stream);
+/* lxo_greedy_decode(_attn) that also returns the model's probability of every token it emits: logp_out f32 [B, max_steps] (device,
+ * NOT NULL), logp_out[b][t] = log_softmax(logits of step t)[ids_out[b][t]] -- the reference's DecoderOutput.logits reduced to the
+ * chosen token.  A row that has emitted END goes on being decoded (as its ids do) and its later columns are the log-probs of those
+ * ids: the sequence log-prob is the sum through the first END.  Columns >= *steps_out are unspecified.  alpha_out: as in
+ * lxo_greedy_decode_attn, or NULL for none.  The persistent chain, where the shape qualifies, computes the log-probs in place
+ * (its ids are those of lxo_greedy_decode); the launch-per-step fall-back rewrites them with the ids. */
+int lxo_greedy_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                             int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream);
 /* The same loops ONE STEP AT A TIME: the calls behind the reference's decoder-cell protocol (dynamic_decode.py:35-36,43-44:
  * decoder_cell.initialize() / .step(time, state, inputs, finished); greedy_decoder_cell.py:46-66,
  * beam_search_decoder_cell.py:113-187).  latex_ocr_amd/model/components/ wraps them in cell objects with the reference's
@@ -330,6 +338,14 @@ int lxo_beam_decode(const lxo_shape* s, const float* params, const void* wpack, 
 int lxo_beam_decode_attn(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                          int id_end, int max_iter, int32_t* ids_out, int32_t* parents_out, float* alpha_out,
                          int* steps_out, void* stream);
+/* lxo_beam_decode(_attn) that also returns the running log-probs of the hypotheses (the beam state's log_probs,
+ * beam_search_decoder_cell.py:146-187): scores_out f32 [B, max_steps, beam] (device, NOT NULL), scores_out[b][t][i] = the score with
+ * which slot i was selected at step t = the log-prob of the token sequence that back-traces from (t, i) through parents_out.  The slots
+ * of a step are in descending score order (top_k).  A finished hypothesis extends only with END at log-prob 0: its score is frozen.
+ * With the diversity penalty on (div_gamma, div_prob) the scores include it, as the reference's state does.  Columns >= *steps_out
+ * are unspecified.  alpha_out: as in lxo_beam_decode_attn, or NULL for none.  ids_out / parents_out are those of lxo_beam_decode. */
+int lxo_beam_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                           int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream);
 
 /* ---- data parallel: one process per GPU, RCCL over xGMI -------------------------------------
  * The reference trains on one device (one sess.run per step, model/img2seq.py:169).  Samples are independent through encoder,

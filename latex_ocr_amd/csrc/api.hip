@@ -173,6 +173,14 @@ extern "C" int lxo_greedy_decode_attn(const lxo_shape* s, const float* params, c
     CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, ids_out, alpha_out, steps_out, (hipStream_t)stream), "lxo_greedy_decode_attn");
     return 0;
 }
+extern "C" int lxo_greedy_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                        int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    if (!logp_out) return fail(-1, "lxo_greedy_decode_scores: null logp_out");
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, ids_out, alpha_out, steps_out, (hipStream_t)stream, logp_out),
+                 "lxo_greedy_decode_scores");
+    return 0;
+}
 extern "C" int lxo_decode_begin(const lxo_shape* s, const float* params, const void* wpack, void* ws, void* stream) {
     MAKE_PLAN(P, s);
     CHECK_LAUNCH(lxo_impl_decode_begin(P, params, wpack, ws, (hipStream_t)stream), "lxo_decode_begin");
@@ -196,6 +204,14 @@ extern "C" int lxo_beam_decode_attn(const lxo_shape* s, const float* params, con
     MAKE_PLAN(P, s);
     if (!alpha_out) return fail(-1, "lxo_beam_decode_attn: null alpha_out");
     CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, alpha_out, steps_out, (hipStream_t)stream), "lxo_beam_decode_attn");
+    return 0;
+}
+extern "C" int lxo_beam_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                      int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    if (!scores_out) return fail(-1, "lxo_beam_decode_scores: null scores_out");
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, alpha_out, steps_out, (hipStream_t)stream, scores_out),
+                 "lxo_beam_decode_scores");
     return 0;
 }
 

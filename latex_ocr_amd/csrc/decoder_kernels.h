@@ -40,10 +40,11 @@ int lxo_k_colsum(const float* a, long long lda, float* out, long long M, int N, 
 int lxo_k_embed_scatter(const float* demb, const int* formula, float* dtable, float* dstart, int B, int T, int D, int V, int det, hipStream_t st);
 int lxo_k_init_bwd(const float* dcc, Slabs dxh, const float* c0, const float* rec0, int ldr, float* dpre, int B, int U, int O, hipStream_t st);
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
-                 int* finished, int* n_unfinished, hipStream_t st);
+                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out = nullptr);      // logp_out (nullable): [n][max_steps] log-prob of the id
 int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
                     float* scratch, float* logp, int* finished,
-                    int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st);
+                    int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
+                    float* scores_out = nullptr);      // scores_out (nullable): [nimg][max_steps][k] the running log-probs after the step
 int lxo_k_beam_gather(float* rec, int ldr, int XH, float* cs, int U, const int* parents, int k, float* tmp_rec, float* tmp_cs, int n, void* recb, int ldrb, hipStream_t st);      // recb (nullable): bf16 mirror of the re-ordered [o | h] rows
 int lxo_k_tile_rows(const float* src, int lds, float* dst, int ldd, int n, int k, int cols, hipStream_t st);
 int lxo_k_global_norm_scale(long long n, const float* g, float clip, float* sumsq_tmp, float* out, hipStream_t st);

@@ -1501,10 +1501,11 @@ __global__ __launch_bounds__(256) void init_bwd_kernel(const float* __restrict__
 }
 
 // ---- decode ----
-// greedy_decoder_cell.py:58-64: id = argmax (first max), finished |= id == END; one wave per row
+// greedy_decoder_cell.py:58-64: id = argmax (first max), finished |= id == END; one wave per row.
+// logp_out (nullable) [n][max_steps]: log_softmax(logits)[id] = logits[id] - lse, the log-sum-exp from one more pass over the row the wave has read
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int Vp, int V, int n, int id_end,
                                                     int* __restrict__ ids_step, int* __restrict__ ids_out, int max_steps, int step,
-                                                    int* __restrict__ finished, int* __restrict__ n_unfinished) {
+                                                    int* __restrict__ finished, int* __restrict__ n_unfinished, float* __restrict__ logp_out) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
@@ -1516,8 +1517,15 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
         const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
         if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
     }
+    float lp = 0.f;
+    if (logp_out) {
+        float l = 0.f;
+        for (int j = lane; j < V; j += 64) l += expf(lg[j] - best);
+        lp = -logf(wave_sum(l));                               // logits[id] - (best + log l), logits[id] = best
+    }
     if (lane == 0) {
         if (bi >= V) bi = 0;
+        if (logp_out) logp_out[(long long)row * max_steps + step] = lp;
         ids_step[row] = bi;
         ids_out[(long long)row * max_steps + step] = bi;
         const int f = finished[row] | (bi == id_end ? 1 : 0);
@@ -1538,7 +1546,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
                                                        float* __restrict__ logp, int* __restrict__ finished,
                                                        int* __restrict__ ids_step, int* __restrict__ parents_step,
                                                        int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                       int* __restrict__ n_unfinished) {
+                                                       int* __restrict__ n_unfinished, float* __restrict__ scores_out) {
     __shared__ float lse[16];
     __shared__ float cand_v[16 * 4]; __shared__ int cand_i[16 * 4];
     __shared__ float sel_v[16]; __shared__ int sel_i[16];
@@ -1623,6 +1631,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
         parents_step[b * k + tid] = par;
         ids_out[((long long)b * max_steps + time) * k + tid] = id;
         if (par_out) par_out[((long long)b * max_steps + time) * k + tid] = par;
+        if (scores_out) scores_out[((long long)b * max_steps + time) * k + tid] = sel_v[tid];      // the running log-prob after the step (state.log_probs)
         logp[b * k + tid] = sel_v[tid];
         finished[b * k + tid] = f;
         if (!f) atomicAdd(n_unfinished, 1);
@@ -1673,7 +1682,7 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
                                                             float* __restrict__ logp, int* __restrict__ finished,
                                                             int* __restrict__ ids_step, int* __restrict__ parents_step,
                                                             int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                            int* __restrict__ n_unfinished) {
+                                                            int* __restrict__ n_unfinished, float* __restrict__ scores_out) {
     __shared__ float lse[16];
     __shared__ float sel_v[16]; __shared__ int sel_i[16];
     __shared__ int fin_old[16];
@@ -1805,6 +1814,7 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
         parents_step[b * k + tid] = par;
         ids_out[((long long)b * max_steps + time) * k + tid] = id;
         if (par_out) par_out[((long long)b * max_steps + time) * k + tid] = par;
+        if (scores_out) scores_out[((long long)b * max_steps + time) * k + tid] = sel_v[tid];      // the running log-prob after the step (state.log_probs)
         logp[b * k + tid] = sel_v[tid];
         finished[b * k + tid] = f;
         if (!f) atomicAdd(n_unfinished, 1);
@@ -2182,13 +2192,14 @@ int lxo_k_init_bwd(const float* dcc, Slabs dxh, const float* c0, const float* re
     DONE;
 }
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
-                 int* finished, int* n_unfinished, hipStream_t st) {
-    LAUNCH(argmax_kernel, cdiv(n, 4), logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished);
+                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out) {
+    LAUNCH(argmax_kernel, cdiv(n, 4), logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out);
     DONE;
 }
 int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
                     float* scratch, float* logp, int* finished,
-                    int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st) {
+                    int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
+                    float* scores_out) {
     if (k > 16) return -2;
     DivPen dp = {0.f, 0u, (unsigned)div_seed, scratch};
     if (div_gamma > 0.f && div_gamma != 1.f && div_prob > 0.f) {      // the reference returns early for gamma == 1 or prob == 0
@@ -2198,9 +2209,9 @@ int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, i
     static int fast = -1;                                      // LXO_BEAM_FAST=0: the general kernel always (A/B)
     if (fast < 0) { const char* e = getenv("LXO_BEAM_FAST"); fast = (e && e[0] == '0') ? 0 : 1; }
     if (fast && dp.log_gamma == 0.f && (long long)k * V <= BS_TH * BS_NPT && k * BS_NW <= 64)
-        hipLaunchKernelGGL(beam_step_fast_kernel, dim3(nimg), dim3(BS_TH), 0, st, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished);
+        hipLaunchKernelGGL(beam_step_fast_kernel, dim3(nimg), dim3(BS_TH), 0, st, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out);
     else
-    LAUNCH(beam_step_kernel, nimg, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished);
+    LAUNCH(beam_step_kernel, nimg, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out);
     DONE;
 }
 int lxo_k_beam_gather(float* rec, int ldr, int XH, float* cs, int U, const int* parents, int k, float* tmp_rec, float* tmp_cs, int n, void* recb, int ldrb, hipStream_t st) {

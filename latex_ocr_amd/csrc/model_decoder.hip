@@ -733,7 +733,7 @@ static int decode_loop_chunked(int max_iter, int CHUNK, int* flags, hipStream_t 
 }
 
 int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter,
-                           int* ids_out, float* alpha_out, int* steps_out, hipStream_t st) {
+                           int* ids_out, float* alpha_out, int* steps_out, hipStream_t st, float* logp_out) {
     const int B = P.s.B, ms = P.s.max_steps;
     if (ms < max_iter + 1) return -5;
     RC(attention_prepare(P, prm, wp, ws, 1, st));
@@ -757,7 +757,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
         x.tx = P.ws<float>(ws, W_DEC_TX);
         x.rec = P.ws<float>(ws, W_REC); x.recb = P.ws<bf16_t>(ws, W_RECB); x.cs = P.ws<float>(ws, W_CS);
         x.part = P.ws<float>(ws, W_APART); x.sync = P.ws<unsigned>(ws, W_XSYNC);
-        x.ids_step = ids_step; x.ids_out = ids_out; x.finished = finished;
+        x.ids_step = ids_step; x.ids_out = ids_out; x.logp_out = logp_out; x.finished = finished;
         x.B = B; x.R = P.R; x.REC = P.REC; x.RECB = P.RECB; x.V = P.s.V; x.id_end = id_end; x.max_steps = ms;
         x.t0 = 0; x.nsteps = 1; x.unfinished = flags;
         x.stop = ids_step + B;                            // one word behind the fed-back ids (region "dec_ids" holds B x max_steps ints)
@@ -793,7 +793,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
         RC(decode_common_step(P, prm, wp, ws, B, 1, cur, time == 0 ? nullptr : ids_step, st));
         if (alpha_out)      // attention weights of this step (what attention_mechanism.py:96-105 hands to its py_func hook)
             HIPRC(hipMemcpyAsync(alpha_out + (size_t)time * B * P.Rp, P.ws<float>(ws, W_ALPHA), (size_t)B * P.Rp * 4, hipMemcpyDeviceToDevice, st));
-        RC(lxo_k_argmax(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, id_end, ids_step, ids_out, ms, time, finished, unfinished, st));
+        RC(lxo_k_argmax(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, id_end, ids_step, ids_out, ms, time, finished, unfinished, st, logp_out));
         return 0;
     }));
     return 0;
@@ -882,7 +882,7 @@ int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* 
 }
 
 int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter,
-                         int* ids_out, int* parents_out, float* alpha_out, int* steps_out, hipStream_t st) {
+                         int* ids_out, int* parents_out, float* alpha_out, int* steps_out, hipStream_t st, float* scores_out) {
     const int B = P.s.B, k = P.s.beam, ms = P.s.max_steps, nv = B * k, U = P.s.U;
     if (ms < max_iter + 1 || k < 1 || k > 16) return -5;
     RC(attention_prepare(P, prm, wp, ws, k, st));
@@ -912,7 +912,7 @@ int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* 
             HIPRC(hipMemcpyAsync(alpha_out + (size_t)time * nv * P.Rp, P.ws<float>(ws, W_ALPHA), (size_t)nv * P.Rp * 4, hipMemcpyDeviceToDevice, st));
         RC(lxo_k_beam_step(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, k, id_end, time, P.s.div_gamma, P.s.div_prob, P.s.div_seed, tmp,
                            logp, finished, ids_step, par_step,
-                           ids_out, parents_out, ms, unfinished, st));
+                           ids_out, parents_out, ms, unfinished, st, scores_out));
         if (!indirect)
         RC(lxo_k_beam_gather(rec + (size_t)cur * nv * P.REC, P.REC, P.XH, cs + (size_t)cur * nv * U, U, par_step, k,
                              tmp, tmp + (size_t)nv * P.XH, nv,

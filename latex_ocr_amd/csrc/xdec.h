@@ -57,6 +57,9 @@ struct XDecDec {
     int* stop;                        // one word, zero at the start of the decode: set once every row of every chain has finished -- the chains of
                                       // this launch stop within three steps of that point, later (speculative) launches return at once
     int B, R, REC, RECB, V, id_end, t0, nsteps, max_steps;
+    float* logp_out;                  // [B][max_steps] log_softmax(logits)[id] (nullable: the instantiation without scores runs; last, so that the
+                                      // other members keep their kernel-argument offsets).  A workgroup hands s = sum exp(v_j - m) over its 16
+                                      // columns beside its arg-max word (m = that word's value) as a second tagged word
 };
 int lxo_launch_xdec_dec(const XDecDec& p, int U, int O, int C, int E, hipStream_t st);
 

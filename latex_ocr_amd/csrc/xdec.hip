@@ -789,7 +789,9 @@ int launch_nb(const XDecFwd& p, int att_u, hipStream_t st) {
 // xdec_fwd_kernel's phases with the decode's feedback (XDecDec in xdec.h).  Iteration s of the loop = [boundary: logits and arg-max of step
 // s - 1, from the o fragments P1 polls anyway] + [step s: P1 .. P4]; iteration nsteps is the boundary alone.  LDS: the y_W_o fragments take
 // the place of the raw scores (no alpha is kept), the o projection's A tile has 8 rows instead of 16.
-template <int NB>
+// SC: the log-prob of every arg-max (p.logp_out).  Beside its {max, tag | index} word a workgroup hands over {s, tag << 16}, s = the sum of
+// exp(v - max) over its 16 columns; the merge forms log p = -log sum_r s_r exp(m_r - M).  SC = false is the ids-only chain.
+template <int NB, bool SC>
 __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     // 2 rows per wave and block in flight (the training chain: 4): the decode form carries more loop-invariant addresses (token table, ids,
     // arg-max words) and with 4 rows the allocator spills 55 dwords of them into the serial phases; with 2 it spills 9
@@ -879,6 +881,8 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     const rsrc_t rll_ht = make_rsrc(ll_ht, (unsigned)B * 256u * 8u);
     const rsrc_t rll_o = make_rsrc(ll_o, (unsigned)B * 256u * 8u);
     const rsrc_t rll_am = make_rsrc(ll_am, (unsigned)B * 32u * 8u);
+    unsigned* ll_sm = ll_am + B * 32 * 2;                        // SC: the exponential-sum words [B][32 workgroups], behind the arg-max words
+    const rsrc_t rll_sm = make_rsrc(ll_sm, (unsigned)B * 32u * 8u);
     unsigned ph = 0;
     // early exit (dynamic_decode.py:38-51 stops once every row has finished): workgroup 0 of a chain looks, one boundary late and without
     // waiting, at how many chains have reported a step and how many rows it left unfinished, and raises a STOP bit in its arg-max word --
@@ -938,6 +942,7 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                     for (int w = 0; w < XW; ++w) v += redl[w][erow][eu];
                     int vi = v0 + eu;
                     if (vi >= p.V) v = -3.0e38f;
+                    const float vc = v;
 #pragma unroll
                     for (int o = 8; o > 0; o >>= 1) {
                         const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(vi, o);
@@ -945,6 +950,12 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                     }
                     // (workgroup 0, row 0 carries the chain's STOP bit: what thread 0 probed at the previous boundary)
                     const unsigned stopbit = (rank == 0 && erow == 0 && pr_done == 8 && pr_unf == 0) ? 0x8000u : 0u;
+                    if constexpr (SC) {
+                        float sr = v0 + eu < p.V ? expf(vc - v) : 0.f;   // columns >= V: 0
+#pragma unroll
+                        for (int o = 8; o > 0; o >>= 1) sr += __shfl_xor(sr, o);
+                        if (eu == 0) { const u32x2 ws = {__float_as_uint(sr), (unsigned)t << 16}; *reinterpret_cast<u32x2*>(ll_sm + ((b0 + erow) * 32 + rank) * 2) = ws; }
+                    }
                     if (eu == 0) { const u32x2 wv = {__float_as_uint(v), ((unsigned)t << 16) | stopbit | (unsigned)vi}; *reinterpret_cast<u32x2*>(ll_am + ((b0 + erow) * 32 + rank) * 2) = wv; }
                 }
                 // every workgroup gathers the 32 candidates of each of its chain's rows (thread = (row, candidate)) and reduces them
@@ -952,10 +963,16 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                     const int row = tid >> 5, cr = tid & 31;
                     const unsigned off = (unsigned)(((b0 + row) * 32 + cr) * 8);
                     float v = -3.0e38f; int vi = 0x7fffffff;
+                    float sr = 0.f;
                     const unsigned long long c0 = wall_clock64();
                     for (;;) {
                         const u32x2 wv = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rll_am, (int)off, 0, 16));
-                        const bool ok = (wv[1] >> 16) == (unsigned)t;
+                        bool ok = (wv[1] >> 16) == (unsigned)t;
+                        if constexpr (SC) {
+                            const u32x2 ws = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rll_sm, (int)off, 0, 16));
+                            ok = ok && ws[1] == ((unsigned)t << 16);
+                            if (ok) sr = __uint_as_float(ws[0]);
+                        }
                         if (ok) { v = __uint_as_float(wv[0]); vi = (int)(wv[1] & 0xffffu); }      // (bit 15 of workgroup 0's row-0 word: STOP)
                         if (__ballot(!ok) == 0ull) break;
                         if (s_dead || wall_clock64() - c0 > 20000000ull) {
@@ -965,17 +982,24 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                     }
                     if (tid == 0) s_stop = (vi >> 15) & 1;               // thread 0 holds workgroup 0's row-0 word: the chain's STOP bit
                     vi &= 0x7fff;
+                    const float mr = v;
 #pragma unroll
                     for (int o = 16; o > 0; o >>= 1) {
                         const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(vi, o);
                         if (ov > v || (ov == v && oi < vi)) { v = ov; vi = oi; }
                     }
+                    if constexpr (SC) {
+                        sr *= expf(mr - v);                               // rescaled to the row's max
+#pragma unroll
+                        for (int o = 16; o > 0; o >>= 1) sr += __shfl_xor(sr, o);
+                    }
                     if (cr == 0) {
                         if (vi >= p.V) vi = 0;
                         ids_l[row] = vi;
-                        if (rank == 0) {                          // one workgroup per chain publishes: ids, finished flags
+                        if (rank == 0) {                          // one workgroup per chain publishes: ids, log-probs, finished flags
                             const int bb = b0 + row;
                             p.ids_out[(long long)bb * p.max_steps + (tg - 1)] = vi;
+                            if constexpr (SC) p.logp_out[(long long)bb * p.max_steps + (tg - 1)] = -logf(sr);
                             p.ids_step[bb] = vi;
                             const int fo = p.finished[bb] | (vi == p.id_end ? 1 : 0);
                             p.finished[bb] = fo;
@@ -1281,14 +1305,16 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     if (tid == 0 && s_dead) *reinterpret_cast<volatile int*>(p.stop) = 1;
 }
 
-template <int NB>
-int launch_dec_nb(const XDecDec& p, hipStream_t st) {
+template <int NB, bool SC>
+int launch_dec_sc(const XDecDec& p, hipStream_t st) {
     constexpr int DYN = XW * 12 * 64 * 16;
     static bool attr_done = false;
-    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_dec_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
-    hipLaunchKernelGGL((xdec_dec_kernel<NB>), dim3(256), dim3(512), DYN, st, p);
+    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_dec_kernel<NB, SC>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
+    hipLaunchKernelGGL((xdec_dec_kernel<NB, SC>), dim3(256), dim3(512), DYN, st, p);
     return (int)hipGetLastError();
 }
+template <int NB>
+int launch_dec_nb(const XDecDec& p, hipStream_t st) { return p.logp_out ? launch_dec_sc<NB, true>(p, st) : launch_dec_sc<NB, false>(p, st); }
 
 // ------------------------------------------------------------------------------------------------ backward chain ----
 // Steps T-1 .. 0 of BPTT in one launch, same chains, same identity, same barrier.  Per step:
@@ -1794,7 +1820,7 @@ int lxo_launch_xdec_dec(const XDecDec& p, int U, int O, int C, int E, hipStream_
     // tickets / flags and the hand-over area, but NOT the error word (int 512): an error of an earlier launch of this decode stays visible
     HIPRC(hipMemsetAsync(p.sync, 0, 8 * 64 * 4, st));
     HIPRC(hipMemsetAsync(p.sync + 8 * 64 + 1, 0, kXDecBlockBytes - (8 * 64 + 1) * 4, st));
-    HIPRC(hipMemsetAsync(p.sync + kXDecBlockBytes / 4 + kXDecSyncBytes / 4, 0, (size_t)p.B * 32 * 8, st));      // the arg-max words (block 1's hand-over area)
+    HIPRC(hipMemsetAsync(p.sync + kXDecBlockBytes / 4 + kXDecSyncBytes / 4, 0, (size_t)p.B * 32 * 8 * (p.logp_out ? 2 : 1), st));      // the arg-max words (block 1's hand-over area; + the exponential sums)
     if (kLL & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * nq * PLW * 8, st));               // the polled chunk partials (tags restart with every launch)
     switch (nb) {
     case 1: return launch_dec_nb<1>(p, st);

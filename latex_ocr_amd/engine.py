@@ -627,10 +627,12 @@ class Engine(object):
             return B
         return next(n for n in (8, 16, 32, 64) if B < n)
 
-    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False):
+    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False):
         """ids int32 [B, T'] as pred_test.ids of the greedy graph (decoder.py:64,70).  With return_attention also the
         attention maps alpha f32 [B, T', H', W'] (what the reference collects through its py_func hook,
         attention_mechanism.py:96-105, for visualize_attention.py).
+        return_scores: -> (ids, logp) or (ids, alpha, logp), logp f32 [B, T'] = log_softmax(logits)[ids] of every step
+        (lxo_greedy_decode_scores); the sequence log-prob of a row is the sum through its first END.
         A batch the persistent decode chain does not take (B not in {8, 16, 32, 64}) is filled up to the next such size with COPIES of its own
         images (rows are independent and a copy finishes with its original, so neither the ids of the real rows nor the step count change):
         20 images decode in 26 us per step on the chain where the launch-per-step kernels take 44."""
@@ -644,7 +646,12 @@ class Engine(object):
         B = self._encode_only(img, 1)
         ids = torch.zeros(B, self.max_steps, dtype=torch.int32, device=self.device)
         steps = ctypes.c_int(0)
+        logp = torch.zeros(B, self.max_steps, dtype=torch.float32, device=self.device) if return_scores else None
         if not return_attention:
+            if return_scores:
+                self._ck(self.lib.lxo_greedy_decode_scores(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
+                                                           _p(ids), _p(logp), None, ctypes.byref(steps), self._stream()), "greedy_decode_scores")
+                return ids[:B0, :steps.value].cpu().numpy(), logp[:B0, :steps.value].cpu().numpy()
             self._ck(self.lib.lxo_greedy_decode(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
                                                 _p(ids), ctypes.byref(steps), self._stream()), "greedy_decode")
             return ids[:B0, :steps.value].cpu().numpy()
@@ -653,10 +660,16 @@ class Engine(object):
         R = Hp * Wp
         Rp = (R + 7) // 8 * 8
         alpha = torch.zeros(self.max_steps, B, Rp, dtype=torch.float32, device=self.device)
-        self._ck(self.lib.lxo_greedy_decode_attn(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                 _p(ids), _p(alpha), ctypes.byref(steps), self._stream()), "greedy_decode_attn")
+        if return_scores:
+            self._ck(self.lib.lxo_greedy_decode_scores(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
+                                                       _p(ids), _p(logp), _p(alpha), ctypes.byref(steps), self._stream()), "greedy_decode_scores")
+        else:
+            self._ck(self.lib.lxo_greedy_decode_attn(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
+                                                     _p(ids), _p(alpha), ctypes.byref(steps), self._stream()), "greedy_decode_attn")
         n = steps.value
         a = alpha[:n, :, :R].permute(1, 0, 2).reshape(B, n, Hp, Wp).cpu().numpy()
+        if return_scores:
+            return ids[:, :n].cpu().numpy(), a, logp[:, :n].cpu().numpy()
         return ids[:, :n].cpu().numpy(), a
 
     # one step at a time: what model/components (the reference's decoder-cell protocol) drives
@@ -724,11 +737,14 @@ class Engine(object):
         Vp = (self.n_tok + 31) // 32 * 32
         return self.region("dec_logits", "f32", (self._dec_rows(), Vp))[:, :self.n_tok].cpu().numpy()
 
-    def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False):
+    def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False,
+                    return_scores=False):
         """ids int32 [B, T', k] as pred_test.ids of the beam graph before the transpose at img2seq.py:241.
         div_gamma / div_prob: add_div_penalty of beam_search_decoder_cell.py:258-287 (off at 1 / 0, the shipped values).
         return_attention: -> (ids, parents, alpha f32 [B, T', k, H', W']): alpha[b, t, j] = the map decoder row j of image b attended with at
-        step t (lxo_beam_decode_attn; the rows the reference's py_func tap sees under config.decoding = "beam_search")."""
+        step t (lxo_beam_decode_attn; the rows the reference's py_func tap sees under config.decoding = "beam_search").
+        return_scores: -> (ids, parents, scores) or (ids, parents, alpha, scores), scores f32 [B, T', k] = the running log-prob of slot k after
+        step t (the beam state's log_probs; lxo_beam_decode_scores): the log-prob of the sequence that back-traces from (t, k)."""
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B = self._encode_only(img, int(beam_size))
@@ -737,6 +753,21 @@ class Engine(object):
         ids = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         par = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         steps = ctypes.c_int(0)
+        if return_scores:
+            sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device)
+            alpha, a = None, None
+            if return_attention:
+                from .model.utils.image import encoder_out_hw
+                Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
+                R = Hp * Wp
+                alpha = torch.zeros(self.max_steps, B * beam_size, (R + 7) // 8 * 8, dtype=torch.float32, device=self.device)
+            self._ck(self.lib.lxo_beam_decode_scores(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
+                                                     _p(ids), _p(par), _p(sc), _p(alpha), ctypes.byref(steps), self._stream()), "beam_decode_scores")
+            n = steps.value
+            out = (ids[:, :n].cpu().numpy(), par[:, :n].cpu().numpy())
+            if return_attention:
+                out += (alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous().cpu().numpy(),)
+            return out + (sc[:, :n].cpu().numpy(),)
         if return_attention:
             from .model.utils.image import encoder_out_hw
             Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))

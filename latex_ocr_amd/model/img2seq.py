@@ -162,8 +162,16 @@ class Img2SeqModel(BaseModel):
         perp = -np.exp(ce_words / float(n_words))
         return files, perp
 
-    def predict_batch(self, images):
-        """Reference: model/img2seq.py:256-276."""
+    def predict_batch(self, images, return_scores=False):
+        """Reference: model/img2seq.py:256-276.
+        return_scores: -> (hyps, scores), scores[i][b] = (sequence log-prob, [log-prob of each token up to and including the first END]) of
+        hypothesis hyps[i][b]; the sequence log-prob is the sum of the token log-probs.  Greedy: the hypotheses are the default call's.
+        Beam search: the hypotheses are the back-traced ones (utils/text.beam_backtrace) whatever config.beam_backtrace says -- the final
+        running log-prob of slot i belongs to the token path that ends in slot i, not to the per-step columns of the reference's read-out
+        (quirk C-1) -- and a token's log-prob is the difference of the running scores along that path (with the diversity penalty on, the
+        penalised scores)."""
+        if return_scores:
+            return self._predict_scored(images)
         fd = self._get_feed_dict(images, dropout=1)
         ids_eval = self._decode(fd["img"])
         hyps = [[] for _ in range(ids_eval.shape[1])]
@@ -172,6 +180,34 @@ class Img2SeqModel(BaseModel):
                 p = truncate_end(pred, self._vocab.id_end)
                 hyps[i].append(" ".join(self._vocab.id_to_tok[int(idx)] for idx in p))
         return hyps
+
+    def _predict_scored(self, images):
+        fd = self._get_feed_dict(images, dropout=1)
+        cfg = self._config
+        max_iter = getattr(cfg, "max_length_formula", 150) + 1
+        id_end = self._vocab.id_end
+        if getattr(cfg, "decoding", "greedy") == "beam_search":
+            from .utils.text import beam_backtrace
+            self._div_calls = getattr(self, "_div_calls", 0) + 1
+            ids, par, sc = self.engine.beam_decode(fd["img"], id_end, cfg.beam_size, max_iter=max_iter,
+                                                   div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0),
+                                                   div_seed=self._div_calls, return_scores=True)
+            ids, run = beam_backtrace(ids, par), beam_backtrace(sc, par)          # token paths and their running log-probs
+            tok = np.diff(run, axis=1, prepend=0.0)
+        else:
+            ids, tok = self.engine.greedy_decode(fd["img"], id_end, max_iter=max_iter, return_scores=True)
+            ids, tok = ids[:, :, None], tok[:, :, None]
+        k = ids.shape[2]
+        hyps, scores = [[] for _ in range(k)], [[] for _ in range(k)]
+        for b in range(ids.shape[0]):
+            for i in range(k):
+                path = ids[b, :, i]
+                end = np.flatnonzero(path == id_end)
+                n = int(end[0]) + 1 if end.size else len(path)
+                lp = [float(x) for x in tok[b, :n, i]]
+                hyps[i].append(" ".join(self._vocab.id_to_tok[int(idx)] for idx in truncate_end(path, id_end)))
+                scores[i].append((float(np.sum(np.asarray(lp, dtype=np.float64))), lp))
+        return hyps, scores
 
     def predict(self, img):
         """Reference: model/img2seq.py:278-285."""

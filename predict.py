@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Prediction driver with the shape of the reference's predict.py:38-68: restore the trained model from a results
 directory and print the LaTeX hypothesis for each image path given (the reference's interactive shell and its
-pdf/LaTeX->PNG cropping helpers are out of scope)."""
+pdf/LaTeX->PNG cropping helpers are out of scope).  --scores adds the hypothesis' log-prob and its geometric-mean token
+probability exp(log-prob / tokens) (Img2SeqModel.predict_batch(..., return_scores=True))."""
 import argparse
 
 import numpy as np
@@ -15,6 +16,7 @@ from latex_ocr_amd.model.utils.text import Vocab
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--results", default="results/small/")
+    ap.add_argument("--scores", action="store_true", help="print the log-prob and the geometric-mean token probability of each hypothesis")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     d = a.results
@@ -26,6 +28,13 @@ def main(argv=None):
     out = []
     for path in a.images:
         img = np.asarray(Image.open(path).convert("RGB"))
+        if a.scores:
+            hyps, scores = model.predict_batch([greyscale(img)], return_scores=True)
+            hyps = [h[0] for h in hyps]
+            lp, toks = scores[0][0]
+            print(path, "=>", hyps[0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
+            out.append((hyps, [s[0] for s in scores]))
+            continue
         hyps = model.predict(greyscale(img))
         print(path, "=>", hyps[0])
         out.append(hyps)

@@ -1,5 +1,6 @@
 """Greedy / beam decode latency on synthetic 128x512 crops (random-init weights never emit END, so every run decodes
-the full max_iter + 1 steps)."""
+the full max_iter + 1 steps).  --scores: each decode once without and once with return_scores (token log-probs / hypothesis
+scores), interleaved over --reps rounds, for the A/B of the scored calls."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -9,12 +10,36 @@ from latex_ocr_amd.model.utils.image import pad_batch_images
 V, B = 500, 64
 imgs, _ = synthetic.make_set(B, 128, 512, V, 30, 101, seed=5)
 img = torch.from_numpy(pad_batch_images(imgs)).cuda()
-for beam in (1, 5):
-    eng = Engine(V, dtype="bf16", beam=beam, max_steps=152)
-    fn = (lambda: eng.greedy_decode(img, V - 1, max_iter=100)) if beam == 1 else (lambda: eng.beam_decode(img, V - 1, beam, max_iter=100))
-    fn(); torch.cuda.synchronize()
-    t0 = time.perf_counter(); n = 3
+scores_ab = "--scores" in sys.argv
+reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
+
+
+def timed(fn, n=3):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
     for _ in range(n): out = fn()
     torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / n
-    print("beam %d: %d steps, %.1f ms per batch of %d (%.1f us per step, %.0f img/s)" % (beam, out.shape[1], dt * 1e3, B, dt * 1e6 / out.shape[1], B / dt))
+    out = out[0] if isinstance(out, tuple) else out
+    return (time.perf_counter() - t0) / n, out.shape[1]
+
+
+for beam in (1, 5):
+    eng = Engine(V, dtype="bf16", beam=beam, max_steps=152)
+    if beam == 1:
+        arms = {False: lambda: eng.greedy_decode(img, V - 1, max_iter=100), True: lambda: eng.greedy_decode(img, V - 1, max_iter=100, return_scores=True)}
+    else:
+        arms = {False: lambda: eng.beam_decode(img, V - 1, beam, max_iter=100), True: lambda: eng.beam_decode(img, V - 1, beam, max_iter=100, return_scores=True)}
+    if not scores_ab:
+        arms[False]()
+        dt, steps = timed(arms[False])
+        print("beam %d: %d steps, %.1f ms per batch of %d (%.1f us per step, %.0f img/s)" % (beam, steps, dt * 1e3, B, dt * 1e6 / steps, B / dt))
+        continue
+    arms[False](); arms[True]()
+    per = {False: [], True: []}
+    for r in range(reps):
+        for sc in ((False, True) if r % 2 == 0 else (True, False)):
+            dt, steps = timed(arms[sc])
+            per[sc].append(dt * 1e6 / steps)
+    a, b = sorted(per[False]), sorted(per[True])
+    print("beam %d: us per step (median of %d, min..max)  ids only %.2f (%.2f..%.2f)  with scores %.2f (%.2f..%.2f)  ratio %.4f"
+          % (beam, reps, a[reps // 2], a[0], a[-1], b[reps // 2], b[0], b[-1], b[reps // 2] / a[reps // 2]))
