@@ -1,11 +1,13 @@
 #!/usr/bin/env python
 """Text evaluation driver with the shape of the reference's evaluate_txt.py:13-50: reload the
-configs saved in the results dir, restore the latest checkpoint, decode the test set, score."""
+configs saved in the results dir, restore the latest checkpoint, decode the test set, score.  --per-sample FILE also writes the
+teacher-forced score of every test sample's own label (Img2SeqModel.score_batch), one TSV line each -- index, tokens, sequence
+log-prob, mean token log-prob, first position where the model's top-1 differs from the label -- lowest mean first."""
 import argparse
 
 from latex_ocr_amd.model.evaluation.text import score_files
 from latex_ocr_amd.model.img2seq import Img2SeqModel
-from latex_ocr_amd.model.utils.general import Config
+from latex_ocr_amd.model.utils.general import Config, minibatches
 from latex_ocr_amd.model.utils.text import Vocab
 from train import make_sets
 
@@ -13,6 +15,7 @@ from train import make_sets
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--results", default="results/small/")
+    ap.add_argument("--per-sample", default=None, metavar="FILE", help="write per-sample teacher-forced scores of the labels (TSV)")
     a = ap.parse_args(argv)
     d = a.results
     config_data, config_vocab, config_model = Config(d + "data.json"), Config(d + "vocab.json"), Config(d + "model.json")
@@ -25,7 +28,22 @@ def main(argv=None):
     scores = score_files(files[0], files[1])
     scores["perplexity"] = perplexity
     model.logger.info("- Test Txt: " + " || ".join("{} is {:04.2f}".format(k, v) for k, v in scores.items()))
+    if a.per_sample:
+        write_per_sample(model, vocab, test_set, a.per_sample, config_eval.batch_size)
     return scores
+
+
+def write_per_sample(model, vocab, test_set, path, batch_size):
+    """One line per test sample, in ascending mean token log-prob: the labels the model finds least likely first."""
+    rows, i = [], 0
+    for img, formula in minibatches(test_set, batch_size):
+        for form, (lp, toks, first) in zip(formula, model.score_batch(img, formula)):
+            rows.append((lp / len(toks), i, " ".join(vocab.id_to_tok[int(t)] for t in form), lp, first))
+            i += 1
+    rows.sort(key=lambda r: (r[0], r[1]))
+    with open(path, "w") as f:
+        for mean, idx, toks, lp, first in rows:
+            f.write("%d\t%s\t%.6f\t%.6f\t%d\n" % (idx, toks, lp, mean, first))
 
 
 if __name__ == "__main__":

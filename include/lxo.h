@@ -226,6 +226,15 @@ int lxo_ce_loss_fwd_bwd(const lxo_shape* s, void* ws, const int32_t* formula,
  * synchronisation sits between forward and backward (img2seq.py:69-71 takes the mean over all tokens of the batch). */
 int lxo_ce_loss_fwd_bwd_dev(const lxo_shape* s, void* ws, const int32_t* formula,
                             const int32_t* lengths, const float* ntok_dev, void* stream);
+/* Teacher-forced scoring, after lxo_decoder_train_fwd with the same shape and formula: per-token log-probs, the model's top-1 token per
+ * position and per-sequence sums; reads ws region "logits", writes only the caller's outputs (device, [B, T] / [B]).
+ * logp_out f32 [B, T] (NOT NULL): log_softmax(logits of step t)[formula[b][t]] for t < lengths[b], 0 after.
+ * top1_out int32 [B, T] (nullable): the arg-max of step t's logits (the lower id on ties, as greedy decode picks it), -1 for t >= lengths[b].
+ * seq_out f32 [B] (nullable): logp_out[b][0] + ... + logp_out[b][lengths[b] - 1], added in ascending t in f32.
+ * -seq_out summed over the batch is the "sum CE" lxo_ce_loss_fwd_bwd leaves, up to summation order.  Token ids outside [0, V) are clamped
+ * (the caller should refuse them).  When the forward chain's error word is set every logp / seq is NaN and every top1 -1. */
+int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
+                     float* logp_out, int32_t* top1_out, float* seq_out, void* stream);
 /* BPTT through the decoder (what TF autodiff does for img2seq.py:119-123);
  * accumulates decoder gradients into grads and leaves d(enc) in ws region "d_img" (bf16 mode: already masked by conv6's
  * ReLU and converted, with conv6's bias gradient added to grads; f32 mode: the plain f32 gradient). */

@@ -130,6 +130,15 @@ extern "C" int lxo_ce_loss_fwd_bwd_dev(const lxo_shape* s, void* ws, const int32
     CHECK_LAUNCH(lxo_impl_ce_loss(P, ws, formula, lengths, 0.f, ntok_dev, (hipStream_t)stream), "lxo_ce_loss_fwd_bwd_dev");
     return 0;
 }
+extern "C" int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
+                                float* logp_out, int32_t* top1_out, float* seq_out, void* stream) {
+    MAKE_PLAN(P, s);
+    if (s->T <= 0) return fail(-1, "T must be positive");
+    if (!ws || !formula || !lengths) return fail(-1, "lxo_score_tokens: null workspace, formula or lengths");
+    if (!logp_out) return fail(-1, "lxo_score_tokens: null logp_out");
+    CHECK_LAUNCH(lxo_impl_score_tokens(P, ws, formula, lengths, logp_out, top1_out, seq_out, (hipStream_t)stream), "lxo_score_tokens");
+    return 0;
+}
 extern "C" int lxo_decoder_train_bwd(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                                      const int32_t* formula, float* grads, void* stream) {
     MAKE_PLAN(P, s);

@@ -1821,6 +1821,116 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
     }
 }
 
+// ---- teacher-forced scoring (lxo_score_tokens) ----
+// Forward-only read-out of the training logits: logp_out[b][t] = logits[row][formula[b][t]] - lse(row) and top1_out[b][t] (nullable) =
+// the row's first maximum (argmax_kernel's rule: the lower index on ties), row = t * B + b.  No d(logits), no loss statistics, no atomics.
+// One wave per row with the row in registers, as ce_loss_rows_kernel, and with its expressions (bf16 mode: v_exp_f32, f32 mode: expf):
+// -sum logp over the live tokens is that kernel's sum CE up to summation order.  Rows t >= lengths[b]: logp 0, top1 -1.  A failed forward
+// chain (chain_err set): every logp NaN, every top1 -1, as the CE kernel turns its loss into NaN.
+template <bool BF, int KV>
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                        const int* __restrict__ lengths, float* __restrict__ logp_out, int* __restrict__ top1_out,
+                                                        const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool bad = chain_err && chain_err[0] != 0u;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const int t = row / B, b = row - t * B;
+        const long long o = (long long)b * T + t;
+        if (bad || t >= lengths[b]) {
+            if (lane == 0) { logp_out[o] = bad ? __uint_as_float(0x7fc00000u) : 0.f; if (top1_out) top1_out[o] = -1; }
+            continue;
+        }
+        const float* lg = logits + (long long)row * Vp;
+        int tgt = formula[o];
+        tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
+        const float xt = lg[tgt];
+        float x[KV];
+#pragma unroll
+        for (int q = 0; q < KV / 4; ++q) {
+            const int j0 = 4 * (lane + 64 * q);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(lg + (j0 < Vp ? j0 : 0));          // unconditional (clamped) load
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[4 * q + e] = (j0 + e < V) ? v[e] : -3.0e38f;
+        }
+        float m = x[0];
+#pragma unroll
+        for (int e = 1; e < KV; ++e) m = fmaxf(m, x[e]);
+        m = wave_max(m);
+        float l = 0.f;
+#pragma unroll
+        for (int e = 0; e < KV; ++e) l += BF ? __expf(x[e] - m) : expf(x[e] - m);
+        l = wave_sum(l);
+        const float lse = m + logf(l);
+        float best = -3.0e38f; int bi = 0x7fffffff;
+        if (top1_out) {
+            // a lane's columns in ascending order (strict >: its first maximum), then the wave's (value desc, index asc)
+#pragma unroll
+            for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int j = 4 * (lane + 64 * q) + e;
+                    if (j < V && x[4 * q + e] > best) { best = x[4 * q + e]; bi = j; }
+                }
+            wave_argmax(best, bi);
+        }
+        if (lane == 0) { logp_out[o] = xt - lse; if (top1_out) top1_out[o] = bi < V ? bi : 0; }
+    }
+}
+
+// The same for any Vp (the row does not fit in registers): three strided passes per row, with ce_loss_kernel's expressions (expf in both
+// modes), so that its sum CE is again -sum logp up to summation order.
+__global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                   const int* __restrict__ lengths, float* __restrict__ logp_out, int* __restrict__ top1_out,
+                                                   const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool bad = chain_err && chain_err[0] != 0u;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const int t = row / B, b = row - t * B;
+        const long long o = (long long)b * T + t;
+        if (bad || t >= lengths[b]) {
+            if (lane == 0) { logp_out[o] = bad ? __uint_as_float(0x7fc00000u) : 0.f; if (top1_out) top1_out[o] = -1; }
+            continue;
+        }
+        const float* lg = logits + (long long)row * Vp;
+        int tgt = formula[o];
+        tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
+        float m = -3.0e38f;
+        for (int j = lane; j < V; j += 64) m = fmaxf(m, lg[j]);
+        m = wave_max(m);
+        float l = 0.f;
+        for (int j = lane; j < V; j += 64) l += expf(lg[j] - m);
+        l = wave_sum(l);
+        const float lse = m + logf(l);
+        float best = -3.0e38f; int bi = 0x7fffffff;
+        if (top1_out) {
+            for (int j = lane; j < V; j += 64) { const float x = lg[j]; if (x > best) { best = x; bi = j; } }
+            wave_argmax(best, bi);
+        }
+        if (lane == 0) { logp_out[o] = lg[tgt] - lse; if (top1_out) top1_out[o] = bi < V ? bi : 0; }
+    }
+}
+
+// seq_out[b] = logp_out[b][0] + ... + logp_out[b][len - 1], one thread per sequence adding in ascending t: the f32 sum in np.float32's
+// left-to-right order, whatever the grid of the pass before; a failed forward chain: NaN.  The loads go out 16 at a time ahead of their
+// additions (one load after another, T = 101 took 21 us of dependent latency)
+__global__ __launch_bounds__(256) void score_seq_kernel(const float* __restrict__ logp, const int* __restrict__ lengths, float* __restrict__ seq_out,
+                                                       const unsigned* __restrict__ chain_err, int B, int T) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int n = lengths[b];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    const float* p = logp + (long long)b * T;
+    float s = 0.f;
+    for (int t0 = 0; t0 < n; t0 += 16) {
+        float v[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[e] = t0 + e < n ? p[t0 + e] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) if (t0 + e < n) s += v[e];
+    }
+    seq_out[b] = (chain_err && chain_err[0] != 0u) ? __uint_as_float(0x7fc00000u) : s;
+}
+
 // new[v] = old[b*k + parents[v]] for the carried state (o | h of rec, and c)   (beam_search_decoder_cell.py:176-178)
 __global__ __launch_bounds__(256) void beam_gather_kernel(const float* __restrict__ rec, int ldr, int XH, const float* __restrict__ cs, int U,
                                                          const int* __restrict__ parents, int k, float* __restrict__ tmp_rec, float* __restrict__ tmp_cs, int n) {
@@ -2155,6 +2265,21 @@ int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* le
     if (dt == LXO_BF16) LAUNCH((ce_loss_kernel<bf16_t>), g, logits, formula, lengths, (bf16_t*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp);
     else LAUNCH((ce_loss_kernel<float>), g, logits, formula, lengths, (float*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp);
     if (part) return lxo_k_det_reduce(part, g, 2, 2, loss_acc, st);
+    DONE;
+}
+int lxo_k_score(int dt, const float* logits, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out,
+                const unsigned* chain_err, int B, int T, int V, int Vp, hipStream_t st) {
+    int g = cdiv(T * B, 4);
+    if (Vp % 4 == 0 && Vp <= 1024 && ((uintptr_t)logits & 15) == 0) {
+        if (g > 2048) g = 2048;
+#define SC_ROWS(BF_, KV_) LAUNCH((score_rows_kernel<BF_, KV_>), g, logits, formula, lengths, logp_out, top1_out, chain_err, B, T, V, Vp)
+        if (dt == LXO_BF16) { if (Vp <= 256) SC_ROWS(true, 4); else if (Vp <= 512) SC_ROWS(true, 8); else SC_ROWS(true, 16); }
+        else { if (Vp <= 256) SC_ROWS(false, 4); else if (Vp <= 512) SC_ROWS(false, 8); else SC_ROWS(false, 16); }
+#undef SC_ROWS
+    } else {
+        LAUNCH(score_kernel, g > 512 ? 512 : g, logits, formula, lengths, logp_out, top1_out, chain_err, B, T, V, Vp);
+    }
+    if (seq_out) LAUNCH(score_seq_kernel, cdiv(B, 256), logp_out, lengths, seq_out, chain_err, B, T);
     DONE;
 }
 // ordered column sums (no atomics): per-row-block partial sums into the scratch, then the blocks in order; a = f32 or (bf16 != 0) bf16

@@ -300,6 +300,13 @@ int lxo_impl_ce_loss(const Plan& P, void* ws, const int* formula, const int* len
     return 0;
 }
 
+// teacher-forced scoring of the formula the last lxo_decoder_train_fwd ran: reads ws region "logits" (and the forward chain's error word),
+// writes the caller's outputs only
+int lxo_impl_score_tokens(const Plan& P, void* ws, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out, hipStream_t st) {
+    return lxo_k_score(P.s.dtype, P.ws<float>(ws, W_LOGITS), formula, lengths, logp_out, top1_out, seq_out,
+                       P.bf ? P.ws<unsigned>(ws, W_XSYNC) + 8 * 64 : nullptr, P.s.B, P.s.T, P.s.V, P.Vp, st);
+}
+
 // The weight-gradient side stream of the encoder backward (model_encoder.hip: lxo_set_encoder_side_stream) also takes the decoder's
 // deferred all-step weight gradients (round 5): behind the backward chain the critical path is init states -> d_att_img (bound by the
 // transcendental rate) -> d_img -> conv6; the four dense dW GEMMs, d_z's column sum, the embedding gradient and dW_att_img feed nothing

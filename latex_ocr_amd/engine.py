@@ -585,6 +585,59 @@ class Engine(object):
         s = self.loss(lengths, 1.0 / max(n, 1)).cpu().numpy()
         return float(s[0]), n
 
+    def score(self, img, formula, lengths, return_top1=False):
+        """Teacher-forced scoring of given formulas (lxo_score_tokens): -> (logp f32 [B, T], seq f32 [B]) or (logp, top1 int32 [B, T], seq),
+        host arrays.  logp[b, t] = log_softmax(logits of step t)[formula[b, t]] for t < lengths[b], 0 after; top1[b, t] = the model's
+        arg-max at step t (lower id on ties, the greedy rule), -1 after; seq[b] = the f32 sum of logp[b, :lengths[b]] in ascending t
+        (-sum(seq) = evaluate_batch's CE sum up to summation order).  The forward is forward(img, formula) without dropout -- the chain
+        batch padding comes with it -- and a batch above 64 is scored in consecutive pieces of at most 64 rows, so each piece can take
+        the persistent chain.  Touches no gradient, loss statistic or optimizer state."""
+        f = formula.detach().cpu().numpy() if isinstance(formula, torch.Tensor) else np.asarray(formula)
+        ln = lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
+        f = np.ascontiguousarray(f, dtype=np.int64)
+        ln = np.ascontiguousarray(ln, dtype=np.int64).reshape(-1)
+        B = int(img.shape[0])
+        if f.ndim != 2 or f.shape[0] != B or ln.shape[0] != B:
+            raise ValueError("score: formula must be [B, T] and lengths [B] for B = %d images, got %s and %s" % (B, f.shape, ln.shape))
+        if f.size and (f.min() < 0 or f.max() >= self.n_tok):
+            raise ValueError("score: token ids must lie in [0, %d), got %d .. %d" % (self.n_tok, int(f.min()), int(f.max())))
+        if ln.size and (ln.min() < 0 or ln.max() > f.shape[1]):
+            raise ValueError("score: lengths must lie in [0, T = %d], got %d .. %d" % (f.shape[1], int(ln.min()), int(ln.max())))
+        f, ln = f.astype(np.int32), ln.astype(np.int32)
+        parts = [self._score_piece(img[i:i + 64], f[i:i + 64], ln[i:i + 64], return_top1) for i in range(0, B, 64)]
+        logp, seq = np.concatenate([p[0] for p in parts]), np.concatenate([p[2] for p in parts])
+        return (logp, np.concatenate([p[1] for p in parts]), seq) if return_top1 else (logp, seq)
+
+    def _score_piece(self, img, formula, lengths, top1_on):
+        while True:
+            self.forward(img, formula)
+            B, T = int(self.shape.B), int(self.shape.T)
+            live, n = int(self.live_B), B * T
+            ln = np.zeros(B, np.int32)
+            ln[:live] = lengths                                     # the dead rows forward() appended: length 0, logp 0 / top1 -1
+            ln_dev = self._lengths_dev(ln)
+            chain = self._chains_possible()
+            # ONE device buffer and one copy to the host: logp | top1 | seq | the forward chain's sync words (chain_status's slice)
+            buf = torch.empty(2 * n + B + (8 * 64 + 1 if chain else 0), dtype=torch.int32, device=self.device)
+            logp, top1, seq = buf[:n].view(torch.float32), buf[n:2 * n] if top1_on else None, buf[2 * n:2 * n + B].view(torch.float32)
+            self._ck(self.lib.lxo_score_tokens(self.sref(), _p(self.ws), _p(self._formula), _p(ln_dev), _p(logp), _p(top1), _p(seq),
+                                               self._stream()), "score_tokens")
+            if chain:
+                buf[2 * n + B:].copy_(self.region("xdec_sync", "i32")[:8 * 64 + 1])
+            h = buf.cpu().numpy()
+            out = (h[:n].view(np.float32).reshape(B, T)[:live].copy(), h[n:2 * n].reshape(B, T)[:live].copy() if top1_on else None,
+                   h[2 * n:2 * n + B].view(np.float32)[:live].copy())
+            if chain:
+                # a chain that did not assemble (forward() checks the first one itself): the launch-per-step kernels from now on, and
+                # this piece again
+                w = h[2 * n + B:]
+                used, err = bool(w[32:512:64].any()), int(w[512])
+                self.chain_used = used and not err
+                if err:
+                    self._chain_fallback("forward", err)
+                    continue
+            return out
+
     # --------------------------------------------------------------- decode --
     def _encode_only(self, img, beam):
         B, H, W = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])

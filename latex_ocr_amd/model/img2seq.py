@@ -16,10 +16,12 @@ from .utils.text import pad_batch_formulas
 
 
 class Img2SeqModel(BaseModel):
-    def __init__(self, config, dir_output, vocab):
-        """Reference: model/img2seq.py:23-32."""
+    def __init__(self, config, dir_output, vocab, lib=None):
+        """Reference: model/img2seq.py:23-32.  lib: a bound library to drive instead of liblxo.so (_abi.bind; the engine then runs on
+        config.device, default "cpu" -- the host build of the sources under test)."""
         super(Img2SeqModel, self).__init__(config, dir_output)
         self._vocab = vocab
+        self._lib = lib
         self.dist = None            # latex_ocr_amd.dist.DataParallel when launched one process per GPU (attach_dist)
 
     def attach_dist(self, dist):
@@ -31,9 +33,12 @@ class Img2SeqModel(BaseModel):
     def _build_engine(self):
         from ..engine import Engine
         cfg = self._config
+        lib = getattr(self, "_lib", None)
+        dev = str(getattr(cfg, "device", ""))
         self.engine = Engine(self._vocab.n_tok, dims=dims_from_config(cfg),
                              dtype=getattr(cfg, "compute_dtype", "bf16"),
-                             device=getattr(cfg, "device", "cuda:0") if str(getattr(cfg, "device", "")).startswith("cuda") else "cuda:0",
+                             device=dev if dev.startswith("cuda") else ("cuda:0" if lib is None else dev or "cpu"),
+                             lib=lib,
                              seed=getattr(cfg, "seed", 0),
                              beam=getattr(cfg, "beam_size", 1) if getattr(cfg, "decoding", "greedy") == "beam_search" else 1,
                              max_steps=getattr(cfg, "max_length_formula", 150) + 2)
@@ -180,6 +185,25 @@ class Img2SeqModel(BaseModel):
                 p = truncate_end(pred, self._vocab.id_end)
                 hyps[i].append(" ".join(self._vocab.id_to_tok[int(idx)] for idx in p))
         return hyps
+
+    def score_batch(self, images, formulas):
+        """Teacher-forced scores of given transcriptions (Engine.score): formulas are token-id lists or space-separated token strings
+        (Vocab.form_prepro: unknown tokens -> id_unk), padded as _get_feed_dict pads a training batch, so the END the reference appends is
+        scored too.  -> one (sequence log-prob, [token log-probs incl. END], first position where the model's top-1 differs from the
+        formula or -1) per (image, formula) pair."""
+        if len(images) != len(formulas):
+            raise ValueError("score_batch: %d images but %d formulas" % (len(images), len(formulas)))
+        prepro = self._vocab.form_prepro
+        forms = [prepro(f) if isinstance(f, str) else [int(x) for x in f] for f in formulas]
+        fd = self._get_feed_dict(images, formula=forms, dropout=1)
+        f, ln = fd["formula"], fd["formula_length"]
+        logp, top1, seq = self.engine.score(fd["img"], f, ln, return_top1=True)
+        out = []
+        for b in range(len(forms)):
+            n = int(ln[b])
+            diff = np.flatnonzero(top1[b, :n] != f[b, :n])
+            out.append((float(seq[b]), [float(x) for x in logp[b, :n]], int(diff[0]) if diff.size else -1))
+        return out
 
     def _predict_scored(self, images):
         fd = self._get_feed_dict(images, dropout=1)

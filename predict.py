@@ -2,7 +2,9 @@
 """Prediction driver with the shape of the reference's predict.py:38-68: restore the trained model from a results
 directory and print the LaTeX hypothesis for each image path given (the reference's interactive shell and its
 pdf/LaTeX->PNG cropping helpers are out of scope).  --scores adds the hypothesis' log-prob and its geometric-mean token
-probability exp(log-prob / tokens) (Img2SeqModel.predict_batch(..., return_scores=True))."""
+probability exp(log-prob / tokens) (Img2SeqModel.predict_batch(..., return_scores=True)).  --formula "<tokens>" (one image) scores
+that transcription instead of decoding: its log-prob (END included), geometric-mean token probability and the first position where
+the model's top-1 token differs from it (Img2SeqModel.score_batch)."""
 import argparse
 
 import numpy as np
@@ -17,8 +19,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--results", default="results/small/")
     ap.add_argument("--scores", action="store_true", help="print the log-prob and the geometric-mean token probability of each hypothesis")
+    ap.add_argument("--formula", default=None, help="score this space-separated token sequence against the (single) image")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
+    if a.formula is not None and len(a.images) != 1:
+        ap.error("--formula scores one image")
     d = a.results
     config_vocab, config_model = Config(d + "vocab.json"), Config(d + "model.json")
     vocab = Vocab(config_vocab)
@@ -28,6 +33,11 @@ def main(argv=None):
     out = []
     for path in a.images:
         img = np.asarray(Image.open(path).convert("RGB"))
+        if a.formula is not None:
+            lp, toks, first = model.score_batch([greyscale(img)], [a.formula])[0]
+            print(path, "<=", a.formula, "\tlogp %.4f\tgeo-mean p %.4f\tfirst disagreement %d" % (lp, np.exp(lp / max(1, len(toks))), first))
+            out.append((lp, toks, first))
+            continue
         if a.scores:
             hyps, scores = model.predict_batch([greyscale(img)], return_scores=True)
             hyps = [h[0] for h in hyps]
