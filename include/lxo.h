@@ -104,7 +104,8 @@ typedef struct lxo_shape {
     int B, H, W, T, V;
     int C, E, U, O, D;
     int dtype;      /* LXO_F32 (parity mode) or LXO_BF16 (bf16 storage, f32 accumulate) */
-    int beam;       /* decode only: beam width the workspace is sized for (>= 1) */
+    int beam;       /* decode only: beam width the workspace is sized for (>= 1); beam decode takes 2 .. min(16, V) (lxo_beam_decode and
+                     * lxo_decode_begin refuse a wider beam: at time 0 only V candidates exist) */
     int max_steps;  /* decode only: step capacity (max_length_formula + 2) */
     /* training only: tf.nn.dropout keep probability on h and o (attention_cell.py:72,83; config.dropout,
      * fed at img2seq.py:166) and the seed of this step's counter-based masks; 0 or >= 1 disables */
@@ -218,7 +219,8 @@ int lxo_set_encoder_side_stream(void* stream);
 int lxo_decoder_train_fwd(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                           const int32_t* formula, void* stream);
 /* loss of model/img2seq.py:68-75 and d(loss)/d(logits).  inv_ntok = 1 / (number of
- * unmasked tokens in the GLOBAL batch).  ws region "loss" = {sum CE, token count}. */
+ * unmasked tokens in the GLOBAL batch).  ws region "loss" = {sum CE, token count}.  Target ids outside [0, V) are
+ * clamped into it (< 0 -> 0, >= V -> V - 1), as lxo_score_tokens does; d(logits) is 0 in the padding columns [V, Vp). */
 int lxo_ce_loss_fwd_bwd(const lxo_shape* s, void* ws, const int32_t* formula,
                         const int32_t* lengths, float inv_ntok, void* stream);
 /* The same with the GLOBAL token count read from device memory (*ntok_dev, a float): under data parallelism the count is

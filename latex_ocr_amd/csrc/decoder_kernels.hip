@@ -2325,7 +2325,7 @@ int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, i
                     float* scratch, float* logp, int* finished,
                     int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
                     float* scores_out) {
-    if (k > 16) return -2;
+    if (k > 16 || k > V) return -2;                            // k > V: at time 0 only V candidates exist -- a k-th selection would have no index
     DivPen dp = {0.f, 0u, (unsigned)div_seed, scratch};
     if (div_gamma > 0.f && div_gamma != 1.f && div_prob > 0.f) {      // the reference returns early for gamma == 1 or prob == 0
         dp.log_gamma = logf(div_gamma);

@@ -848,7 +848,7 @@ int lxo_impl_decode_cell_step(const Plan& P, const float* prm, const void* wp, v
 // finalize) is bound to.  State (c, h, o, running log-probs, finished flags, previous ids) stays in the workspace. ----
 int lxo_impl_decode_begin(const Plan& P, const float* prm, const void* wp, void* ws, hipStream_t st) {
     const int B = P.s.B, k = P.s.beam > 1 ? P.s.beam : 1, nv = B * k;
-    if (P.s.max_steps < 1 || k > 16) return -5;
+    if (P.s.max_steps < 1 || k > 16 || k > P.s.V) return -5;
     RC(attention_prepare(P, prm, wp, ws, k, st));
     if (P.att_exp()) RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)B * P.R * P.s.E, st));      // bf16 decode: E_x = e^{2 att_img}, once per call
     if (fused_steps(P)) RC(mirror_oh(P, ws, 0, nv, st));
@@ -861,7 +861,7 @@ int lxo_impl_decode_begin(const Plan& P, const float* prm, const void* wp, void*
 int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int time,
                          int* ids_out, int* parents_out, int* finished_out, int* unfinished_host, hipStream_t st) {
     const int B = P.s.B, k = P.s.beam > 1 ? P.s.beam : 1, nv = B * k, ms = P.s.max_steps, U = P.s.U;
-    if (time < 0 || time >= ms) return -5;
+    if (time < 0 || time >= ms || k > 16 || k > P.s.V) return -5;
     int* flags = P.ws<int>(ws, W_DEC_FLAGS);
     int* finished = flags + 64;
     int* ids_step = P.ws<int>(ws, W_DEC_IDS);
@@ -891,7 +891,7 @@ int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* 
 int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter,
                          int* ids_out, int* parents_out, float* alpha_out, int* steps_out, hipStream_t st, float* scores_out) {
     const int B = P.s.B, k = P.s.beam, ms = P.s.max_steps, nv = B * k, U = P.s.U;
-    if (ms < max_iter + 1 || k < 1 || k > 16) return -5;
+    if (ms < max_iter + 1 || k < 1 || k > 16 || k > P.s.V) return -5;      // k > V: fewer first-step candidates than hypotheses
     RC(attention_prepare(P, prm, wp, ws, k, st));
     if (P.att_exp()) RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)B * P.R * P.s.E, st));      // bf16: E_x = e^{2 att_img}, once per call
     if (fused_steps(P)) RC(mirror_oh(P, ws, 0, nv, st));

@@ -725,9 +725,18 @@ class Engine(object):
             return ids[:, :n].cpu().numpy(), a, logp[:, :n].cpu().numpy()
         return ids[:, :n].cpu().numpy(), a
 
+    def _check_beam(self, beam_size):
+        """a beam wider than the vocabulary has no k-th candidate at time 0 (tf.nn.top_k raises there too); the kernels take k <= 16"""
+        k = int(beam_size)
+        if k > self.n_tok:
+            raise ValueError("beam width %d exceeds the vocabulary size %d" % (k, self.n_tok))
+        if k > 16:
+            raise ValueError("beam width %d exceeds 16, the widest beam the decode kernels take" % k)
+
     # one step at a time: what model/components (the reference's decoder-cell protocol) drives
     def decode_begin(self, img, beam_size=1, max_steps=152, div_gamma=1.0, div_prob=0.0, div_seed=0):
         """initialize(): encoder + attention set-up + initial states for beam_size hypotheses per image."""
+        self._check_beam(beam_size)
         if self.max_steps < max_steps:
             self.max_steps, self.ws = int(max_steps), None
         B = self._encode_only(img, int(beam_size))
@@ -798,6 +807,7 @@ class Engine(object):
         step t (lxo_beam_decode_attn; the rows the reference's py_func tap sees under config.decoding = "beam_search").
         return_scores: -> (ids, parents, scores) or (ids, parents, alpha, scores), scores f32 [B, T', k] = the running log-prob of slot k after
         step t (the beam state's log_probs; lxo_beam_decode_scores): the log-prob of the sequence that back-traces from (t, k)."""
+        self._check_beam(beam_size)
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B = self._encode_only(img, int(beam_size))

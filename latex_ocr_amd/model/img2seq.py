@@ -244,7 +244,8 @@ class Img2SeqModel(BaseModel):
         Beam search: the reference's visualiser draws row 0 of the merged batch x beam tensor of every step (`attentionVector[0]`,
         visualize_attention.py:55), for every step the loop ran -- it ends when ALL beams have finished, so there are more slices than tokens
         in the best hypothesis (51 slices for 48 tokens at k = 2); that is what comes back here.  With the
-        `beam_backtrace` extension each step's map is the one of the row its best token was read off (parents[t][0])."""
+        `beam_backtrace` extension each step's map is the one of the row the back-traced best hypothesis read its token off: walking
+        back from slot 0 at the last step, the parent of the path's slot at that step (utils/text.beam_slots)."""
         fd = self._get_feed_dict([img], dropout=1)
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1
@@ -254,8 +255,9 @@ class Img2SeqModel(BaseModel):
                                                       div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0),
                                                       div_seed=self._div_calls, return_attention=True)
             if getattr(cfg, "beam_backtrace", False):
-                from .utils.text import beam_backtrace
-                maps = np.stack([alpha[0, t, par[0, t, 0]] for t in range(alpha.shape[1])])
+                from .utils.text import beam_backtrace, beam_slots
+                slot = beam_slots(par)[0, :, 0]
+                maps = np.stack([alpha[0, t, par[0, t, slot[t]]] for t in range(alpha.shape[1])])
                 ids = beam_backtrace(ids, par)
             else:
                 maps = alpha[0, :, 0]

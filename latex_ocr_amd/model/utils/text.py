@@ -100,12 +100,20 @@ def beam_backtrace(ids, parents):
     The reference's BeamSearchDecoderCell.finalize (beam_search_decoder_cell.py:190-250) never does this (it
     returns ids[:, t, i] per step); this is the optional corrected read-out."""
     import numpy as np
-    ids, parents = np.asarray(ids), np.asarray(parents)
-    B, T, k = ids.shape
-    out = np.empty_like(ids)
-    slot = np.tile(np.arange(k)[None, :], (B, 1))
+    return np.take_along_axis(np.asarray(ids), beam_slots(parents), axis=2)
+
+
+def beam_slots(parents):
+    """The slot walk behind beam_backtrace: parents int [B, T, k] -> slots int [B, T, k], slots[b, t, i] = the beam slot at step t of
+    the hypothesis that ends in slot i at the last step.  Its token at step t is ids[b, t, slots[b, t, i]]; the decoder row that step
+    read it off (the row whose attention map produced it) is its parent, parents[b, t, slots[b, t, i]]."""
+    import numpy as np
+    parents = np.asarray(parents)
+    B, T, k = parents.shape
+    out = np.empty_like(parents)
+    slot = np.tile(np.arange(k, dtype=parents.dtype)[None, :], (B, 1))
     rows = np.arange(B)[:, None]
     for t in range(T - 1, -1, -1):
-        out[:, t, :] = ids[rows, t, slot]
+        out[:, t, :] = slot
         slot = parents[rows, t, slot]
     return out

@@ -100,6 +100,61 @@ def test_beam_backtrace_follows_parents():
     assert out[0, :, 1].tolist() == [5, 7, 3]
 
 
+def test_beam_slots_walk():
+    from latex_ocr_amd.model.utils.text import beam_backtrace, beam_slots
+    # three beams, four steps, two images: image 0's best path leaves slot 0 (slot 0 at t=3 extends slot 2, which extends slot 0, which
+    # extends slot 2 of t=0)
+    par = np.array([[[0, 0, 0], [2, 0, 1], [1, 2, 0], [2, 0, 0]],
+                    [[0, 0, 0], [0, 1, 2], [0, 1, 2], [0, 1, 2]]])      # image 1: every slot keeps its own line (its t=0 row: any, all copies of row 0)
+    slots = beam_slots(par)
+    assert slots.shape == par.shape
+    assert slots[0, :, 0].tolist() == [2, 0, 2, 0]                        # t=3: 0; t=2: par[3][0] = 2; t=1: par[2][2] = 0; t=0: par[1][0] = 2
+    assert slots[0, :, 0].tolist() != [0, 0, 0, 0]
+    assert slots[0, :, 1].tolist() == [0, 1, 0, 1] and slots[0, :, 2].tolist() == [0, 1, 0, 2]
+    assert (slots[1] == np.arange(3)[None, :]).all()
+    ids = np.arange(2 * 4 * 3).reshape(2, 4, 3) + 100
+    out = beam_backtrace(ids, par)
+    for b in range(2):
+        for i in range(3):
+            assert out[b, :, i].tolist() == [ids[b, t, slots[b, t, i]] for t in range(4)]
+    sc = -np.arange(24, dtype=np.float32).reshape(2, 4, 3)
+    assert beam_backtrace(sc, par).dtype == np.float32
+
+
+def test_predict_with_attention_follows_the_backtraced_path():
+    """with config.beam_backtrace the map of step t is the one of the decoder row that produced the back-traced token: the parent of
+    the path's slot at t -- not the parent of slot 0, which belongs to another hypothesis once the path leaves slot 0"""
+    from latex_ocr_amd.model.img2seq import Img2SeqModel
+    from latex_ocr_amd.model.utils.general import Config
+    par = np.array([[[0, 0, 0], [2, 0, 1], [1, 2, 0], [2, 0, 0]]], np.int32)
+    ids = np.array([[[1, 2, 3], [4, 5, 6], [7, 8, 9], [10, 11, 12]]], np.int32)
+    alpha = np.zeros((1, 4, 3, 2, 5), np.float32)
+    for t in range(4):
+        for j in range(3):
+            alpha[0, t, j] = 10 * t + j                                     # map of row j at step t, recognisable by value
+
+    class Eng(object):
+        def beam_decode(self, img, id_end, beam_size, **kw):
+            assert kw.get("return_attention") and beam_size == 3
+            return ids, par, alpha
+
+    class Voc(object):
+        id_end = 99
+        id_to_tok = {i: "t%d" % i for i in range(100)}
+
+    m = Img2SeqModel.__new__(Img2SeqModel)
+    m._config = Config({"decoding": "beam_search", "beam_size": 3, "beam_backtrace": True, "max_length_formula": 3})
+    m._vocab, m.engine = Voc(), Eng()
+    text, maps = m.predict_with_attention(np.zeros((32, 48), np.uint8))
+    # the path ending in slot 0: slots [2, 0, 2, 0] at t = 0..3, tokens ids[t][slot]; rows read = par[t][slot] = [0, 2, 0, 2]
+    assert text == "t3 t4 t9 t10"
+    assert [float(maps[t, 0, 0]) for t in range(4)] == [0.0, 12.0, 20.0, 32.0]
+    assert [float(alpha[0, t, par[0, t, 0], 0, 0]) for t in range(4)] == [0.0, 12.0, 21.0, 32.0]     # the old read-out (parent of slot 0) differs at t=2
+    m._config = Config({"decoding": "beam_search", "beam_size": 3, "beam_backtrace": False, "max_length_formula": 3})
+    text, maps = m.predict_with_attention(np.zeros((32, 48), np.uint8))
+    assert text == "t1 t4 t7 t10" and [float(maps[t, 0, 0]) for t in range(4)] == [0.0, 10.0, 20.0, 30.0]     # the reference's row 0
+
+
 def test_encoder_out_hw_and_attention_overlay(tmp_path):
     from PIL import Image
     from latex_ocr_amd.model.utils.image import encoder_out_hw
