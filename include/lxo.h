@@ -308,6 +308,16 @@ int lxo_greedy_decode_attn(const lxo_shape* s, const float* params, const void* 
  * (its ids are those of lxo_greedy_decode); the launch-per-step fall-back rewrites them with the ids. */
 int lxo_greedy_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
                              int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream);
+/* Greedy decode from a given prefix.  prefix int32 [B, prefix_ld] and prefix_len int32 [B] (device, NOT NULL, prefix_ld >= 1): at a
+ * step t < P_b = prefix_len[b] row b emits prefix[b][t] (fed to step t + 1 like any emitted id) and stays unfinished; from step P_b on it
+ * is lxo_greedy_decode's arg-max step.  The loop ends, as there, after the first step that leaves no row unfinished or after step max_iter.
+ * Contract: 0 <= P_b <= min(prefix_ld, max_iter), prefix ids in [0, V) and never id_end; rows may differ in P_b.  What the device holds
+ * is read defensively (a length is clamped into that range, an id outside [0, V) reads as 0): nothing faults.  logp_out (nullable):
+ * as in lxo_greedy_decode_scores; at a forced step, the log-prob of the forced id.  alpha_out (nullable): as in lxo_greedy_decode_attn
+ * (the launch-per-step path).  With every P_b = 0 the outputs are those of lxo_greedy_decode(_scores). */
+int lxo_greedy_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                             const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                             int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream);
 /* The same loops ONE STEP AT A TIME: the calls behind the reference's decoder-cell protocol (dynamic_decode.py:35-36,43-44:
  * decoder_cell.initialize() / .step(time, state, inputs, finished); greedy_decoder_cell.py:46-66,
  * beam_search_decoder_cell.py:113-187).  latex_ocr_amd/model/components/ wraps them in cell objects with the reference's
@@ -356,6 +366,14 @@ int lxo_beam_decode_attn(const lxo_shape* s, const float* params, const void* wp
  * With the diversity penalty on (div_gamma, div_prob) the scores include it, as the reference's state does.  Columns >= *steps_out
  * are unspecified.  alpha_out: as in lxo_beam_decode_attn, or NULL for none.  ids_out / parents_out are those of lxo_beam_decode. */
 int lxo_beam_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                           int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream);
+/* Beam decode from a given prefix (prefix, prefix_ld, prefix_len per image, as in lxo_greedy_decode_prefix).  At a step t < P_b every slot j
+ * of image b takes prefix[b][t] with parent j and its running log-prob grows by that id's log-prob (no diversity penalty): the k slots stay
+ * identical.  Step P_b selects its top-k over slot 0 alone, as step 0 does without a prefix; later steps over all k V candidates.  The
+ * diversity penalty's hash keeps the global step index.  scores_out (nullable): as in lxo_beam_decode_scores.  With every P_b = 0 the
+ * outputs are those of lxo_beam_decode(_scores). */
+int lxo_beam_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                           const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
                            int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream);
 
 /* ---- data parallel: one process per GPU, RCCL over xGMI -------------------------------------

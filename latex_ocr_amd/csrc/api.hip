@@ -190,6 +190,16 @@ extern "C" int lxo_greedy_decode_scores(const lxo_shape* s, const float* params,
                  "lxo_greedy_decode_scores");
     return 0;
 }
+extern "C" int lxo_greedy_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                        const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                        int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    if (!prefix || !prefix_len || prefix_ld < 1) return fail(-1, "lxo_greedy_decode_prefix: null prefix / prefix_len or prefix_ld < 1");
+    const DecPrefix pf = {prefix, prefix_len, prefix_ld, prefix_ld < max_iter ? prefix_ld : max_iter};
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, ids_out, alpha_out, steps_out, (hipStream_t)stream, logp_out, &pf),
+                 "lxo_greedy_decode_prefix");
+    return 0;
+}
 extern "C" int lxo_decode_begin(const lxo_shape* s, const float* params, const void* wpack, void* ws, void* stream) {
     MAKE_PLAN(P, s);
     CHECK_LAUNCH(lxo_impl_decode_begin(P, params, wpack, ws, (hipStream_t)stream), "lxo_decode_begin");
@@ -221,6 +231,16 @@ extern "C" int lxo_beam_decode_scores(const lxo_shape* s, const float* params, c
     if (!scores_out) return fail(-1, "lxo_beam_decode_scores: null scores_out");
     CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, alpha_out, steps_out, (hipStream_t)stream, scores_out),
                  "lxo_beam_decode_scores");
+    return 0;
+}
+extern "C" int lxo_beam_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                      const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                      int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    if (!prefix || !prefix_len || prefix_ld < 1) return fail(-1, "lxo_beam_decode_prefix: null prefix / prefix_len or prefix_ld < 1");
+    const DecPrefix pf = {prefix, prefix_len, prefix_ld, prefix_ld < max_iter ? prefix_ld : max_iter};
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, alpha_out, steps_out, (hipStream_t)stream, scores_out, &pf),
+                 "lxo_beam_decode_prefix");
     return 0;
 }
 

@@ -1501,11 +1501,20 @@ __global__ __launch_bounds__(256) void init_bwd_kernel(const float* __restrict__
 }
 
 // ---- decode ----
+// Forced prefix (PF instantiations of the decode kernels, DecPrefix in decoder_kernels.h): row r emits ids[r][t] at steps t < len[r].  What
+// the device holds is read defensively -- a length is clamped into [0, lim], lim = min(ld, max_iter), and an id outside [0, V) is read as
+// 0 -- so that no caller error faults.
+LXO_DEV int pfx_len(const DecPrefix& q, int r) { return min(max(q.len[r], 0), q.lim); }
+LXO_DEV int pfx_id(const DecPrefix& q, int r, int t, int V) { const int f = q.ids[(long long)r * q.ld + t]; return (f >= 0 && f < V) ? f : 0; }
+
 // greedy_decoder_cell.py:58-64: id = argmax (first max), finished |= id == END; one wave per row.
 // logp_out (nullable) [n][max_steps]: log_softmax(logits)[id] = logits[id] - lse, the log-sum-exp from one more pass over the row the wave has read
+// PF: at a step inside its prefix a row emits the forced id f (logp: logits[f] - lse) and stays unfinished
+template <bool PF>
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int Vp, int V, int n, int id_end,
                                                     int* __restrict__ ids_step, int* __restrict__ ids_out, int max_steps, int step,
-                                                    int* __restrict__ finished, int* __restrict__ n_unfinished, float* __restrict__ logp_out) {
+                                                    int* __restrict__ finished, int* __restrict__ n_unfinished, float* __restrict__ logp_out,
+                                                    DecPrefix pf) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
@@ -1517,18 +1526,22 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
         const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
         if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
     }
+    int fi = -1;                                               // PF: the forced id of this step (-1: a free step)
+    if constexpr (PF) { if (step < pfx_len(pf, row)) fi = pfx_id(pf, row, step, V); }
     float lp = 0.f;
     if (logp_out) {
         float l = 0.f;
         for (int j = lane; j < V; j += 64) l += expf(lg[j] - best);
         lp = -logf(wave_sum(l));                               // logits[id] - (best + log l), logits[id] = best
+        if constexpr (PF) { if (fi >= 0) lp += lg[fi] - best; }
     }
     if (lane == 0) {
         if (bi >= V) bi = 0;
+        if constexpr (PF) { if (fi >= 0) bi = fi; }
         if (logp_out) logp_out[(long long)row * max_steps + step] = lp;
         ids_step[row] = bi;
         ids_out[(long long)row * max_steps + step] = bi;
-        const int f = finished[row] | (bi == id_end ? 1 : 0);
+        const int f = finished[row] | (bi == id_end && fi < 0 ? 1 : 0);
         finished[row] = f;
         if (!f) atomicAdd(n_unfinished, 1);
     }
@@ -1541,12 +1554,27 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
 // rank = position of the entry in the descending sort of its hypothesis' V scores (ties: lower id first, as
 // tf.nn.top_k orders them).  Bernoulli draws: the counter hash of drop_scale on (time, image, beam, id).
 struct DivPen { float log_gamma; unsigned thr; unsigned seed; float* scratch; };   // log_gamma == 0 or thr == 0: off
+// PF (both beam kernels): at a step t < P inside image b's prefix every slot j takes the forced id with parent j, its running log-prob grows by
+// that id's log-prob, no diversity penalty -- the k slots stay identical, as in the initial state.  Step P selects over slot 0 alone (what
+// time 0 does without a prefix), later steps over all k V candidates.
+LXO_DEV void beam_forced_out(int b, int k, int tid, int time, int id, float v, int fin, int* ids_step, int* parents_step, int* ids_out, int* par_out,
+                             int max_steps, float* scores_out, float* logp, int* finished, int* n_unfinished) {
+    ids_step[b * k + tid] = id;
+    parents_step[b * k + tid] = tid;
+    ids_out[((long long)b * max_steps + time) * k + tid] = id;
+    if (par_out) par_out[((long long)b * max_steps + time) * k + tid] = tid;
+    if (scores_out) scores_out[((long long)b * max_steps + time) * k + tid] = v;
+    logp[b * k + tid] = v;
+    finished[b * k + tid] = fin;
+    if (!fin) atomicAdd(n_unfinished, 1);
+}
 
+template <bool PF>
 __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logits, int Vp, int V, int k, int id_end, int time, DivPen dp,
                                                        float* __restrict__ logp, int* __restrict__ finished,
                                                        int* __restrict__ ids_step, int* __restrict__ parents_step,
                                                        int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                       int* __restrict__ n_unfinished, float* __restrict__ scores_out) {
+                                                       int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf) {
     __shared__ float lse[16];
     __shared__ float cand_v[16 * 4]; __shared__ int cand_i[16 * 4];
     __shared__ float sel_v[16]; __shared__ int sel_i[16];
@@ -1566,7 +1594,19 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
     }
     if (tid < k) fin_old[tid] = finished[b * k + tid];
     __syncthreads();
-    const int nb = time > 0 ? k : 1;
+    int t0 = 0;                                                // PF: the image's prefix length -- its beam search starts there
+    if constexpr (PF) {
+        t0 = pfx_len(pf, b);
+        if (time < t0) {
+            if (tid < k) {
+                const int id = pfx_id(pf, b, time, V);
+                beam_forced_out(b, k, tid, time, id, logp[b * k + tid] + (logits[((long long)b * k + tid) * Vp + id] - lse[tid]), fin_old[tid],
+                                ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
+            }
+            return;
+        }
+    }
+    const int nb = time > t0 ? k : 1;
     const int total = nb * V;
     const bool div = dp.log_gamma != 0.f && dp.thr != 0u;
     float* pen = dp.scratch + (long long)b * k * Vp;
@@ -1678,11 +1718,12 @@ LXO_DEV void wave_argmax(float& v, int& i) {
     }
 }
 #endif
+template <bool PF>
 __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __restrict__ logits, int Vp, int V, int k, int id_end, int time,
                                                             float* __restrict__ logp, int* __restrict__ finished,
                                                             int* __restrict__ ids_step, int* __restrict__ parents_step,
                                                             int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                            int* __restrict__ n_unfinished, float* __restrict__ scores_out) {
+                                                            int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf) {
     __shared__ float lse[16];
     __shared__ float sel_v[16]; __shared__ int sel_i[16];
     __shared__ int fin_old[16];
@@ -1690,7 +1731,9 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float FMIN = -3.40282347e38f;
     __shared__ float wc_v[BS_NW * 16]; __shared__ int wc_i[BS_NW * 16];      // the waves' k best each
-    const int nb = time > 0 ? k : 1;
+    int t0 = 0;                                                // PF: the image's prefix length (beam_step_kernel)
+    if constexpr (PF) t0 = pfx_len(pf, b);
+    const int nb = time > t0 ? k : 1;
     const int total = nb * V;
     float raw[BS_NPT];                                         // raw logits of this thread's candidates (unconditional, clamped: requested before anything is waited for)
     {
@@ -1755,6 +1798,16 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
     }
     if (tid < k) { fin_old[tid] = finished[b * k + tid]; lp_old[tid] = logp[b * k + tid]; }
     __syncthreads();
+    if constexpr (PF) {
+        if (time < t0) {
+            if (tid < k) {
+                const int id = pfx_id(pf, b, time, V);
+                beam_forced_out(b, k, tid, time, id, lp_old[tid] + (logits[((long long)b * k + tid) * Vp + id] - lse[tid]), fin_old[tid],
+                                ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
+            }
+            return;
+        }
+    }
     // candidates of this thread: i = tid + BS_TH u -> (hypothesis, id) walked instead of divided; their raw logits were requested in front of the
     // log-sum-exp pass (raw[]: the second read of the rows no longer waits behind the first)
     float val[BS_NPT];
@@ -2317,14 +2370,17 @@ int lxo_k_init_bwd(const float* dcc, Slabs dxh, const float* c0, const float* re
     DONE;
 }
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
-                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out) {
-    LAUNCH(argmax_kernel, cdiv(n, 4), logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out);
+                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out, const DecPrefix* prefix) {
+    if (prefix)
+        LAUNCH(argmax_kernel<true>, cdiv(n, 4), logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, *prefix);
+    else
+    LAUNCH(argmax_kernel<false>, cdiv(n, 4), logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, DecPrefix{});
     DONE;
 }
 int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
                     float* scratch, float* logp, int* finished,
                     int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
-                    float* scores_out) {
+                    float* scores_out, const DecPrefix* prefix) {
     if (k > 16 || k > V) return -2;                            // k > V: at time 0 only V candidates exist -- a k-th selection would have no index
     DivPen dp = {0.f, 0u, (unsigned)div_seed, scratch};
     if (div_gamma > 0.f && div_gamma != 1.f && div_prob > 0.f) {      // the reference returns early for gamma == 1 or prob == 0
@@ -2333,10 +2389,16 @@ int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, i
     }
     static int fast = -1;                                      // LXO_BEAM_FAST=0: the general kernel always (A/B)
     if (fast < 0) { const char* e = getenv("LXO_BEAM_FAST"); fast = (e && e[0] == '0') ? 0 : 1; }
-    if (fast && dp.log_gamma == 0.f && (long long)k * V <= BS_TH * BS_NPT && k * BS_NW <= 64)
-        hipLaunchKernelGGL(beam_step_fast_kernel, dim3(nimg), dim3(BS_TH), 0, st, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out);
+    const DecPrefix pf = prefix ? *prefix : DecPrefix{};
+    if (fast && dp.log_gamma == 0.f && (long long)k * V <= BS_TH * BS_NPT && k * BS_NW <= 64) {
+        if (prefix)
+            hipLaunchKernelGGL(beam_step_fast_kernel<true>, dim3(nimg), dim3(BS_TH), 0, st, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
+        else
+        hipLaunchKernelGGL(beam_step_fast_kernel<false>, dim3(nimg), dim3(BS_TH), 0, st, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
+    } else if (prefix)
+        LAUNCH(beam_step_kernel<true>, nimg, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
     else
-    LAUNCH(beam_step_kernel, nimg, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out);
+    LAUNCH(beam_step_kernel<false>, nimg, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
     DONE;
 }
 int lxo_k_beam_gather(float* rec, int ldr, int XH, float* cs, int U, const int* parents, int k, float* tmp_rec, float* tmp_cs, int n, void* recb, int ldrb, hipStream_t st) {

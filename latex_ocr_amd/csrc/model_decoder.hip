@@ -740,9 +740,10 @@ static int decode_loop_chunked(int max_iter, int CHUNK, int* flags, hipStream_t 
 }
 
 int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter,
-                           int* ids_out, float* alpha_out, int* steps_out, hipStream_t st, float* logp_out) {
+                           int* ids_out, float* alpha_out, int* steps_out, hipStream_t st, float* logp_out, const DecPrefix* prefix) {
     const int B = P.s.B, ms = P.s.max_steps;
     if (ms < max_iter + 1) return -5;
+    if (prefix && (!prefix->ids || !prefix->len || prefix->ld < 1)) return -5;
     RC(attention_prepare(P, prm, wp, ws, 1, st));
     if (P.att_exp()) RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)B * P.R * P.s.E, st));      // bf16: E_x = e^{2 att_img}, once per call
     if (fused_steps(P)) RC(mirror_oh(P, ws, 0, B, st));
@@ -765,6 +766,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
         x.rec = P.ws<float>(ws, W_REC); x.recb = P.ws<bf16_t>(ws, W_RECB); x.cs = P.ws<float>(ws, W_CS);
         x.part = P.ws<float>(ws, W_APART); x.sync = P.ws<unsigned>(ws, W_XSYNC);
         x.ids_step = ids_step; x.ids_out = ids_out; x.logp_out = logp_out; x.finished = finished;
+        if (prefix) { x.prefix = prefix->ids; x.prefix_len = prefix->len; x.prefix_ld = prefix->ld; x.prefix_lim = prefix->lim; }
         x.B = B; x.R = P.R; x.REC = P.REC; x.RECB = P.RECB; x.V = P.s.V; x.id_end = id_end; x.max_steps = ms;
         x.t0 = 0; x.nsteps = 1; x.unfinished = flags;
         x.stop = ids_step + B;                            // one word behind the fed-back ids (region "dec_ids" holds B x max_steps ints)
@@ -800,7 +802,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
         RC(decode_common_step(P, prm, wp, ws, B, 1, cur, time == 0 ? nullptr : ids_step, st));
         if (alpha_out)      // attention weights of this step (what attention_mechanism.py:96-105 hands to its py_func hook)
             HIPRC(hipMemcpyAsync(alpha_out + (size_t)time * B * P.Rp, P.ws<float>(ws, W_ALPHA), (size_t)B * P.Rp * 4, hipMemcpyDeviceToDevice, st));
-        RC(lxo_k_argmax(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, id_end, ids_step, ids_out, ms, time, finished, unfinished, st, logp_out));
+        RC(lxo_k_argmax(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, id_end, ids_step, ids_out, ms, time, finished, unfinished, st, logp_out, prefix));
         return 0;
     }));
     return 0;
@@ -889,9 +891,10 @@ int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* 
 }
 
 int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter,
-                         int* ids_out, int* parents_out, float* alpha_out, int* steps_out, hipStream_t st, float* scores_out) {
+                         int* ids_out, int* parents_out, float* alpha_out, int* steps_out, hipStream_t st, float* scores_out, const DecPrefix* prefix) {
     const int B = P.s.B, k = P.s.beam, ms = P.s.max_steps, nv = B * k, U = P.s.U;
     if (ms < max_iter + 1 || k < 1 || k > 16 || k > P.s.V) return -5;      // k > V: fewer first-step candidates than hypotheses
+    if (prefix && (!prefix->ids || !prefix->len || prefix->ld < 1)) return -5;
     RC(attention_prepare(P, prm, wp, ws, k, st));
     if (P.att_exp()) RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)B * P.R * P.s.E, st));      // bf16: E_x = e^{2 att_img}, once per call
     if (fused_steps(P)) RC(mirror_oh(P, ws, 0, nv, st));
@@ -919,7 +922,7 @@ int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* 
             HIPRC(hipMemcpyAsync(alpha_out + (size_t)time * nv * P.Rp, P.ws<float>(ws, W_ALPHA), (size_t)nv * P.Rp * 4, hipMemcpyDeviceToDevice, st));
         RC(lxo_k_beam_step(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, k, id_end, time, P.s.div_gamma, P.s.div_prob, P.s.div_seed, tmp,
                            logp, finished, ids_step, par_step,
-                           ids_out, parents_out, ms, unfinished, st, scores_out));
+                           ids_out, parents_out, ms, unfinished, st, scores_out, prefix));
         if (!indirect)
         RC(lxo_k_beam_gather(rec + (size_t)cur * nv * P.REC, P.REC, P.XH, cs + (size_t)cur * nv * U, U, par_step, k,
                              tmp, tmp + (size_t)nv * P.XH, nv,

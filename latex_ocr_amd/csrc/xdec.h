@@ -60,6 +60,9 @@ struct XDecDec {
     float* logp_out;                  // [B][max_steps] log_softmax(logits)[id] (nullable: the instantiation without scores runs; last, so that the
                                       // other members keep their kernel-argument offsets).  A workgroup hands s = sum exp(v_j - m) over its 16
                                       // columns beside its arg-max word (m = that word's value) as a second tagged word
+    const int* prefix;                // [B][prefix_ld] forced ids (nullable: the instantiation without a prefix runs); row b emits prefix[b][t] at the
+    const int* prefix_len;            // steps t < prefix_len[b] (clamped into [0, prefix_lim], prefix_lim = min(prefix_ld, max_iter); an id outside
+    int prefix_ld, prefix_lim;        // [0, V) is read as 0).  With logp_out the workgroup owning the forced column hands its logit over as a third word
 };
 int lxo_launch_xdec_dec(const XDecDec& p, int U, int O, int C, int E, hipStream_t st);
 

@@ -791,7 +791,16 @@ int launch_nb(const XDecFwd& p, int att_u, hipStream_t st) {
 // the place of the raw scores (no alpha is kept), the o projection's A tile has 8 rows instead of 16.
 // SC: the log-prob of every arg-max (p.logp_out).  Beside its {max, tag | index} word a workgroup hands over {s, tag << 16}, s = the sum of
 // exp(v - max) over its 16 columns; the merge forms log p = -log sum_r s_r exp(m_r - M).  SC = false is the ids-only chain.
-template <int NB, bool SC>
+// PF: a forced prefix (p.prefix).  At a boundary inside its prefix a row takes the forced id f in place of the merged arg-max and stays
+// unfinished.  With SC the workgroup owning column f (rank f / 16) hands over a third word {v_f, tag << 16} beside the other two, the merge
+// forms log p = v_f - M - log sum_r s_r exp(m_r - M).  PF = false is the chain without a prefix.
+LXO_DEV int xdec_plen(const XDecDec& p, int bb) { return min(max(p.prefix_len[bb], 0), p.prefix_lim); }
+LXO_DEV int xdec_forced(const XDecDec& p, int bb, int step, int plen) {  // the forced id of row bb (prefix length plen) at `step`, -1: a free step
+    if (step >= plen) return -1;
+    const int f = p.prefix[(long long)bb * p.prefix_ld + step];
+    return (f >= 0 && f < p.V) ? f : 0;
+}
+template <int NB, bool SC, bool PF>
 __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     // 2 rows per wave and block in flight (the training chain: 4): the decode form carries more loop-invariant addresses (token table, ids,
     // arg-max words) and with 4 rows the allocator spills 55 dwords of them into the serial phases; with 2 it spills 9
@@ -883,11 +892,19 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     const rsrc_t rll_am = make_rsrc(ll_am, (unsigned)B * 32u * 8u);
     unsigned* ll_sm = ll_am + B * 32 * 2;                        // SC: the exponential-sum words [B][32 workgroups], behind the arg-max words
     const rsrc_t rll_sm = make_rsrc(ll_sm, (unsigned)B * 32u * 8u);
+    unsigned* ll_fv = ll_sm + B * 32 * 2;                        // SC && PF: the forced-logit words [B][32 workgroups], behind the sums
+    const rsrc_t rll_fv = make_rsrc(ll_fv, (unsigned)B * 32u * 8u);
     unsigned ph = 0;
     // early exit (dynamic_decode.py:38-51 stops once every row has finished): workgroup 0 of a chain looks, one boundary late and without
     // waiting, at how many chains have reported a step and how many rows it left unfinished, and raises a STOP bit in its arg-max word --
     // the one word every workgroup of the chain reads, so the whole chain leaves the loop at the same boundary
     int pr_done = 0, pr_unf = 1;
+    // PF: the prefix lengths of this thread's rows, read once per launch -- the merge's row (tid >> 5) and, with SC, the logits row (tid >> 4)
+    int plen_m = 0, plen_l = 0;
+    if constexpr (PF) {
+        if (tid < NB * 32) plen_m = xdec_plen(p, b0 + (tid >> 5));
+        if constexpr (SC) { if (tid < NB * 16) plen_l = xdec_plen(p, b0 + (tid >> 4)); }
+    }
     for (int t = 0; t <= T; ++t) {
         const int tg = p.t0 + t;                                 // global step index of the step this iteration runs
         const long long sp = (long long)(tg & 1) * B, sn = (long long)((tg + 1) & 1) * B;
@@ -955,6 +972,10 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
 #pragma unroll
                         for (int o = 8; o > 0; o >>= 1) sr += __shfl_xor(sr, o);
                         if (eu == 0) { const u32x2 ws = {__float_as_uint(sr), (unsigned)t << 16}; *reinterpret_cast<u32x2*>(ll_sm + ((b0 + erow) * 32 + rank) * 2) = ws; }
+                        if constexpr (PF) {
+                            const int fr = xdec_forced(p, b0 + erow, tg - 1, plen_l);
+                            if (fr == v0 + eu) { const u32x2 wf = {__float_as_uint(vc), (unsigned)t << 16}; *reinterpret_cast<u32x2*>(ll_fv + ((b0 + erow) * 32 + rank) * 2) = wf; }
+                        }
                     }
                     if (eu == 0) { const u32x2 wv = {__float_as_uint(v), ((unsigned)t << 16) | stopbit | (unsigned)vi}; *reinterpret_cast<u32x2*>(ll_am + ((b0 + erow) * 32 + rank) * 2) = wv; }
                 }
@@ -963,7 +984,9 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                     const int row = tid >> 5, cr = tid & 31;
                     const unsigned off = (unsigned)(((b0 + row) * 32 + cr) * 8);
                     float v = -3.0e38f; int vi = 0x7fffffff;
-                    float sr = 0.f;
+                    float sr = 0.f, vf = 0.f;
+                    int fr = -1;                                          // PF: the row's forced id at step tg - 1
+                    if constexpr (PF) fr = xdec_forced(p, b0 + row, tg - 1, plen_m);
                     const unsigned long long c0 = wall_clock64();
                     for (;;) {
                         const u32x2 wv = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rll_am, (int)off, 0, 16));
@@ -972,6 +995,13 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                             const u32x2 ws = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rll_sm, (int)off, 0, 16));
                             ok = ok && ws[1] == ((unsigned)t << 16);
                             if (ok) sr = __uint_as_float(ws[0]);
+                        }
+                        if constexpr (SC && PF) {
+                            if (fr >= 0 && (fr >> 4) == cr) {             // the candidate thread of the owning workgroup polls its third word too
+                                const u32x2 wf = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rll_fv, (int)off, 0, 16));
+                                ok = ok && wf[1] == ((unsigned)t << 16);
+                                if (ok) vf = __uint_as_float(wf[0]);
+                            }
                         }
                         if (ok) { v = __uint_as_float(wv[0]); vi = (int)(wv[1] & 0xffffu); }      // (bit 15 of workgroup 0's row-0 word: STOP)
                         if (__ballot(!ok) == 0ull) break;
@@ -993,15 +1023,17 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
 #pragma unroll
                         for (int o = 16; o > 0; o >>= 1) sr += __shfl_xor(sr, o);
                     }
+                    if constexpr (SC && PF) vf = __shfl(vf, (lane & 32) | (fr >> 4 & 31));      // from the owner's candidate thread
                     if (cr == 0) {
                         if (vi >= p.V) vi = 0;
+                        if constexpr (PF) { if (fr >= 0) vi = fr; }
                         ids_l[row] = vi;
                         if (rank == 0) {                          // one workgroup per chain publishes: ids, log-probs, finished flags
                             const int bb = b0 + row;
                             p.ids_out[(long long)bb * p.max_steps + (tg - 1)] = vi;
-                            if constexpr (SC) p.logp_out[(long long)bb * p.max_steps + (tg - 1)] = -logf(sr);
+                            if constexpr (SC) p.logp_out[(long long)bb * p.max_steps + (tg - 1)] = (PF && fr >= 0) ? (vf - v) - logf(sr) : -logf(sr);
                             p.ids_step[bb] = vi;
-                            const int fo = p.finished[bb] | (vi == p.id_end ? 1 : 0);
+                            const int fo = p.finished[bb] | (vi == p.id_end && fr < 0 ? 1 : 0);
                             p.finished[bb] = fo;
                             unf_l[row] = fo ? 0 : 1;
                         }
@@ -1305,16 +1337,18 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     if (tid == 0 && s_dead) *reinterpret_cast<volatile int*>(p.stop) = 1;
 }
 
-template <int NB, bool SC>
+template <int NB, bool SC, bool PF>
 int launch_dec_sc(const XDecDec& p, hipStream_t st) {
     constexpr int DYN = XW * 12 * 64 * 16;
     static bool attr_done = false;
-    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_dec_kernel<NB, SC>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
-    hipLaunchKernelGGL((xdec_dec_kernel<NB, SC>), dim3(256), dim3(512), DYN, st, p);
+    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_dec_kernel<NB, SC, PF>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
+    hipLaunchKernelGGL((xdec_dec_kernel<NB, SC, PF>), dim3(256), dim3(512), DYN, st, p);
     return (int)hipGetLastError();
 }
+template <int NB, bool PF>
+int launch_dec_pf(const XDecDec& p, hipStream_t st) { return p.logp_out ? launch_dec_sc<NB, true, PF>(p, st) : launch_dec_sc<NB, false, PF>(p, st); }
 template <int NB>
-int launch_dec_nb(const XDecDec& p, hipStream_t st) { return p.logp_out ? launch_dec_sc<NB, true>(p, st) : launch_dec_sc<NB, false>(p, st); }
+int launch_dec_nb(const XDecDec& p, hipStream_t st) { return p.prefix ? launch_dec_pf<NB, true>(p, st) : launch_dec_pf<NB, false>(p, st); }
 
 // ------------------------------------------------------------------------------------------------ backward chain ----
 // Steps T-1 .. 0 of BPTT in one launch, same chains, same identity, same barrier.  Per step:
@@ -1820,7 +1854,7 @@ int lxo_launch_xdec_dec(const XDecDec& p, int U, int O, int C, int E, hipStream_
     // tickets / flags and the hand-over area, but NOT the error word (int 512): an error of an earlier launch of this decode stays visible
     HIPRC(hipMemsetAsync(p.sync, 0, 8 * 64 * 4, st));
     HIPRC(hipMemsetAsync(p.sync + 8 * 64 + 1, 0, kXDecBlockBytes - (8 * 64 + 1) * 4, st));
-    HIPRC(hipMemsetAsync(p.sync + kXDecBlockBytes / 4 + kXDecSyncBytes / 4, 0, (size_t)p.B * 32 * 8 * (p.logp_out ? 2 : 1), st));      // the arg-max words (block 1's hand-over area; + the exponential sums)
+    HIPRC(hipMemsetAsync(p.sync + kXDecBlockBytes / 4 + kXDecSyncBytes / 4, 0, (size_t)p.B * 32 * 8 * (p.logp_out ? (p.prefix ? 3 : 2) : 1), st));      // the arg-max words (block 1's hand-over area; + the exponential sums, + the forced logits)
     if (kLL & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * nq * PLW * 8, st));               // the polled chunk partials (tags restart with every launch)
     switch (nb) {
     case 1: return launch_dec_nb<1>(p, st);

@@ -680,7 +680,40 @@ class Engine(object):
             return B
         return next(n for n in (8, 16, 32, 64) if B < n)
 
-    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False):
+    def _prefix_args(self, prefix, prefix_lengths, B0, Bp, id_end, max_iter):
+        """Checks a forced decode prefix before any launch and stages it on the device: -> (prefix int32 [Bp, ld], ld, lengths int32 [Bp]).
+        prefix: ids [B0, T] (None lengths: every row T long); rows >= B0 of a filled-up batch copy row index % B0, as their images do."""
+        pf = prefix.detach().cpu().numpy() if isinstance(prefix, torch.Tensor) else np.asarray(prefix)
+        pf = np.ascontiguousarray(pf, dtype=np.int64)
+        if pf.ndim != 2 or pf.shape[0] != B0:
+            raise ValueError("prefix must be [B, T] for B = %d images, got shape %s" % (B0, pf.shape))
+        T = int(pf.shape[1])
+        if prefix_lengths is None:
+            ln = np.full(B0, T, np.int64)
+        else:
+            ln = prefix_lengths.detach().cpu().numpy() if isinstance(prefix_lengths, torch.Tensor) else np.asarray(prefix_lengths)
+            ln = np.ascontiguousarray(ln, dtype=np.int64)
+            if ln.shape != (B0,):
+                raise ValueError("prefix_lengths must be [B] for B = %d images, got shape %s" % (B0, ln.shape))
+        lim = min(T, int(max_iter))
+        if ln.size and (ln.min() < 0 or ln.max() > lim):
+            raise ValueError("prefix lengths must lie in [0, min(T_prefix, max_iter) = %d], got %d .. %d" % (lim, int(ln.min()), int(ln.max())))
+        live = np.arange(T)[None, :] < ln[:, None]                  # the positions each row forces
+        if live.any():
+            v = pf[live]
+            if v.min() < 0 or v.max() >= self.n_tok:
+                raise ValueError("prefix ids must lie in [0, %d), got %d .. %d" % (self.n_tok, int(v.min()), int(v.max())))
+            if (v == int(id_end)).any():
+                rows = sorted(set(np.nonzero(live & (pf == int(id_end)))[0].tolist()))
+                raise ValueError("prefix rows %s contain id_end = %d" % (rows, int(id_end)))
+        pf = np.where(live, pf, 0)
+        if T == 0:
+            pf = np.zeros((B0, 1), np.int64)
+        rows = np.arange(Bp) % B0
+        return (self._to_dev(np.ascontiguousarray(pf[rows], dtype=np.int32), torch.int32), int(pf.shape[1]),
+                self._to_dev(np.ascontiguousarray(ln[rows], dtype=np.int32), torch.int32))
+
+    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False, prefix=None, prefix_lengths=None):
         """ids int32 [B, T'] as pred_test.ids of the greedy graph (decoder.py:64,70).  With return_attention also the
         attention maps alpha f32 [B, T', H', W'] (what the reference collects through its py_func hook,
         attention_mechanism.py:96-105, for visualize_attention.py).
@@ -688,11 +721,16 @@ class Engine(object):
         (lxo_greedy_decode_scores); the sequence log-prob of a row is the sum through its first END.
         A batch the persistent decode chain does not take (B not in {8, 16, 32, 64}) is filled up to the next such size with COPIES of its own
         images (rows are independent and a copy finishes with its original, so neither the ids of the real rows nor the step count change):
-        20 images decode in 26 us per step on the chain where the launch-per-step kernels take 44."""
+        20 images decode in 26 us per step on the chain where the launch-per-step kernels take 44.
+        prefix / prefix_lengths: decode from a given prefix (lxo_greedy_decode_prefix): ids [B, T_prefix] and lengths [B] (None: T_prefix
+        each); row b emits prefix[b, :P_b] first -- its logp there is the model's log-prob of the forced tokens -- and decodes on from there.
+        A ValueError before any launch for a shape mismatch, an id outside [0, V), id_end inside a prefix, or a length outside
+        [0, min(T_prefix, max_iter)]."""
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
         Bp = B0 if return_attention else self._decode_chain_batch(B0)
+        pfx = self._prefix_args(prefix, prefix_lengths, B0, Bp, id_end, max_iter) if prefix is not None else None
         if Bp != B0:
             img = self._to_dev(img, torch.uint8)
             img = img[torch.arange(Bp, device=img.device) % B0]
@@ -700,6 +738,23 @@ class Engine(object):
         ids = torch.zeros(B, self.max_steps, dtype=torch.int32, device=self.device)
         steps = ctypes.c_int(0)
         logp = torch.zeros(B, self.max_steps, dtype=torch.float32, device=self.device) if return_scores else None
+        if pfx is not None:
+            alpha, R = None, 0
+            if return_attention:
+                from .model.utils.image import encoder_out_hw
+                Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
+                R = Hp * Wp
+                alpha = torch.zeros(self.max_steps, B, (R + 7) // 8 * 8, dtype=torch.float32, device=self.device)
+            self._ck(self.lib.lxo_greedy_decode_prefix(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
+                                                       _p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(logp), _p(alpha), ctypes.byref(steps),
+                                                       self._stream()), "greedy_decode_prefix")
+            n = steps.value
+            out = (ids[:B0, :n].cpu().numpy(),)
+            if return_attention:
+                out += (alpha[:n, :, :R].permute(1, 0, 2).reshape(B, n, Hp, Wp).cpu().numpy(),)
+            if return_scores:
+                out += (logp[:B0, :n].cpu().numpy(),)
+            return out if len(out) > 1 else out[0]
         if not return_attention:
             if return_scores:
                 self._ck(self.lib.lxo_greedy_decode_scores(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
@@ -800,22 +855,46 @@ class Engine(object):
         return self.region("dec_logits", "f32", (self._dec_rows(), Vp))[:, :self.n_tok].cpu().numpy()
 
     def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False,
-                    return_scores=False):
+                    return_scores=False, prefix=None, prefix_lengths=None):
         """ids int32 [B, T', k] as pred_test.ids of the beam graph before the transpose at img2seq.py:241.
         div_gamma / div_prob: add_div_penalty of beam_search_decoder_cell.py:258-287 (off at 1 / 0, the shipped values).
         return_attention: -> (ids, parents, alpha f32 [B, T', k, H', W']): alpha[b, t, j] = the map decoder row j of image b attended with at
         step t (lxo_beam_decode_attn; the rows the reference's py_func tap sees under config.decoding = "beam_search").
         return_scores: -> (ids, parents, scores) or (ids, parents, alpha, scores), scores f32 [B, T', k] = the running log-prob of slot k after
-        step t (the beam state's log_probs; lxo_beam_decode_scores): the log-prob of the sequence that back-traces from (t, k)."""
+        step t (the beam state's log_probs; lxo_beam_decode_scores): the log-prob of the sequence that back-traces from (t, k).
+        prefix / prefix_lengths: per image, as in greedy_decode (lxo_beam_decode_prefix): every slot takes the forced tokens, the beam search
+        starts after them."""
         self._check_beam(beam_size)
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
+        B0 = int(img.shape[0])
+        pfx = self._prefix_args(prefix, prefix_lengths, B0, B0, id_end, max_iter) if prefix is not None else None
         B = self._encode_only(img, int(beam_size))
         self.shape.div_gamma, self.shape.div_prob = float(div_gamma or 0.0), float(div_prob or 0.0)
         self.shape.div_seed = int(div_seed) & 0x7FFFFFFF
         ids = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         par = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         steps = ctypes.c_int(0)
+        if pfx is not None:
+            sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device) if return_scores else None
+            alpha = None
+            if return_attention:
+                from .model.utils.image import encoder_out_hw
+                Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
+                R = Hp * Wp
+                alpha = torch.zeros(self.max_steps, B * beam_size, (R + 7) // 8 * 8, dtype=torch.float32, device=self.device)
+            self._ck(self.lib.lxo_beam_decode_prefix(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
+                                                     _p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(par), _p(sc), _p(alpha), ctypes.byref(steps),
+                                                     self._stream()), "beam_decode_prefix")
+            n = steps.value
+            out = (ids[:, :n].cpu().numpy(),)
+            if return_parents or return_attention or return_scores:
+                out += (par[:, :n].cpu().numpy(),)
+            if return_attention:
+                out += (alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous().cpu().numpy(),)
+            if return_scores:
+                out += (sc[:, :n].cpu().numpy(),)
+            return out if len(out) > 1 else out[0]
         if return_scores:
             sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device)
             alpha, a = None, None

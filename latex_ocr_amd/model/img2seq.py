@@ -205,7 +205,24 @@ class Img2SeqModel(BaseModel):
             out.append((float(seq[b]), [float(x) for x in logp[b, :n]], int(diff[0]) if diff.size else -1))
         return out
 
-    def _predict_scored(self, images):
+    def complete_batch(self, images, prefixes, return_scores=False):
+        """Decode each image from a given prefix (Engine greedy_decode / beam_decode with prefix=): the prefixes are token-id lists or
+        space-separated token strings (Vocab.form_prepro, as score_batch takes them, but no END is appended), one per image; "" or []
+        decodes from the start.  config.decoding chooses greedy or beam search; beam hypotheses are the back-traced ones, as
+        predict_batch(return_scores=True) returns them.  -> hyps (hyps[i][b]: hypothesis i of image b, its prefix included), or
+        (hyps, scores) with return_scores, scores as in predict_batch (the forced tokens' log-probs included)."""
+        if len(images) != len(prefixes):
+            raise ValueError("complete_batch: %d images but %d prefixes" % (len(images), len(prefixes)))
+        prepro = self._vocab.form_prepro
+        forms = [(prepro(f) if f.strip() else []) if isinstance(f, str) else [int(x) for x in f] for f in prefixes]      # "": no token
+        ln = np.array([len(f) for f in forms], np.int32)
+        pf = np.zeros((len(forms), max(1, int(ln.max()) if ln.size else 1)), np.int32)
+        for b, f in enumerate(forms):
+            pf[b, :len(f)] = f
+        hyps, scores = self._predict_scored(images, pf, ln)
+        return (hyps, scores) if return_scores else hyps
+
+    def _predict_scored(self, images, prefix=None, prefix_lengths=None):
         fd = self._get_feed_dict(images, dropout=1)
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1
@@ -215,11 +232,12 @@ class Img2SeqModel(BaseModel):
             self._div_calls = getattr(self, "_div_calls", 0) + 1
             ids, par, sc = self.engine.beam_decode(fd["img"], id_end, cfg.beam_size, max_iter=max_iter,
                                                    div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0),
-                                                   div_seed=self._div_calls, return_scores=True)
+                                                   div_seed=self._div_calls, return_scores=True, prefix=prefix, prefix_lengths=prefix_lengths)
             ids, run = beam_backtrace(ids, par), beam_backtrace(sc, par)          # token paths and their running log-probs
             tok = np.diff(run, axis=1, prepend=0.0)
         else:
-            ids, tok = self.engine.greedy_decode(fd["img"], id_end, max_iter=max_iter, return_scores=True)
+            ids, tok = self.engine.greedy_decode(fd["img"], id_end, max_iter=max_iter, return_scores=True, prefix=prefix,
+                                                 prefix_lengths=prefix_lengths)
             ids, tok = ids[:, :, None], tok[:, :, None]
         k = ids.shape[2]
         hyps, scores = [[] for _ in range(k)], [[] for _ in range(k)]

@@ -4,7 +4,8 @@ directory and print the LaTeX hypothesis for each image path given (the referenc
 pdf/LaTeX->PNG cropping helpers are out of scope).  --scores adds the hypothesis' log-prob and its geometric-mean token
 probability exp(log-prob / tokens) (Img2SeqModel.predict_batch(..., return_scores=True)).  --formula "<tokens>" (one image) scores
 that transcription instead of decoding: its log-prob (END included), geometric-mean token probability and the first position where
-the model's top-1 token differs from it (Img2SeqModel.score_batch)."""
+the model's top-1 token differs from it (Img2SeqModel.score_batch).  --prefix "<tokens>" (one image) decodes from that prefix: the
+hypothesis keeps it and the model writes the rest (Img2SeqModel.complete_batch); it combines with --scores."""
 import argparse
 
 import numpy as np
@@ -20,10 +21,13 @@ def main(argv=None):
     ap.add_argument("--results", default="results/small/")
     ap.add_argument("--scores", action="store_true", help="print the log-prob and the geometric-mean token probability of each hypothesis")
     ap.add_argument("--formula", default=None, help="score this space-separated token sequence against the (single) image")
+    ap.add_argument("--prefix", default=None, help="decode the (single) image from this space-separated token prefix")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     if a.formula is not None and len(a.images) != 1:
         ap.error("--formula scores one image")
+    if a.prefix is not None and (len(a.images) != 1 or a.formula is not None):
+        ap.error("--prefix completes one image and does not combine with --formula")
     d = a.results
     config_vocab, config_model = Config(d + "vocab.json"), Config(d + "model.json")
     vocab = Vocab(config_vocab)
@@ -37,6 +41,15 @@ def main(argv=None):
             lp, toks, first = model.score_batch([greyscale(img)], [a.formula])[0]
             print(path, "<=", a.formula, "\tlogp %.4f\tgeo-mean p %.4f\tfirst disagreement %d" % (lp, np.exp(lp / max(1, len(toks))), first))
             out.append((lp, toks, first))
+            continue
+        if a.prefix is not None:
+            hyps, scores = model.complete_batch([greyscale(img)], [a.prefix], return_scores=True)
+            lp, toks = scores[0][0]
+            if a.scores:
+                print(path, "=>", hyps[0][0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
+            else:
+                print(path, "=>", hyps[0][0])
+            out.append(([h[0] for h in hyps], [s[0] for s in scores]) if a.scores else [h[0] for h in hyps])
             continue
         if a.scores:
             hyps, scores = model.predict_batch([greyscale(img)], return_scores=True)
