@@ -493,6 +493,8 @@ def test_dead_padding_rows_live_B_same_loss_and_gradients():
         ff = np.ascontiguousarray(np.concatenate([f, f[:pad]]))                     # the dead row: any valid token ids
         ll = np.ascontiguousarray(np.concatenate([l, np.zeros(pad, l.dtype)]))      # ... and length 0
         S.shape.live_B = 2 if pad else 0
+        for r in ("img", "y6"):                 # not zero to begin with: the encoder has to write the dead row's zeros itself
+            S.region(r, np.uint8)[:] = 0xFF
         S.ck(S.L.lxo_encoder_fwd(S.sref(), ptr(S.params), ptr(S.wpack), ptr(S.ws), ptr(img), None), "enc")
         S.ck(S.L.lxo_decoder_train_fwd(S.sref(), ptr(S.params), ptr(S.wpack), ptr(S.ws), ptr(ff), None), "dec")
         S.ck(S.L.lxo_ce_loss_fwd_bwd(S.sref(), ptr(S.ws), ptr(ff), ptr(ll), ctypes.c_float(1.0 / int(l.sum())), None), "loss")
