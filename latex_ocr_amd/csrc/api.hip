@@ -170,34 +170,42 @@ extern "C" int lxo_adam_step(long long n, float* params, const float* grads, flo
     CHECK_LAUNCH(lxo_k_adam(params, grads, m, v, n, lr_t, beta1, beta2, eps, scale_dev, (hipStream_t)stream), "lxo_adam_step");
     return 0;
 }
+// The whole-loop decodes: one implementation per kind; the entry points differ in which outputs they take (impl.h: DecodeOuts) and demand
 extern "C" int lxo_greedy_decode(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                                  int id_end, int max_iter, int32_t* ids_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
-    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, ids_out, nullptr, steps_out, (hipStream_t)stream), "lxo_greedy_decode");
+    const DecodeOuts o = {ids_out, nullptr, nullptr, nullptr, nullptr};
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode");
     return 0;
 }
 extern "C" int lxo_greedy_decode_attn(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                                       int id_end, int max_iter, int32_t* ids_out, float* alpha_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
-    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, ids_out, alpha_out, steps_out, (hipStream_t)stream), "lxo_greedy_decode_attn");
+    const DecodeOuts o = {ids_out, nullptr, nullptr, alpha_out, nullptr};
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_attn");
     return 0;
 }
 extern "C" int lxo_greedy_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
                                         int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
     if (!logp_out) return fail(-1, "lxo_greedy_decode_scores: null logp_out");
-    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, ids_out, alpha_out, steps_out, (hipStream_t)stream, logp_out),
-                 "lxo_greedy_decode_scores");
+    const DecodeOuts o = {ids_out, nullptr, logp_out, alpha_out, nullptr};
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_scores");
     return 0;
+}
+// the forced prefix of the _prefix calls (decoder_kernels.h); false: an array is missing or prefix_ld < 1
+static bool make_prefix(DecPrefix* pf, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len, int max_iter) {
+    *pf = DecPrefix{prefix, prefix_len, prefix_ld, prefix_ld < max_iter ? prefix_ld : max_iter};
+    return prefix && prefix_len && prefix_ld >= 1;
 }
 extern "C" int lxo_greedy_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
                                         const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
                                         int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
-    if (!prefix || !prefix_len || prefix_ld < 1) return fail(-1, "lxo_greedy_decode_prefix: null prefix / prefix_len or prefix_ld < 1");
-    const DecPrefix pf = {prefix, prefix_len, prefix_ld, prefix_ld < max_iter ? prefix_ld : max_iter};
-    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, ids_out, alpha_out, steps_out, (hipStream_t)stream, logp_out, &pf),
-                 "lxo_greedy_decode_prefix");
+    DecPrefix pf;
+    if (!make_prefix(&pf, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, "lxo_greedy_decode_prefix: null prefix / prefix_len or prefix_ld < 1");
+    const DecodeOuts o = {ids_out, nullptr, logp_out, alpha_out, &pf};
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_prefix");
     return 0;
 }
 extern "C" int lxo_decode_begin(const lxo_shape* s, const float* params, const void* wpack, void* ws, void* stream) {
@@ -215,32 +223,34 @@ extern "C" int lxo_decode_step(const lxo_shape* s, const float* params, const vo
 extern "C" int lxo_beam_decode(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                                int id_end, int max_iter, int32_t* ids_out, int32_t* parents_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
-    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, nullptr, steps_out, (hipStream_t)stream), "lxo_beam_decode");
+    const DecodeOuts o = {ids_out, parents_out, nullptr, nullptr, nullptr};
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_beam_decode");
     return 0;
 }
 extern "C" int lxo_beam_decode_attn(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                                     int id_end, int max_iter, int32_t* ids_out, int32_t* parents_out, float* alpha_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
     if (!alpha_out) return fail(-1, "lxo_beam_decode_attn: null alpha_out");
-    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, alpha_out, steps_out, (hipStream_t)stream), "lxo_beam_decode_attn");
+    const DecodeOuts o = {ids_out, parents_out, nullptr, alpha_out, nullptr};
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_beam_decode_attn");
     return 0;
 }
 extern "C" int lxo_beam_decode_scores(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
                                       int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
     if (!scores_out) return fail(-1, "lxo_beam_decode_scores: null scores_out");
-    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, alpha_out, steps_out, (hipStream_t)stream, scores_out),
-                 "lxo_beam_decode_scores");
+    const DecodeOuts o = {ids_out, parents_out, scores_out, alpha_out, nullptr};
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_beam_decode_scores");
     return 0;
 }
 extern "C" int lxo_beam_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
                                       const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
                                       int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream) {
     MAKE_PLAN(P, s);
-    if (!prefix || !prefix_len || prefix_ld < 1) return fail(-1, "lxo_beam_decode_prefix: null prefix / prefix_len or prefix_ld < 1");
-    const DecPrefix pf = {prefix, prefix_len, prefix_ld, prefix_ld < max_iter ? prefix_ld : max_iter};
-    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, ids_out, parents_out, alpha_out, steps_out, (hipStream_t)stream, scores_out, &pf),
-                 "lxo_beam_decode_prefix");
+    DecPrefix pf;
+    if (!make_prefix(&pf, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, "lxo_beam_decode_prefix: null prefix / prefix_len or prefix_ld < 1");
+    const DecodeOuts o = {ids_out, parents_out, scores_out, alpha_out, &pf};
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_beam_decode_prefix");
     return 0;
 }
 

@@ -13,16 +13,17 @@ int lxo_impl_score_tokens(const Plan& P, void* ws, const int* formula, const int
 // parts: bit 0 = d_o from the logits + d y_W_o (final before the recurrence runs), bit 1 = BPTT + every other decoder gradient + d_img
 int lxo_impl_decoder_train_bwd(const Plan& P, const float* prm, const void* wp, void* ws, const int* formula, float* grads, int parts, hipStream_t st,
                                bool defer_join = false, void* ready = nullptr);
-int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, int* ids_out, float* alpha_out, int* steps_out, hipStream_t st,
-                           float* logp_out = nullptr, const DecPrefix* prefix = nullptr);      // prefix (nullable): forced ids (decoder_kernels.h)
+// Where a whole-loop decode writes and what it is forced to emit (device arrays; all but ids nullable): scores = the token log-probs
+// (greedy) / the running log-probs (beam), alpha = the attention maps, prefix = forced ids (decoder_kernels.h).  Greedy has no parents.
+struct DecodeOuts { int* ids; int* parents; float* scores; float* alpha; const DecPrefix* prefix; };
+int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out, int* steps_out, hipStream_t st);
 int lxo_impl_decode_begin(const Plan& P, const float* prm, const void* wp, void* ws, hipStream_t st);
 int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int time, int* ids_out, int* parents_out, int* finished_out, int* unfinished_host, hipStream_t st);
 int lxo_impl_chain_guard(const Plan& P, void* ws, const float* grads, float* scale, int have_scale, unsigned* status, hipStream_t st);
 int lxo_impl_decode_state_get(const Plan& P, void* ws, int time, float* c, float* h, float* o, hipStream_t st);
 int lxo_impl_decode_state_set(const Plan& P, void* ws, int time, const float* c, const float* h, const float* o, const int* ids_prev, hipStream_t st);
 int lxo_impl_decode_cell_step(const Plan& P, const float* prm, const void* wp, void* ws, int time, int start_token, hipStream_t st);
-int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, int* ids_out, int* parents_out, float* alpha_out, int* steps_out, hipStream_t st,
-                         float* scores_out = nullptr, const DecPrefix* prefix = nullptr);
+int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out, int* steps_out, hipStream_t st);
 int lxo_impl_set_side_stream(hipStream_t s);
 int lxo_impl_set_encoder_side_stream(hipStream_t s);
 // optional row-BiLSTM encoder (model_rowenc.hip): features in ws region "img" in place; backward: "d_img" (f32) in place + parameter gradients

@@ -3,6 +3,7 @@
 // Reference graph: model/decoder.py:41-72, model/components/attention_mechanism.py,
 // model/components/attention_cell.py:58-89, model/img2seq.py:68-75.
 #include "plan.h"
+#include "impl.h"
 #include "gemm.h"
 #include "decoder_kernels.h"
 #include "rstep.h"
@@ -645,7 +646,8 @@ static int decode_common_step(const Plan& P, const float* prm, const void* wp, v
     return 0;
 }
 
-// Host side of dynamic_decode's `while not all(finished)` (dynamic_decode.py:38-61): steps are enqueued in chunks of CHUNK;
+// Host side of dynamic_decode's `while not all(finished)` (dynamic_decode.py:38-61): steps are enqueued in chunks (8 steps of launches, or
+// one launch of the persistent greedy-decode chain);
 // each chunk ends with an asynchronous copy of its per-step "rows still unfinished" counters into pinned host memory and
 // an event.  The host enqueues chunk c + 1 BEFORE it waits for chunk c's event, so the stream never drains while the
 // host looks at the flags (the round-1 loop synchronised the stream every 8 steps); if chunk c turns out to contain the
@@ -662,20 +664,23 @@ int poll_init() {
     return 0;
 }
 }  // namespace
-template <typename StepFn>
-static int decode_loop(int max_iter, int* flags, hipStream_t st, int* steps_out, StepFn step) {
+// `enqueue(first, n, device counters)` enqueues steps first .. first + n - 1 (n <= steps_per_enqueue); step first + c adds its unfinished
+// rows to counter word c.  counter_words (<= 32) words are cleared before an enqueue and copied back behind it.
+template <typename EnqueueFn>
+static int decode_loop(int max_iter, int steps_per_enqueue, int counter_words, int* flags, hipStream_t st, int* steps_out, EnqueueFn enqueue) {
     RC(poll_init());
-    const int CHUNK = 8;
+    if (steps_per_enqueue > counter_words) steps_per_enqueue = counter_words;
     int enq = 0;                 // steps enqueued so far
     int nchunks = 0;             // chunks enqueued
     int steps = -1;              // final step count once known
     auto enqueue_chunk = [&]() -> int {
         const int slot = nchunks & 1;
         int* dflags = flags + slot * 32;                      // device counters of this chunk (flags[0..63]: two slots of 32)
-        HIPRC(hipMemsetAsync(dflags, 0, CHUNK * sizeof(int), st));
-        int n = 0;
-        for (; n < CHUNK && enq <= max_iter; ++n, ++enq) RC(step(enq, dflags + n));
-        HIPRC(hipMemcpyAsync(g_poll.host + slot * 64, dflags, CHUNK * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPRC(hipMemsetAsync(dflags, 0, counter_words * sizeof(int), st));
+        int n = max_iter + 1 - enq; if (n > steps_per_enqueue) n = steps_per_enqueue;
+        RC(enqueue(enq, n, dflags));
+        enq += n;
+        HIPRC(hipMemcpyAsync(g_poll.host + slot * 64, dflags, counter_words * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPRC(hipEventRecord(g_poll.ev[slot], st));
         g_poll.host[slot * 64 + 32] = n;                      // steps in this chunk
         g_poll.host[slot * 64 + 33] = enq - n;                // first step of this chunk
@@ -690,8 +695,10 @@ static int decode_loop(int max_iter, int* flags, hipStream_t st, int* steps_out,
         HIPRC(hipEventSynchronize(g_poll.ev[slot]));
         const int n = g_poll.host[slot * 64 + 32], first = g_poll.host[slot * 64 + 33];
         for (int c = 0; c < n; ++c) {
-            // dynamic_decode.py:38-51: stop after the first step that leaves nothing unfinished, or after step max_iter
-            if (g_poll.host[slot * 64 + c] == 0 || first + c >= max_iter) { steps = first + c + 1; break; }
+            // dynamic_decode.py:38-51: stop after the first step that leaves nothing unfinished, or after step max_iter.  Low 16 bits: the
+            // unfinished rows (the greedy chain keeps "chains that reported" in the high bits; a launch-per-step counter is at most
+            // B * beam <= 64 * 16 rows, so the mask changes nothing there)
+            if ((g_poll.host[slot * 64 + c] & 0xffff) == 0 || first + c >= max_iter) { steps = first + c + 1; break; }
         }
         ++checked;
         if (steps < 0 && checked == nchunks && enq > max_iter) steps = enq;      // cannot happen (the last step hits the bound); belt and braces
@@ -700,60 +707,83 @@ static int decode_loop(int max_iter, int* flags, hipStream_t st, int* steps_out,
     if (steps_out) *steps_out = steps;
     return 0;
 }
-
-// The same host loop at CHUNK granularity: one call of `chunk(first_step, n_steps, device counters)` enqueues n_steps steps (the persistent
-// greedy-decode chain runs a chunk as ONE launch).
-template <typename ChunkFn>
-static int decode_loop_chunked(int max_iter, int CHUNK, int* flags, hipStream_t st, int* steps_out, ChunkFn chunk) {
-    RC(poll_init());
-    if (CHUNK > 32) CHUNK = 32;
-    int enq = 0, nchunks = 0, steps = -1;
-    auto enqueue_chunk = [&]() -> int {
-        const int slot = nchunks & 1;
-        int* dflags = flags + slot * 32;
-        HIPRC(hipMemsetAsync(dflags, 0, 32 * sizeof(int), st));
-        int n = max_iter + 1 - enq; if (n > CHUNK) n = CHUNK;
-        RC(chunk(enq, n, dflags));
-        enq += n;
-        HIPRC(hipMemcpyAsync(g_poll.host + slot * 64, dflags, 32 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPRC(hipEventRecord(g_poll.ev[slot], st));
-        g_poll.host[slot * 64 + 32] = n;
-        g_poll.host[slot * 64 + 33] = enq - n;
-        ++nchunks;
+// The launch-per-step decodes: 8 steps per enqueue, `step(time, its counter word)` enqueues one
+template <typename StepFn>
+static int decode_loop_steps(int max_iter, int* flags, hipStream_t st, int* steps_out, StepFn step) {
+    return decode_loop(max_iter, 8, 8, flags, st, steps_out, [&](int first, int n, int* unfinished) -> int {
+        for (int c = 0; c < n; ++c) RC(step(first + c, unfinished + c));
         return 0;
-    };
-    RC(enqueue_chunk());
-    int checked = 0;
-    while (steps < 0) {
-        if (enq <= max_iter) RC(enqueue_chunk());
-        const int slot = checked & 1;
-        HIPRC(hipEventSynchronize(g_poll.ev[slot]));
-        const int n = g_poll.host[slot * 64 + 32], first = g_poll.host[slot * 64 + 33];
-        for (int c = 0; c < n; ++c)
-            if ((g_poll.host[slot * 64 + c] & 0xffff) == 0 || first + c >= max_iter) { steps = first + c + 1; break; }      // low 16 bits: unfinished rows (high bits: chains that reported)
-        ++checked;
-        if (steps < 0 && checked == nchunks && enq > max_iter) steps = enq;
+    });
+}
+
+// What the decode calls share, fetched once per call: the selection kind, its rows and the workspace regions it works in
+struct Dec {
+    int k, nv;                      // hypotheses per image, decoder rows (B * k)
+    bool beam;                      // select with beam_step (else arg-max): lxo_beam_decode at any k, the step-wise calls at k > 1
+    int *flags, *finished;          // [0..63]: per-step unfinished counters (two slots of 32); behind them finished[nv]
+    int *ids_step, *par_step;       // the ids fed back into the next step, their parent slots
+    float *logp, *tmp;              // beam: running log-probs, scratch
+    float *rec, *cs; bf16_t* recb;  // the two state slots (slot 0 holds the initial state, slots alternate); bf16 mirror of rec or null
+    float *logits, *alpha;          // of the step that just ran
+};
+static Dec dec_of(const Plan& P, void* ws, int k, bool beam) {
+    Dec d;
+    d.k = k; d.nv = P.s.B * k; d.beam = beam;
+    d.flags = P.ws<int>(ws, W_DEC_FLAGS); d.finished = d.flags + 64;
+    d.ids_step = P.ws<int>(ws, W_DEC_IDS); d.par_step = P.ws<int>(ws, W_BEAM_PAR);
+    d.logp = P.ws<float>(ws, W_BEAM_LP); d.tmp = P.ws<float>(ws, W_BEAM_TMP);
+    d.rec = P.ws<float>(ws, W_REC); d.cs = P.ws<float>(ws, W_CS);
+    d.logits = P.ws<float>(ws, W_DEC_LOGITS); d.alpha = P.ws<float>(ws, W_ALPHA);
+    d.recb = (fused_steps(P) && P.bf) ? P.ws<bf16_t>(ws, W_RECB) : nullptr;
+    return d;
+}
+// The shapes and arguments every decode call refuses (-5): fewer record columns than steps, a beam the kernels do not take (k > V: fewer
+// first-step candidates than hypotheses), a prefix without its arrays
+static int decode_check(const Plan& P, int k, int steps_needed, const DecPrefix* prefix) {
+    if (P.s.max_steps < steps_needed || k < 1 || k > 16 || k > P.s.V) return -5;
+    if (prefix && (!prefix->ids || !prefix->len || prefix->ld < 1)) return -5;
+    return 0;
+}
+// Before step 0: initial state, cleared flags, and what is computed once per call.  `again` (the greedy chain's fall-back, behind a
+// chain that failed): only the initial state and the finished flags are rebuilt
+static int decode_setup(const Plan& P, const float* prm, const void* wp, void* ws, const Dec& d, bool again, hipStream_t st) {
+    RC(attention_prepare(P, prm, wp, ws, d.k, st));
+    if (!again && P.att_exp())      // bf16: E_x = e^{2 att_img}, once per call
+        RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)P.s.B * P.R * P.s.E, st));
+    if (fused_steps(P)) RC(mirror_oh(P, ws, 0, d.nv, st));
+    HIPRC(hipMemsetAsync(d.flags, 0, 256 + (size_t)d.nv * 4, st));
+    if (again) return 0;
+    if (d.beam) HIPRC(hipMemsetAsync(d.logp, 0, (size_t)d.nv * 4, st));
+    if (fused_steps(P)) RC(decode_token_table(P, prm, wp, ws, st));
+    return 0;
+}
+// Behind decode_common_step(time): the attention maps of the step's rows as they ran, if asked for (beam: row b * k + j = hypothesis slot j
+// BEFORE this step's re-ordering -- what the reference's py_func tap sees, attention_mechanism.py:59-65,96-105), then the arg-max, or the
+// beam's top-k and the re-ordering of the new state rows (+ their bf16 mirror) by parent, which feed the next LSTM GEMM.  `indirect`: no
+// re-ordering, the next step reads its rows through par_step
+static int decode_select(const Plan& P, const Dec& d, int id_end, int time, const DecodeOuts& o, int* unfinished, bool indirect, hipStream_t st) {
+    const int ms = P.s.max_steps, U = P.s.U, nv = d.nv, cur = (time + 1) & 1;
+    if (o.alpha) HIPRC(hipMemcpyAsync(o.alpha + (size_t)time * nv * P.Rp, d.alpha, (size_t)nv * P.Rp * 4, hipMemcpyDeviceToDevice, st));
+    if (!d.beam) {
+        RC(lxo_k_argmax(d.logits, P.Vp, P.s.V, nv, id_end, d.ids_step, o.ids, ms, time, d.finished, unfinished, st, o.scores, o.prefix));
+        return 0;
     }
-    if (nchunks > checked) HIPRC(hipEventSynchronize(g_poll.ev[(nchunks - 1) & 1]));
-    if (steps_out) *steps_out = steps;
+    RC(lxo_k_beam_step(d.logits, P.Vp, P.s.V, P.s.B, d.k, id_end, time, P.s.div_gamma, P.s.div_prob, P.s.div_seed, d.tmp, d.logp, d.finished,
+                       d.ids_step, d.par_step, o.ids, o.parents, ms, unfinished, st, o.scores, o.prefix));
+    if (indirect) return 0;
+    RC(lxo_k_beam_gather(d.rec + (size_t)cur * nv * P.REC, P.REC, P.XH, d.cs + (size_t)cur * nv * U, U, d.par_step, d.k,
+                         d.tmp, d.tmp + (size_t)nv * P.XH, nv, d.recb ? d.recb + (size_t)cur * nv * P.RECB : nullptr, P.RECB, st));
     return 0;
 }
 
-int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter,
-                           int* ids_out, float* alpha_out, int* steps_out, hipStream_t st, float* logp_out, const DecPrefix* prefix) {
+int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out,
+                           int* steps_out, hipStream_t st) {
     const int B = P.s.B, ms = P.s.max_steps;
-    if (ms < max_iter + 1) return -5;
-    if (prefix && (!prefix->ids || !prefix->len || prefix->ld < 1)) return -5;
-    RC(attention_prepare(P, prm, wp, ws, 1, st));
-    if (P.att_exp()) RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)B * P.R * P.s.E, st));      // bf16: E_x = e^{2 att_img}, once per call
-    if (fused_steps(P)) RC(mirror_oh(P, ws, 0, B, st));
-    int* flags = P.ws<int>(ws, W_DEC_FLAGS);          // [0..63]: per-step unfinished counters ; [64..]: finished[B]
-    int* finished = flags + 64;
-    int* ids_step = P.ws<int>(ws, W_DEC_IDS);
-    HIPRC(hipMemsetAsync(flags, 0, 256 + (size_t)B * 4, st));
-    // rec/cs slot 0 holds the initial state; slots alternate
-    if (fused_steps(P)) RC(decode_token_table(P, prm, wp, ws, st));
-    if (fused_steps(P) && P.bf && P.att_exp() && !alpha_out && P.s.step_kernels == 0) {
+    const DecPrefix* prefix = out.prefix;
+    RC(decode_check(P, 1, max_iter + 1, prefix));
+    const Dec d = dec_of(P, ws, 1, false);
+    RC(decode_setup(P, prm, wp, ws, d, false, st));
+    if (fused_steps(P) && P.bf && P.att_exp() && !out.alpha && P.s.step_kernels == 0) {
         // the persistent greedy-decode chain (xdec.hip: xdec_dec_kernel): 16 steps per launch; -2 = the shape does not qualify
         XDecDec x; memset(&x, 0, sizeof(x));
         x.Wrt = (const bf16_t*)P.pk(wp, K_LSTM_RT); x.ldrt = P.ldRT;
@@ -765,17 +795,17 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
         x.tx = P.ws<float>(ws, W_DEC_TX);
         x.rec = P.ws<float>(ws, W_REC); x.recb = P.ws<bf16_t>(ws, W_RECB); x.cs = P.ws<float>(ws, W_CS);
         x.part = P.ws<float>(ws, W_APART); x.sync = P.ws<unsigned>(ws, W_XSYNC);
-        x.ids_step = ids_step; x.ids_out = ids_out; x.logp_out = logp_out; x.finished = finished;
+        x.ids_step = d.ids_step; x.ids_out = out.ids; x.logp_out = out.scores; x.finished = d.finished;
         if (prefix) { x.prefix = prefix->ids; x.prefix_len = prefix->len; x.prefix_ld = prefix->ld; x.prefix_lim = prefix->lim; }
         x.B = B; x.R = P.R; x.REC = P.REC; x.RECB = P.RECB; x.V = P.s.V; x.id_end = id_end; x.max_steps = ms;
-        x.t0 = 0; x.nsteps = 1; x.unfinished = flags;
-        x.stop = ids_step + B;                            // one word behind the fed-back ids (region "dec_ids" holds B x max_steps ints)
+        x.t0 = 0; x.nsteps = 1; x.unfinished = d.flags;
+        x.stop = d.ids_step + B;                            // one word behind the fed-back ids (region "dec_ids" holds B x max_steps ints)
         HIPRC(hipMemsetAsync(x.stop, 0, sizeof(int), st));
         HIPRC(hipMemsetAsync(P.ws<unsigned>(ws, W_XSYNC) + 8 * 64, 0, sizeof(unsigned), st));      // the error word: once per decode (the launcher leaves it alone)
         int chunk_steps = 16;                             // steps per launch (LXO_XDEC_DEC_CHUNK: 1 .. 16; read per call so that a test can vary it)
         { const char* e = getenv("LXO_XDEC_DEC_CHUNK"); if (e && atoi(e) > 0 && atoi(e) < 16) chunk_steps = atoi(e); }
         bool took = true;
-        const int rc = decode_loop_chunked(max_iter, chunk_steps, flags, st, steps_out, [&](int first, int n, int* unfinished) -> int {
+        const int rc = decode_loop(max_iter, chunk_steps, 32, d.flags, st, steps_out, [&](int first, int n, int* unfinished) -> int {
             XDecDec y = x; y.t0 = first; y.nsteps = n; y.unfinished = unfinished;
             const int r = lxo_launch_xdec_dec(y, P.s.U, P.s.O, P.s.C, P.s.E, st);
             if (r == -2 && first == 0) { took = false; return -2; }
@@ -788,24 +818,18 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
             HIPRC(hipMemcpyAsync(&errw, P.ws<unsigned>(ws, W_XSYNC) + 8 * 64, sizeof(unsigned), hipMemcpyDeviceToHost, st));
             HIPRC(hipStreamSynchronize(st));
             if (errw == 0) return 0;
-            // fall back to the launch-per-step kernels: the initial state, the finished flags and the token table are rebuilt first
-            RC(attention_prepare(P, prm, wp, ws, 1, st));
-            if (fused_steps(P)) RC(mirror_oh(P, ws, 0, B, st));
+            // fall back to the launch-per-step kernels: the initial state and the finished flags are rebuilt first
+            RC(decode_setup(P, prm, wp, ws, d, true, st));
         } else {
             HIPRC(hipStreamSynchronize(st));              // (nothing was enqueued by the refused first chunk but its counter memset)
             HIPRC(hipMemsetAsync(P.ws<unsigned>(ws, W_XSYNC), 0, 8 * 64 * 4, st));      // no chain in this call: no tickets (Engine.chain_status reads them)
+            HIPRC(hipMemsetAsync(d.flags, 0, 256 + (size_t)B * 4, st));
         }
-        HIPRC(hipMemsetAsync(flags, 0, 256 + (size_t)B * 4, st));
     } else if (P.bf) HIPRC(hipMemsetAsync(P.ws<unsigned>(ws, W_XSYNC), 0, 8 * 64 * 4, st));
-    RC(decode_loop(max_iter, flags, st, steps_out, [&](int time, int* unfinished) -> int {
-        const int cur = (time + 1) & 1;
-        RC(decode_common_step(P, prm, wp, ws, B, 1, cur, time == 0 ? nullptr : ids_step, st));
-        if (alpha_out)      // attention weights of this step (what attention_mechanism.py:96-105 hands to its py_func hook)
-            HIPRC(hipMemcpyAsync(alpha_out + (size_t)time * B * P.Rp, P.ws<float>(ws, W_ALPHA), (size_t)B * P.Rp * 4, hipMemcpyDeviceToDevice, st));
-        RC(lxo_k_argmax(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, id_end, ids_step, ids_out, ms, time, finished, unfinished, st, logp_out, prefix));
-        return 0;
-    }));
-    return 0;
+    return decode_loop_steps(max_iter, d.flags, st, steps_out, [&](int time, int* unfinished) -> int {
+        RC(decode_common_step(P, prm, wp, ws, B, 1, (time + 1) & 1, time == 0 ? nullptr : d.ids_step, st));
+        return decode_select(P, d, id_end, time, out, unfinished, false, st);
+    });
 }
 
 // lxo_chain_guard: scale[0] = NaN when a chain of this step left an error word, else the clip scale / 1 (decoder_kernels.hip)
@@ -849,85 +873,41 @@ int lxo_impl_decode_cell_step(const Plan& P, const float* prm, const void* wp, v
 // ---- the decode loop one step at a time: what the reference's cell protocol (dynamic_decode.py:34-61: initialize / step /
 // finalize) is bound to.  State (c, h, o, running log-probs, finished flags, previous ids) stays in the workspace. ----
 int lxo_impl_decode_begin(const Plan& P, const float* prm, const void* wp, void* ws, hipStream_t st) {
-    const int B = P.s.B, k = P.s.beam > 1 ? P.s.beam : 1, nv = B * k;
-    if (P.s.max_steps < 1 || k > 16 || k > P.s.V) return -5;
-    RC(attention_prepare(P, prm, wp, ws, k, st));
-    if (P.att_exp()) RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)B * P.R * P.s.E, st));      // bf16 decode: E_x = e^{2 att_img}, once per call
-    if (fused_steps(P)) RC(mirror_oh(P, ws, 0, nv, st));
-    HIPRC(hipMemsetAsync(P.ws<int>(ws, W_DEC_FLAGS), 0, 256 + (size_t)nv * 4, st));
-    if (k > 1) HIPRC(hipMemsetAsync(P.ws<float>(ws, W_BEAM_LP), 0, (size_t)nv * 4, st));
-    if (fused_steps(P)) RC(decode_token_table(P, prm, wp, ws, st));
-    return 0;
+    const int k = P.s.beam > 1 ? P.s.beam : 1;
+    RC(decode_check(P, k, 1, nullptr));
+    return decode_setup(P, prm, wp, ws, dec_of(P, ws, k, k > 1), false, st);
 }
 
 int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int time,
                          int* ids_out, int* parents_out, int* finished_out, int* unfinished_host, hipStream_t st) {
-    const int B = P.s.B, k = P.s.beam > 1 ? P.s.beam : 1, nv = B * k, ms = P.s.max_steps, U = P.s.U;
-    if (time < 0 || time >= ms || k > 16 || k > P.s.V) return -5;
-    int* flags = P.ws<int>(ws, W_DEC_FLAGS);
-    int* finished = flags + 64;
-    int* ids_step = P.ws<int>(ws, W_DEC_IDS);
-    HIPRC(hipMemsetAsync(flags, 0, sizeof(int), st));
-    const int cur = (time + 1) & 1;
-    RC(decode_common_step(P, prm, wp, ws, nv, k, cur, time == 0 ? nullptr : ids_step, st));
-    if (k == 1) {
-        RC(lxo_k_argmax(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, id_end, ids_step, ids_out, ms, time, finished, flags, st));
-    } else {
-        int* par_step = P.ws<int>(ws, W_BEAM_PAR);
-        float* tmp = P.ws<float>(ws, W_BEAM_TMP);
-        float* rec = P.ws<float>(ws, W_REC); float* cs = P.ws<float>(ws, W_CS);
-        RC(lxo_k_beam_step(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, k, id_end, time, P.s.div_gamma, P.s.div_prob, P.s.div_seed, tmp,
-                           P.ws<float>(ws, W_BEAM_LP), finished, ids_step, par_step, ids_out, parents_out, ms, flags, st));
-        RC(lxo_k_beam_gather(rec + (size_t)cur * nv * P.REC, P.REC, P.XH, cs + (size_t)cur * nv * U, U, par_step, k,
-                             tmp, tmp + (size_t)nv * P.XH, nv,
-                             (fused_steps(P) && P.bf) ? P.ws<bf16_t>(ws, W_RECB) + (size_t)cur * nv * P.RECB : nullptr, P.RECB, st));      // + the bf16 mirror of the re-ordered [o | h] rows
-    }
-    if (finished_out) HIPRC(hipMemcpyAsync(finished_out, finished, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+    const int k = P.s.beam > 1 ? P.s.beam : 1;
+    if (time < 0 || decode_check(P, k, time + 1, nullptr)) return -5;
+    const Dec d = dec_of(P, ws, k, k > 1);
+    HIPRC(hipMemsetAsync(d.flags, 0, sizeof(int), st));
+    RC(decode_common_step(P, prm, wp, ws, d.nv, k, (time + 1) & 1, time == 0 ? nullptr : d.ids_step, st));
+    // (the state rows are always re-ordered here: the callers may look at the state between steps, see lxo_impl_beam_decode)
+    RC(decode_select(P, d, id_end, time, DecodeOuts{ids_out, parents_out, nullptr, nullptr, nullptr}, d.flags, false, st));
+    if (finished_out) HIPRC(hipMemcpyAsync(finished_out, d.finished, (size_t)d.nv * 4, hipMemcpyDeviceToHost, st));
     if (unfinished_host) {
-        HIPRC(hipMemcpyAsync(unfinished_host, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPRC(hipMemcpyAsync(unfinished_host, d.flags, sizeof(int), hipMemcpyDeviceToHost, st));
         HIPRC(hipStreamSynchronize(st));
     }
     return 0;
 }
 
-int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter,
-                         int* ids_out, int* parents_out, float* alpha_out, int* steps_out, hipStream_t st, float* scores_out, const DecPrefix* prefix) {
-    const int B = P.s.B, k = P.s.beam, ms = P.s.max_steps, nv = B * k, U = P.s.U;
-    if (ms < max_iter + 1 || k < 1 || k > 16 || k > P.s.V) return -5;      // k > V: fewer first-step candidates than hypotheses
-    if (prefix && (!prefix->ids || !prefix->len || prefix->ld < 1)) return -5;
-    RC(attention_prepare(P, prm, wp, ws, k, st));
-    if (P.att_exp()) RC(lxo_k_att_exp(P.ws<void>(ws, W_ATT_IMG), P.ws<void>(ws, W_ATT_EXP), (long long)B * P.R * P.s.E, st));      // bf16: E_x = e^{2 att_img}, once per call
-    if (fused_steps(P)) RC(mirror_oh(P, ws, 0, nv, st));
-    int* flags = P.ws<int>(ws, W_DEC_FLAGS);
-    int* finished = flags + 64;
-    int* ids_step = P.ws<int>(ws, W_DEC_IDS);
-    int* par_step = P.ws<int>(ws, W_BEAM_PAR);
-    float* logp = P.ws<float>(ws, W_BEAM_LP);
-    float* tmp = P.ws<float>(ws, W_BEAM_TMP);
-    HIPRC(hipMemsetAsync(flags, 0, 256 + (size_t)nv * 4, st));
-    HIPRC(hipMemsetAsync(logp, 0, (size_t)nv * 4, st));
-    float* rec = P.ws<float>(ws, W_REC); float* cs = P.ws<float>(ws, W_CS);
-    if (fused_steps(P)) RC(decode_token_table(P, prm, wp, ws, st));
+int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out,
+                         int* steps_out, hipStream_t st) {
+    RC(decode_check(P, P.s.beam, max_iter + 1, out.prefix));
+    const Dec d = dec_of(P, ws, P.s.beam, true);
+    RC(decode_setup(P, prm, wp, ws, d, false, st));
     // the state of a step's rows is that of their PARENT hypotheses (beam_search_decoder_cell.py:176-178).  With the fused step kernels the next LSTM launch
     // reads its [o | h] and c rows through the parents in place; the launch that re-ordered the rows (beam_permute_kernel, 5.3 us + its gap) is only left for
     // the split-K step kernels and for lxo_decode_step, whose callers may look at the state between steps (LXO_BEAM_INDIRECT=0: always re-order; A/B)
     static int indirect_on = -1;
     if (indirect_on < 0) { const char* e = getenv("LXO_BEAM_INDIRECT"); indirect_on = (e && e[0] == '0') ? 0 : 1; }
     const bool indirect = indirect_on && fused_steps(P);
-    RC(decode_loop(max_iter, flags, st, steps_out, [&](int time, int* unfinished) -> int {
-        const int cur = (time + 1) & 1;
-        RC(decode_common_step(P, prm, wp, ws, nv, k, cur, time == 0 ? nullptr : ids_step, st, indirect ? par_step : nullptr));
-        if (alpha_out)      // the attention weights of this step's B x k decoder rows, as they ran (row b * k + j = hypothesis slot j BEFORE this step's
-                            // re-ordering: what the reference's py_func tap sees on the merged batch x beam rows, attention_mechanism.py:59-65,96-105)
-            HIPRC(hipMemcpyAsync(alpha_out + (size_t)time * nv * P.Rp, P.ws<float>(ws, W_ALPHA), (size_t)nv * P.Rp * 4, hipMemcpyDeviceToDevice, st));
-        RC(lxo_k_beam_step(P.ws<float>(ws, W_DEC_LOGITS), P.Vp, P.s.V, B, k, id_end, time, P.s.div_gamma, P.s.div_prob, P.s.div_seed, tmp,
-                           logp, finished, ids_step, par_step,
-                           ids_out, parents_out, ms, unfinished, st, scores_out, prefix));
-        if (!indirect)
-        RC(lxo_k_beam_gather(rec + (size_t)cur * nv * P.REC, P.REC, P.XH, cs + (size_t)cur * nv * U, U, par_step, k,
-                             tmp, tmp + (size_t)nv * P.XH, nv,
-                             (fused_steps(P) && P.bf) ? P.ws<bf16_t>(ws, W_RECB) + (size_t)cur * nv * P.RECB : nullptr, P.RECB, st));    // the re-ordered [o | h] rows (+ their bf16 mirror) feed the next LSTM GEMM
-        return 0;
-    }));
-    return 0;
+    return decode_loop_steps(max_iter, d.flags, st, steps_out, [&](int time, int* unfinished) -> int {
+        RC(decode_common_step(P, prm, wp, ws, d.nv, d.k, (time + 1) & 1, time == 0 ? nullptr : d.ids_step, st, indirect ? d.par_step : nullptr));
+        return decode_select(P, d, id_end, time, out, unfinished, indirect, st);
+    });
 }

@@ -651,15 +651,20 @@ class Engine(object):
                  "encoder_fwd")
         return B
 
+    def _chain_fill_up(self, B, *switches):
+        """Would a persistent chain (csrc/xdec.hip) run for B rows once they are filled up to 8, 16, 32 or 64?  The conditions the training and
+        the greedy-decode chain share; `switches`: the environment variables that turn that chain or its fill-up off with "0" (beside LXO_XDEC)."""
+        d = self.dims
+        return (self._chains_possible() and B < 64 and B not in (8, 16, 32)
+                and d["C"] == 512 and d["U"] == 512 and d["O"] == 512 and d["E"] == 256
+                and not any(os.environ.get(v, "1") == "0" for v in ("LXO_XDEC",) + switches))
+
     def _train_chain_batch(self, B, H=None, W=None):
         """The batch the persistent training chains (csrc/xdec.hip: xdec_fwd_kernel / xdec_bwd_kernel) take for B samples -- 8, 16, 32 or 64 --
         or B itself where they would not run anyway (mirrors lxo_launch_xdec_fwd's conditions).  LXO_TRAIN_PAD=0 / Engine.pad_train = False
         switch the padding off (the launch-per-step kernels then take the batch as it is)."""
         d = self.dims
-        if (self.device.type != "cuda" or self.dtype != _abi.LXO_BF16 or self.step_kernels != 0 or B >= 64 or B in (8, 16, 32)
-                or not getattr(self, "pad_train", True) or d.get("row_bilstm")
-                or not (d["C"] == 512 and d["U"] == 512 and d["O"] == 512 and d["E"] == 256)
-                or "0" in (os.environ.get("LXO_TRAIN_PAD", "1"), os.environ.get("LXO_XDEC", "1"))):
+        if not self._chain_fill_up(B, "LXO_TRAIN_PAD") or not getattr(self, "pad_train", True) or d.get("row_bilstm"):
             return B
         Bp = next(n for n in (8, 16, 32, 64) if B < n)
         if H is not None and not d.get("cnn"):
@@ -673,10 +678,7 @@ class Engine(object):
     def _decode_chain_batch(self, B):
         """The batch the persistent greedy-decode chain (csrc/xdec.hip: xdec_dec_kernel) takes for B images -- 8, 16, 32 or 64 -- or B itself where
         the chain would not run anyway (mirrors lxo_launch_xdec_dec's conditions).  LXO_DECODE_PAD=0 switches the padding off."""
-        d = self.dims
-        if (self.device.type != "cuda" or self.dtype != _abi.LXO_BF16 or self.step_kernels != 0 or B >= 64 or B in (8, 16, 32)
-                or not (d["C"] == 512 and d["U"] == 512 and d["O"] == 512 and d["E"] == 256) or self.n_tok > 512
-                or "0" in (os.environ.get("LXO_DECODE_PAD", "1"), os.environ.get("LXO_XDEC_DEC", "1"), os.environ.get("LXO_XDEC", "1"))):
+        if not self._chain_fill_up(B, "LXO_DECODE_PAD", "LXO_XDEC_DEC") or self.n_tok > 512:
             return B
         return next(n for n in (8, 16, 32, 64) if B < n)
 
@@ -713,6 +715,32 @@ class Engine(object):
         return (self._to_dev(np.ascontiguousarray(pf[rows], dtype=np.int32), torch.int32), int(pf.shape[1]),
                 self._to_dev(np.ascontiguousarray(ln[rows], dtype=np.int32), torch.int32))
 
+    def _alpha_buf(self, rows, img):
+        """-> (the attention-map output buffer f32 [max_steps, rows, R padded to 8], R, H', W') of a decode over the features of `img`"""
+        from .model.utils.image import encoder_out_hw
+        Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
+        R = Hp * Wp
+        return torch.zeros(self.max_steps, rows, (R + 7) // 8 * 8, dtype=torch.float32, device=self.device), R, Hp, Wp
+
+    def _run_decode(self, pick, id_end, max_iter):
+        """Calls the whole-loop entry point `pick` = (function, name, its prefix / output arguments); -> the number of steps it ran."""
+        fn, what, args = pick
+        steps = ctypes.c_int(0)
+        self._ck(fn(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter), *args, ctypes.byref(steps),
+                    self._stream()), what)
+        return steps.value
+
+    def _greedy_entry(self, pfx, ids, logp, alpha):
+        """The entry point for the outputs that are present: _scores refuses a null logp_out, _prefix a null prefix; the plain call is bench.py's."""
+        L = self.lib
+        if pfx is not None:
+            return L.lxo_greedy_decode_prefix, "greedy_decode_prefix", (_p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(logp), _p(alpha))
+        if logp is not None:
+            return L.lxo_greedy_decode_scores, "greedy_decode_scores", (_p(ids), _p(logp), _p(alpha))
+        if alpha is not None:
+            return L.lxo_greedy_decode_attn, "greedy_decode_attn", (_p(ids), _p(alpha))
+        return L.lxo_greedy_decode, "greedy_decode", (_p(ids),)
+
     def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False, prefix=None, prefix_lengths=None):
         """ids int32 [B, T'] as pred_test.ids of the greedy graph (decoder.py:64,70).  With return_attention also the
         attention maps alpha f32 [B, T', H', W'] (what the reference collects through its py_func hook,
@@ -736,49 +764,16 @@ class Engine(object):
             img = img[torch.arange(Bp, device=img.device) % B0]
         B = self._encode_only(img, 1)
         ids = torch.zeros(B, self.max_steps, dtype=torch.int32, device=self.device)
-        steps = ctypes.c_int(0)
         logp = torch.zeros(B, self.max_steps, dtype=torch.float32, device=self.device) if return_scores else None
-        if pfx is not None:
-            alpha, R = None, 0
-            if return_attention:
-                from .model.utils.image import encoder_out_hw
-                Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
-                R = Hp * Wp
-                alpha = torch.zeros(self.max_steps, B, (R + 7) // 8 * 8, dtype=torch.float32, device=self.device)
-            self._ck(self.lib.lxo_greedy_decode_prefix(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                       _p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(logp), _p(alpha), ctypes.byref(steps),
-                                                       self._stream()), "greedy_decode_prefix")
-            n = steps.value
-            out = (ids[:B0, :n].cpu().numpy(),)
-            if return_attention:
-                out += (alpha[:n, :, :R].permute(1, 0, 2).reshape(B, n, Hp, Wp).cpu().numpy(),)
-            if return_scores:
-                out += (logp[:B0, :n].cpu().numpy(),)
-            return out if len(out) > 1 else out[0]
-        if not return_attention:
-            if return_scores:
-                self._ck(self.lib.lxo_greedy_decode_scores(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                           _p(ids), _p(logp), None, ctypes.byref(steps), self._stream()), "greedy_decode_scores")
-                return ids[:B0, :steps.value].cpu().numpy(), logp[:B0, :steps.value].cpu().numpy()
-            self._ck(self.lib.lxo_greedy_decode(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                _p(ids), ctypes.byref(steps), self._stream()), "greedy_decode")
-            return ids[:B0, :steps.value].cpu().numpy()
-        from .model.utils.image import encoder_out_hw
-        Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
-        R = Hp * Wp
-        Rp = (R + 7) // 8 * 8
-        alpha = torch.zeros(self.max_steps, B, Rp, dtype=torch.float32, device=self.device)
+        alpha, R, Hp, Wp = self._alpha_buf(B, img) if return_attention else (None, 0, 0, 0)
+        n = self._run_decode(self._greedy_entry(pfx, ids, logp, alpha), id_end, max_iter)
+        out = [ids[:B0, :n]]
+        if return_attention:
+            out.append(alpha[:n, :B0, :R].permute(1, 0, 2).reshape(B0, n, Hp, Wp))
         if return_scores:
-            self._ck(self.lib.lxo_greedy_decode_scores(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                       _p(ids), _p(logp), _p(alpha), ctypes.byref(steps), self._stream()), "greedy_decode_scores")
-        else:
-            self._ck(self.lib.lxo_greedy_decode_attn(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                     _p(ids), _p(alpha), ctypes.byref(steps), self._stream()), "greedy_decode_attn")
-        n = steps.value
-        a = alpha[:n, :, :R].permute(1, 0, 2).reshape(B, n, Hp, Wp).cpu().numpy()
-        if return_scores:
-            return ids[:, :n].cpu().numpy(), a, logp[:, :n].cpu().numpy()
-        return ids[:, :n].cpu().numpy(), a
+            out.append(logp[:B0, :n])
+        out = tuple(a.cpu().numpy() for a in out)
+        return out if len(out) > 1 else out[0]
 
     def _check_beam(self, beam_size):
         """a beam wider than the vocabulary has no k-th candidate at time 0 (tf.nn.top_k raises there too); the kernels take k <= 16"""
@@ -788,6 +783,11 @@ class Engine(object):
         if k > 16:
             raise ValueError("beam width %d exceeds 16, the widest beam the decode kernels take" % k)
 
+    def _set_diversity(self, div_gamma, div_prob, div_seed):
+        """add_div_penalty of beam_search_decoder_cell.py:258-287 for the bound shape (off at gamma 1 / probability 0)"""
+        self.shape.div_gamma, self.shape.div_prob = float(div_gamma or 0.0), float(div_prob or 0.0)
+        self.shape.div_seed = int(div_seed) & 0x7FFFFFFF
+
     # one step at a time: what model/components (the reference's decoder-cell protocol) drives
     def decode_begin(self, img, beam_size=1, max_steps=152, div_gamma=1.0, div_prob=0.0, div_seed=0):
         """initialize(): encoder + attention set-up + initial states for beam_size hypotheses per image."""
@@ -795,8 +795,7 @@ class Engine(object):
         if self.max_steps < max_steps:
             self.max_steps, self.ws = int(max_steps), None
         B = self._encode_only(img, int(beam_size))
-        self.shape.div_gamma, self.shape.div_prob = float(div_gamma or 0.0), float(div_prob or 0.0)
-        self.shape.div_seed = int(div_seed) & 0x7FFFFFFF
+        self._set_diversity(div_gamma, div_prob, div_seed)
         k = max(1, int(beam_size))
         shp = (B, self.max_steps) if k == 1 else (B, self.max_steps, k)
         self._dec_ids = torch.zeros(*shp, dtype=torch.int32, device=self.device)
@@ -854,6 +853,17 @@ class Engine(object):
         Vp = (self.n_tok + 31) // 32 * 32
         return self.region("dec_logits", "f32", (self._dec_rows(), Vp))[:, :self.n_tok].cpu().numpy()
 
+    def _beam_entry(self, pfx, ids, par, sc, alpha):
+        """The entry point for the outputs that are present (as _greedy_entry; _attn refuses a null alpha_out too)."""
+        L = self.lib
+        if pfx is not None:
+            return L.lxo_beam_decode_prefix, "beam_decode_prefix", (_p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(par), _p(sc), _p(alpha))
+        if sc is not None:
+            return L.lxo_beam_decode_scores, "beam_decode_scores", (_p(ids), _p(par), _p(sc), _p(alpha))
+        if alpha is not None:
+            return L.lxo_beam_decode_attn, "beam_decode_attn", (_p(ids), _p(par), _p(alpha))
+        return L.lxo_beam_decode, "beam_decode", (_p(ids), _p(par))
+
     def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False,
                     return_scores=False, prefix=None, prefix_lengths=None):
         """ids int32 [B, T', k] as pred_test.ids of the beam graph before the transpose at img2seq.py:241.
@@ -870,60 +880,18 @@ class Engine(object):
         B0 = int(img.shape[0])
         pfx = self._prefix_args(prefix, prefix_lengths, B0, B0, id_end, max_iter) if prefix is not None else None
         B = self._encode_only(img, int(beam_size))
-        self.shape.div_gamma, self.shape.div_prob = float(div_gamma or 0.0), float(div_prob or 0.0)
-        self.shape.div_seed = int(div_seed) & 0x7FFFFFFF
+        self._set_diversity(div_gamma, div_prob, div_seed)
         ids = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         par = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
-        steps = ctypes.c_int(0)
-        if pfx is not None:
-            sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device) if return_scores else None
-            alpha = None
-            if return_attention:
-                from .model.utils.image import encoder_out_hw
-                Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
-                R = Hp * Wp
-                alpha = torch.zeros(self.max_steps, B * beam_size, (R + 7) // 8 * 8, dtype=torch.float32, device=self.device)
-            self._ck(self.lib.lxo_beam_decode_prefix(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                     _p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(par), _p(sc), _p(alpha), ctypes.byref(steps),
-                                                     self._stream()), "beam_decode_prefix")
-            n = steps.value
-            out = (ids[:, :n].cpu().numpy(),)
-            if return_parents or return_attention or return_scores:
-                out += (par[:, :n].cpu().numpy(),)
-            if return_attention:
-                out += (alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous().cpu().numpy(),)
-            if return_scores:
-                out += (sc[:, :n].cpu().numpy(),)
-            return out if len(out) > 1 else out[0]
-        if return_scores:
-            sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device)
-            alpha, a = None, None
-            if return_attention:
-                from .model.utils.image import encoder_out_hw
-                Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
-                R = Hp * Wp
-                alpha = torch.zeros(self.max_steps, B * beam_size, (R + 7) // 8 * 8, dtype=torch.float32, device=self.device)
-            self._ck(self.lib.lxo_beam_decode_scores(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                     _p(ids), _p(par), _p(sc), _p(alpha), ctypes.byref(steps), self._stream()), "beam_decode_scores")
-            n = steps.value
-            out = (ids[:, :n].cpu().numpy(), par[:, :n].cpu().numpy())
-            if return_attention:
-                out += (alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous().cpu().numpy(),)
-            return out + (sc[:, :n].cpu().numpy(),)
+        sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device) if return_scores else None
+        alpha, R, Hp, Wp = self._alpha_buf(B * beam_size, img) if return_attention else (None, 0, 0, 0)
+        n = self._run_decode(self._beam_entry(pfx, ids, par, sc, alpha), id_end, max_iter)
+        out = [ids[:, :n]]
+        if return_parents or return_attention or return_scores:
+            out.append(par[:, :n])
         if return_attention:
-            from .model.utils.image import encoder_out_hw
-            Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
-            R = Hp * Wp
-            Rp = (R + 7) // 8 * 8
-            alpha = torch.zeros(self.max_steps, B * beam_size, Rp, dtype=torch.float32, device=self.device)
-            self._ck(self.lib.lxo_beam_decode_attn(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                                   _p(ids), _p(par), _p(alpha), ctypes.byref(steps), self._stream()), "beam_decode_attn")
-            n = steps.value
-            a = alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous().cpu().numpy()
-            return ids[:, :n].cpu().numpy(), par[:, :n].cpu().numpy(), a
-        self._ck(self.lib.lxo_beam_decode(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), int(id_end), int(max_iter),
-                                          _p(ids), _p(par), ctypes.byref(steps), self._stream()), "beam_decode")
-        out = ids[:, :steps.value].cpu().numpy()
-        if return_parents:
-            return out, par[:, :steps.value].cpu().numpy()
-        return out
+            out.append(alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
+        if return_scores:
+            out.append(sc[:, :n])
+        out = tuple(a.cpu().numpy() for a in out)
+        return out if len(out) > 1 else out[0]

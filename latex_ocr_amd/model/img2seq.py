@@ -131,16 +131,20 @@ class Img2SeqModel(BaseModel):
         scores["perplexity"] = perp
         return scores
 
+    def _beam_kwargs(self):
+        """The diversity-penalty arguments of one Engine.beam_decode call (decoder.py:67-68); the seed is the number of beam decodes so far."""
+        cfg = self._config
+        self._div_calls = getattr(self, "_div_calls", 0) + 1
+        return dict(div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0), div_seed=self._div_calls)
+
     def _decode(self, img):
         """pred_test.ids of the decode graph (decoder.py:60-70), shaped [B, k, T'] as after
         img2seq.py:238-241."""
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1          # decoder.py:70
         if getattr(cfg, "decoding", "greedy") == "beam_search":
-            self._div_calls = getattr(self, "_div_calls", 0) + 1
             ids, par = self.engine.beam_decode(img, self._vocab.id_end, cfg.beam_size, max_iter=max_iter, return_parents=True,
-                                               div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0),
-                                               div_seed=self._div_calls)         # decoder.py:67-68
+                                               **self._beam_kwargs())
             if getattr(cfg, "beam_backtrace", False):      # extension: follow parents (the reference never does, quirk C-1)
                 from .utils.text import beam_backtrace
                 ids = beam_backtrace(ids, par)
@@ -229,10 +233,8 @@ class Img2SeqModel(BaseModel):
         id_end = self._vocab.id_end
         if getattr(cfg, "decoding", "greedy") == "beam_search":
             from .utils.text import beam_backtrace
-            self._div_calls = getattr(self, "_div_calls", 0) + 1
-            ids, par, sc = self.engine.beam_decode(fd["img"], id_end, cfg.beam_size, max_iter=max_iter,
-                                                   div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0),
-                                                   div_seed=self._div_calls, return_scores=True, prefix=prefix, prefix_lengths=prefix_lengths)
+            ids, par, sc = self.engine.beam_decode(fd["img"], id_end, cfg.beam_size, max_iter=max_iter, return_scores=True,
+                                                   prefix=prefix, prefix_lengths=prefix_lengths, **self._beam_kwargs())
             ids, run = beam_backtrace(ids, par), beam_backtrace(sc, par)          # token paths and their running log-probs
             tok = np.diff(run, axis=1, prepend=0.0)
         else:
@@ -268,10 +270,8 @@ class Img2SeqModel(BaseModel):
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1
         if getattr(cfg, "decoding", "greedy") == "beam_search":
-            self._div_calls = getattr(self, "_div_calls", 0) + 1
-            ids, par, alpha = self.engine.beam_decode(fd["img"], self._vocab.id_end, cfg.beam_size, max_iter=max_iter,
-                                                      div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0),
-                                                      div_seed=self._div_calls, return_attention=True)
+            ids, par, alpha = self.engine.beam_decode(fd["img"], self._vocab.id_end, cfg.beam_size, max_iter=max_iter, return_attention=True,
+                                                      **self._beam_kwargs())
             if getattr(cfg, "beam_backtrace", False):
                 from .utils.text import beam_backtrace, beam_slots
                 slot = beam_slots(par)[0, :, 0]

@@ -1,4 +1,6 @@
 """Shared helpers of the -m gpu parity tests (HIP path through the C ABI vs the CPU oracle)."""
+import os
+
 import numpy as np
 import torch
 
@@ -18,6 +20,39 @@ def batch(n, H, W, V, lo, hi, seed):
 
 def oracle_params(eng):
     return {k: torch.from_numpy(v.copy()) for k, v in eng.get_params().items()}
+
+
+def train_end_params(V):
+    """Weights that emit END at staggered steps: 260 bf16 Adam steps on tests/test_gpu_benchcfg.py's count_set (ink density tells the formula
+    length).  For the modules' own module-scoped `end_params` fixtures."""
+    from test_gpu_benchcfg import count_set
+    eng = Engine(V, dtype="bf16", seed=0)
+    for step in range(260):
+        imgs, forms = count_set(16, 100 + step)
+        f, l = pad_batch_formulas(forms, V - 2, V - 1)
+        eng.train_step(pad_batch_images(imgs), f, l, 1e-3, sync_loss=False)
+    torch.cuda.synchronize()
+    return eng.get_params()
+
+
+def first_end(row, end):
+    """position of the first `end` in a row of ids, -1 if there is none"""
+    e = np.flatnonzero(np.asarray(row) == end)
+    return int(e[0]) if e.size else -1
+
+
+def with_env(key, val, fn):
+    """fn() with the environment variable `key` set to `val` (None: left as it is), restored afterwards"""
+    old = os.environ.get(key)
+    if val is not None:
+        os.environ[key] = val
+    try:
+        return fn()
+    finally:
+        if old is None:
+            os.environ.pop(key, None)
+        else:
+            os.environ[key] = old
 
 
 def rel(a, b):

@@ -20,13 +20,7 @@ from test_gpu_benchcfg import count_set, V, H, W
 
 @pytest.fixture(scope="module")
 def end_params():
-    eng = Engine(V, dtype="bf16", seed=0)
-    for step in range(260):
-        imgs, forms = count_set(16, 100 + step)
-        f, l = pad_batch_formulas(forms, V - 2, V - 1)
-        eng.train_step(pad_batch_images(imgs), f, l, 1e-3, sync_loss=False)
-    torch.cuda.synchronize()
-    return eng.get_params()
+    return train_end_params(V)
 
 
 def _decode(params, img, step_kernels, max_iter, seed=0):
@@ -39,10 +33,6 @@ def _decode(params, img, step_kernels, max_iter, seed=0):
     return ids, used, err
 
 
-def _first_end(ids):
-    return [int(np.argmax(r == V - 1)) if (r == V - 1).any() else -1 for r in ids]
-
-
 @pytest.mark.parametrize("B", [64, 32, 16, 8])
 def test_decode_chain_equals_launch_per_step_early_exit(end_params, B):
     imgs, forms = count_set(B, 300 + B)
@@ -51,7 +41,7 @@ def test_decode_chain_equals_launch_per_step_early_exit(end_params, B):
     assert used and err == 0, (used, err)                      # the chain ran (8 x 32 tickets) and no hand-over timed out
     b, used_b, _ = _decode(end_params, img, 2, 151)
     assert not used_b
-    first = _first_end(b)
+    first = [first_end(r, V - 1) for r in b]
     print("B=%d: %d steps (chain) / %d (launch per step); first END per row: %d distinct positions, %d .. %d" % (
         B, a.shape[1], b.shape[1], len(set(first)), min(first), max(first)))
     assert b.shape[1] < 152 and min(first) >= 0                # every row emitted END: the loop stopped early ...
@@ -66,15 +56,7 @@ def test_decode_chain_early_exit_across_launches(end_params, chunk):
     find the stop word and return"""
     imgs, forms = count_set(16, 12)
     img = pad_batch_images(imgs)
-    old = os.environ.get("LXO_XDEC_DEC_CHUNK")
-    os.environ["LXO_XDEC_DEC_CHUNK"] = chunk
-    try:
-        a, used, err = _decode(end_params, img, 0, 151)
-    finally:
-        if old is None:
-            os.environ.pop("LXO_XDEC_DEC_CHUNK", None)
-        else:
-            os.environ["LXO_XDEC_DEC_CHUNK"] = old
+    a, used, err = with_env("LXO_XDEC_DEC_CHUNK", chunk, lambda: _decode(end_params, img, 0, 151))
     assert used and err == 0, (used, err)
     b, _, _ = _decode(end_params, img, 2, 151)
     assert a.shape == b.shape and b.shape[1] > int(chunk), (a.shape, b.shape)

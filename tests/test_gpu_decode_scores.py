@@ -27,13 +27,7 @@ END = V - 1
 @pytest.fixture(scope="module")
 def end_params():
     """weights that emit END at staggered steps (the recipe of tests/test_gpu_decchain.py)"""
-    eng = Engine(V, dtype="bf16", seed=0)
-    for step in range(260):
-        imgs, forms = count_set(16, 100 + step)
-        f, l = pad_batch_formulas(forms, V - 2, V - 1)
-        eng.train_step(pad_batch_images(imgs), f, l, 1e-3, sync_loss=False)
-    torch.cuda.synchronize()
-    return eng.get_params()
+    return train_end_params(V)
 
 
 def _engine(dtype, params=None, step_kernels=0, seed=0):
@@ -42,11 +36,6 @@ def _engine(dtype, params=None, step_kernels=0, seed=0):
         eng.load_params(params)
     eng.step_kernels = step_kernels
     return eng
-
-
-def _first_end(row):
-    e = np.flatnonzero(row == END)
-    return int(e[0]) + 1 if e.size else len(row)
 
 
 def _agree_prefix(a, b):
@@ -69,19 +58,6 @@ def test_greedy_f32_logp_vs_oracle():
     assert err < 1e-4
 
 
-def _with_chunk(chunk, fn):
-    old = os.environ.get("LXO_XDEC_DEC_CHUNK")
-    if chunk:
-        os.environ["LXO_XDEC_DEC_CHUNK"] = chunk
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop("LXO_XDEC_DEC_CHUNK", None)
-        else:
-            os.environ["LXO_XDEC_DEC_CHUNK"] = old
-
-
 @pytest.mark.parametrize("B,chunk", [(64, None), (32, None), (16, None), (8, None), (64, "3"), (16, "3")])
 def test_greedy_bf16_chain_scores(end_params, B, chunk):
     img = pad_batch_images(count_set(B, 300 + B)[0])
@@ -93,7 +69,7 @@ def test_greedy_bf16_chain_scores(end_params, B, chunk):
         b, lp = eng.greedy_decode(img, END, max_iter=151, return_scores=True)
         used, err = eng.chain_status()
         return a, (used0, err0), b, lp, (used, err)
-    a, st0, b, lp, st = _with_chunk(chunk, run)
+    a, st0, b, lp, st = with_env("LXO_XDEC_DEC_CHUNK", chunk, run)
     assert st0 == (True, 0) and st == (True, 0), (st0, st)                  # both calls ran the chain, no hand-over timed out
     assert np.array_equal(a, b)                                             # ids bit-identical with and without scores
     c, lpc = _engine("bf16", end_params, step_kernels=2).greedy_decode(img, END, max_iter=151, return_scores=True)
@@ -125,8 +101,8 @@ def test_sequence_logp_is_minus_the_training_ce(end_params, dtype, bar):
     for im in imgs:
         img = pad_batch_images([im])
         ids, lp = eng.greedy_decode(img, END, max_iter=151, return_scores=True)
-        n = _first_end(ids[0])
-        assert ids[0, n - 1] == END
+        n = first_end(ids[0], END) + 1
+        assert n > 0 and ids[0, n - 1] == END
         f, l = pad_batch_formulas([list(ids[0, :n - 1])], V - 2, V - 1)
         ce, nw = eng.evaluate_batch(img, f, l)
         assert nw == n

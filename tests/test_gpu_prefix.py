@@ -27,13 +27,7 @@ END = V - 1
 
 @pytest.fixture(scope="module")
 def end_params():
-    eng = Engine(V, dtype="bf16", seed=0)
-    for step in range(260):
-        imgs, forms = count_set(16, 100 + step)
-        f, l = pad_batch_formulas(forms, V - 2, V - 1)
-        eng.train_step(pad_batch_images(imgs), f, l, 1e-3, sync_loss=False)
-    torch.cuda.synchronize()
-    return eng.get_params()
+    return train_end_params(V)
 
 
 def _engine(dtype, params, step_kernels=0):
@@ -46,18 +40,6 @@ def _engine(dtype, params, step_kernels=0):
 def _prefix(B, T, seed):
     """ids in [0, END): mostly off the model's own path (it writes 7s)"""
     return np.random.RandomState(seed).randint(0, END, size=(B, T)).astype(np.int32)
-
-
-def _with_env(key, val, fn):
-    old = os.environ.get(key)
-    os.environ[key] = val
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(key, None)
-        else:
-            os.environ[key] = old
 
 
 def _oracle_enc(params, img):
@@ -160,8 +142,8 @@ def test_own_greedy_prefix_gives_the_same_decode(end_params, dtype):
     img = pad_batch_images(count_set(16, 53)[0])
     eng = _engine(dtype, end_params)
     ids, lp = eng.greedy_decode(img, END, max_iter=151, return_scores=True)
-    first_end = [int(np.flatnonzero(r == END)[0]) if (r == END).any() else ids.shape[1] for r in ids]
-    ln = np.array([min(i % 5, first_end[i]) for i in range(16)], np.int32)      # never END inside a prefix
+    ends = [first_end(r, END) if (r == END).any() else ids.shape[1] for r in ids]
+    ln = np.array([min(i % 5, ends[i]) for i in range(16)], np.int32)      # never END inside a prefix
     assert ln.max() > 0
     ids2, lp2 = eng.greedy_decode(img, END, max_iter=151, return_scores=True, prefix=ids[:, :4].copy(), prefix_lengths=ln)
     if dtype == "bf16":
@@ -208,7 +190,7 @@ def test_chain_prefix_across_launches(end_params, lens):
         eng = _engine("bf16", end_params)
         out = eng.greedy_decode(img, END, max_iter=151, return_scores=True, prefix=pf, prefix_lengths=ln)
         return out, eng.chain_status()
-    (a, la), st = _with_env("LXO_XDEC_DEC_CHUNK", "3", run)
+    (a, la), st = with_env("LXO_XDEC_DEC_CHUNK", "3", run)
     assert st == (True, 0), st
     (c, lc), _ = run()
     b, lb = _engine("bf16", end_params, step_kernels=2).greedy_decode(img, END, max_iter=151, return_scores=True, prefix=pf, prefix_lengths=ln)
