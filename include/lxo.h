@@ -318,6 +318,21 @@ int lxo_greedy_decode_scores(const lxo_shape* s, const float* params, const void
 int lxo_greedy_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
                              const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
                              int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream);
+/* Greedy decode under a token constraint: an ALLOWED-TOKEN SET PER IMAGE.  allow (device, NOT NULL): bit sets, bit v & 31 of word v >> 5
+ * of row b set = token v may be emitted by image b; allow_ld in words: 0 = one set shared by every image, else >= (V + 31) / 32 and allow
+ * is [B][allow_ld].  Bits at or beyond V are ignored.  The one rule: a banned vocabulary column behaves as a column outside the
+ * vocabulary -- its logit is -inf before anything else happens in the select step.  So the arg-max runs over the allowed columns (ties:
+ * the lower index) and logp_out (nullable) holds logit - logsumexp(allowed logits), the model's distribution renormalised over the set;
+ * with every column allowed the outputs are those of lxo_greedy_decode_prefix / _scores.  The set is constant over the steps of a call.
+ * prefix / prefix_ld / prefix_len: as in lxo_greedy_decode_prefix, or all NULL / 0 for no prefix; a forced id is emitted as given, its
+ * log-prob taken under the same renormalised distribution.  Contract: in every row id_end is allowed and at least one token is; no forced
+ * prefix token is banned in its row.  The device reads defensively: a row that breaks the contract does not fault or hang (it may emit id 0
+ * and an unspecified log-prob).  -1: NULL allow, allow_ld < 0 or 0 < allow_ld < (V + 31) / 32, half a prefix.  alpha_out non-NULL runs the
+ * launch-per-step path.  lxo_decode_step and lxo_score_tokens take no constraint. */
+int lxo_greedy_decode_constrained(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                  const uint32_t* allow, int allow_ld,
+                                  const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                  int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream);
 /* The same loops ONE STEP AT A TIME: the calls behind the reference's decoder-cell protocol (dynamic_decode.py:35-36,43-44:
  * decoder_cell.initialize() / .step(time, state, inputs, finished); greedy_decoder_cell.py:46-66,
  * beam_search_decoder_cell.py:113-187).  latex_ocr_amd/model/components/ wraps them in cell objects with the reference's
@@ -375,6 +390,17 @@ int lxo_beam_decode_scores(const lxo_shape* s, const float* params, const void* 
 int lxo_beam_decode_prefix(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
                            const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
                            int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream);
+/* Beam decode under a token constraint (allow / allow_ld as in lxo_greedy_decode_constrained: ONE ROW PER IMAGE, shared by its beam slots;
+ * prefix as in lxo_beam_decode_prefix or all NULL / 0).  log_softmax runs over the allowed columns; a banned candidate (slot, token) scores
+ * -inf and is never selected, also for a finished hypothesis (whose only live candidate stays END at 0); the diversity penalty ranks banned
+ * columns last, so the rank of an allowed column is the number of allowed columns ahead of it, and its Bernoulli hash keeps the
+ * (time, row, id, V) indexing.  Contract, beyond the greedy call's: every row allows at least `beam` tokens (the first free step selects k
+ * candidates from slot 0 alone -- why beam > V is refused).  With every column allowed the outputs are those of lxo_beam_decode_prefix /
+ * _scores. */
+int lxo_beam_decode_constrained(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                const uint32_t* allow, int allow_ld,
+                                const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream);
 
 /* ---- data parallel: one process per GPU, RCCL over xGMI -------------------------------------
  * The reference trains on one device (one sess.run per step, model/img2seq.py:169).  Samples are independent through encoder,

@@ -208,6 +208,26 @@ extern "C" int lxo_greedy_decode_prefix(const lxo_shape* s, const float* params,
     CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_prefix");
     return 0;
 }
+// the _constrained calls' sets (decoder_kernels.h) and optional prefix; what is refused, or null
+static const char* make_constraint(DecAllow* al, DecPrefix* pf, bool* has_prefix, int V, const uint32_t* allow, int allow_ld,
+                                   const int32_t* prefix, int prefix_ld, const int32_t* prefix_len, int max_iter) {
+    *al = DecAllow{allow, allow_ld};
+    if (!allow || allow_ld < 0 || (allow_ld != 0 && allow_ld < (V + 31) / 32)) return "lxo_*_decode_constrained: null allow or 0 < allow_ld < (V + 31) / 32";
+    *has_prefix = prefix || prefix_len || prefix_ld != 0;
+    if (*has_prefix && !make_prefix(pf, prefix, prefix_ld, prefix_len, max_iter)) return "lxo_*_decode_constrained: a prefix needs prefix, prefix_len and prefix_ld >= 1 (none: all NULL / 0)";
+    return nullptr;
+}
+extern "C" int lxo_greedy_decode_constrained(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                             const uint32_t* allow, int allow_ld, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                             int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    DecAllow al; DecPrefix pf; bool has_prefix = false;
+    if (const char* why = make_constraint(&al, &pf, &has_prefix, P.s.V, allow, allow_ld, prefix, prefix_ld, prefix_len, max_iter))
+        return fail(-1, why);
+    const DecodeOuts o = {ids_out, nullptr, logp_out, alpha_out, has_prefix ? &pf : nullptr, &al};
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_constrained");
+    return 0;
+}
 extern "C" int lxo_decode_begin(const lxo_shape* s, const float* params, const void* wpack, void* ws, void* stream) {
     MAKE_PLAN(P, s);
     CHECK_LAUNCH(lxo_impl_decode_begin(P, params, wpack, ws, (hipStream_t)stream), "lxo_decode_begin");
@@ -251,6 +271,17 @@ extern "C" int lxo_beam_decode_prefix(const lxo_shape* s, const float* params, c
     if (!make_prefix(&pf, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, "lxo_beam_decode_prefix: null prefix / prefix_len or prefix_ld < 1");
     const DecodeOuts o = {ids_out, parents_out, scores_out, alpha_out, &pf};
     CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_beam_decode_prefix");
+    return 0;
+}
+extern "C" int lxo_beam_decode_constrained(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                           const uint32_t* allow, int allow_ld, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                           int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    DecAllow al; DecPrefix pf; bool has_prefix = false;
+    if (const char* why = make_constraint(&al, &pf, &has_prefix, P.s.V, allow, allow_ld, prefix, prefix_ld, prefix_len, max_iter))
+        return fail(-1, why);
+    const DecodeOuts o = {ids_out, parents_out, scores_out, alpha_out, has_prefix ? &pf : nullptr, &al};
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_beam_decode_constrained");
     return 0;
 }
 

@@ -46,14 +46,17 @@ int lxo_k_init_bwd(const float* dcc, Slabs dxh, const float* c0, const float* re
 // A forced decode prefix (lxo_greedy_decode_prefix / lxo_beam_decode_prefix), device arrays: row (greedy) or image (beam) r emits ids[r][t] at
 // steps t < len[r]; lim = min(ld, max_iter) bounds a length (decoder_kernels.hip: how out-of-range values are read)
 struct DecPrefix { const int* ids; const int* len; int ld; int lim; };
+// Allowed-token sets (lxo_greedy_decode_constrained / lxo_beam_decode_constrained), device bit sets: bit v & 31 of word v >> 5 of row b set = image b
+// may emit token v; ld words per row, 0 = one row shared by every image.  A banned column is read as a column outside the vocabulary
+struct DecAllow { const unsigned* bits; int ld; };
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
                  int* finished, int* n_unfinished, hipStream_t st, float* logp_out = nullptr,      // logp_out (nullable): [n][max_steps] log-prob of the id
-                 const DecPrefix* prefix = nullptr);
+                 const DecPrefix* prefix = nullptr, const DecAllow* allow = nullptr);
 int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
                     float* scratch, float* logp, int* finished,
                     int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
                     float* scores_out = nullptr,      // scores_out (nullable): [nimg][max_steps][k] the running log-probs after the step
-                    const DecPrefix* prefix = nullptr);
+                    const DecPrefix* prefix = nullptr, const DecAllow* allow = nullptr);      // allow: one row per IMAGE
 int lxo_k_beam_gather(float* rec, int ldr, int XH, float* cs, int U, const int* parents, int k, float* tmp_rec, float* tmp_cs, int n, void* recb, int ldrb, hipStream_t st);      // recb (nullable): bf16 mirror of the re-ordered [o | h] rows
 int lxo_k_tile_rows(const float* src, int lds, float* dst, int ldd, int n, int k, int cols, hipStream_t st);
 int lxo_k_global_norm_scale(long long n, const float* g, float clip, float* sumsq_tmp, float* out, hipStream_t st);

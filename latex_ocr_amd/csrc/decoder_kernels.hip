@@ -1506,20 +1506,29 @@ __global__ __launch_bounds__(256) void init_bwd_kernel(const float* __restrict__
 // 0 -- so that no caller error faults.
 LXO_DEV int pfx_len(const DecPrefix& q, int r) { return min(max(q.len[r], 0), q.lim); }
 LXO_DEV int pfx_id(const DecPrefix& q, int r, int t, int V) { const int f = q.ids[(long long)r * q.ld + t]; return (f >= 0 && f < V) ? f : 0; }
+// Allowed-token sets (AL instantiations, DecAllow in decoder_kernels.h): a banned column is a column outside the vocabulary -- its logit is
+// -inf before anything else happens in the select step.  The words of a row are read inside [0, (V + 31) / 32): nothing faults on any content.
+LXO_DEV const unsigned* alw_row(const DecAllow& q, int r) { return q.bits + (long long)r * q.ld; }
+LXO_DEV bool alw_ok(const unsigned* row, int v) { return (row[v >> 5] >> (v & 31)) & 1u; }
 
 // greedy_decoder_cell.py:58-64: id = argmax (first max), finished |= id == END; one wave per row.
 // logp_out (nullable) [n][max_steps]: log_softmax(logits)[id] = logits[id] - lse, the log-sum-exp from one more pass over the row the wave has read
 // PF: at a step inside its prefix a row emits the forced id f (logp: logits[f] - lse) and stays unfinished
-template <bool PF>
+// AL: banned columns are skipped in the max pass and in the exp-sum pass (a forced id's log-prob is taken under the same renormalised distribution)
+template <bool PF, bool AL>
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int Vp, int V, int n, int id_end,
                                                     int* __restrict__ ids_step, int* __restrict__ ids_out, int max_steps, int step,
                                                     int* __restrict__ finished, int* __restrict__ n_unfinished, float* __restrict__ logp_out,
-                                                    DecPrefix pf) {
+                                                    DecPrefix pf, DecAllow al) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
     const float* lg = logits + (long long)row * Vp;
     float best = -3.0e38f; int bi = 0x7fffffff;
+    const unsigned* ar = nullptr;
+    if constexpr (AL) ar = alw_row(al, row);
+    if constexpr (AL) { for (int j = lane; j < V; j += 64) { const float x = lg[j]; if (alw_ok(ar, j) && x > best) { best = x; bi = j; } } }
+    else
     for (int j = lane; j < V; j += 64) { const float x = lg[j]; if (x > best) { best = x; bi = j; } }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -1531,6 +1540,8 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
     float lp = 0.f;
     if (logp_out) {
         float l = 0.f;
+        if constexpr (AL) { for (int j = lane; j < V; j += 64) if (alw_ok(ar, j)) l += expf(lg[j] - best); }
+        else
         for (int j = lane; j < V; j += 64) l += expf(lg[j] - best);
         lp = -logf(wave_sum(l));                               // logits[id] - (best + log l), logits[id] = best
         if constexpr (PF) { if (fi >= 0) lp += lg[fi] - best; }
@@ -1568,27 +1579,36 @@ LXO_DEV void beam_forced_out(int b, int k, int tid, int time, int id, float v, i
     finished[b * k + tid] = fin;
     if (!fin) atomicAdd(n_unfinished, 1);
 }
-
-template <bool PF>
+// AL (both beam kernels): the log-sum-exp runs over image b's allowed columns; a banned candidate (slot, token) scores -inf, also for a finished
+// hypothesis, and is never selected while an allowed one is left; the diversity rank of an allowed column counts the allowed columns ahead of it.
+template <bool PF, bool AL>
 __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logits, int Vp, int V, int k, int id_end, int time, DivPen dp,
                                                        float* __restrict__ logp, int* __restrict__ finished,
                                                        int* __restrict__ ids_step, int* __restrict__ parents_step,
                                                        int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                       int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf) {
+                                                       int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf, DecAllow al) {
     __shared__ float lse[16];
     __shared__ float cand_v[16 * 4]; __shared__ int cand_i[16 * 4];
     __shared__ float sel_v[16]; __shared__ int sel_i[16];
     __shared__ int fin_old[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float FMIN = -3.40282347e38f;
+    const unsigned* ar = nullptr;
+    if constexpr (AL) ar = alw_row(al, b);
     // log-sum-exp per beam (one wave per beam, round-robin)
     for (int j = wave; j < k; j += 4) {
         const float* lg = logits + ((long long)b * k + j) * Vp;
         float m = -3.0e38f;
+        float l = 0.f;
+        if constexpr (AL) {
+            for (int c = lane; c < V; c += 64) if (alw_ok(ar, c)) m = fmaxf(m, lg[c]);
+            m = wave_max(m);
+            for (int c = lane; c < V; c += 64) if (alw_ok(ar, c)) l += expf(lg[c] - m);
+        } else {
         for (int c = lane; c < V; c += 64) m = fmaxf(m, lg[c]);
         m = wave_max(m);
-        float l = 0.f;
         for (int c = lane; c < V; c += 64) l += expf(lg[c] - m);
+        }
         l = wave_sum(l);
         if (lane == 0) lse[j] = m + logf(l);
     }
@@ -1618,6 +1638,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
             const float f = fin_old[j] ? 1.f : 0.f;
             sl = (1.f - f) * sl + f * (c == id_end ? 0.f : FMIN);
             row0[j * Vp + c] = logp[b * k + j] + sl;
+            if constexpr (AL) { if (!alw_ok(ar, c)) row0[j * Vp + c] = -INFINITY; }
         }
         __syncthreads();
         for (int i = tid; i < k * V; i += 256) {
@@ -1628,6 +1649,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
             for (int q = 0; q < V; ++q) { const float w = row[q]; rank += (w > v || (w == v && q < c)) ? 1 : 0; }
             const Drop dd = {dp.thr, 1.f, dp.seed, time, b * k + j, (int)gridDim.x * k};
             pen[j * Vp + c] = v + dp.log_gamma * (float)rank * drop_scale(dd, 3u, 0, c, V);
+            if constexpr (AL) { if (!alw_ok(ar, c)) pen[j * Vp + c] = -INFINITY; }
         }
         __syncthreads();
     }
@@ -1645,6 +1667,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
                 const float f = fin_old[j] ? 1.f : 0.f;
                 sl = (1.f - f) * sl + f * (c == id_end ? 0.f : FMIN);
                 val = logp[b * k + j] + sl;
+                if constexpr (AL) { if (!alw_ok(ar, c)) val = -INFINITY; }
             }
             if (val > best || (val == best && i < bi)) { best = val; bi = i; }
         }
@@ -1718,12 +1741,12 @@ LXO_DEV void wave_argmax(float& v, int& i) {
     }
 }
 #endif
-template <bool PF>
+template <bool PF, bool AL>
 __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __restrict__ logits, int Vp, int V, int k, int id_end, int time,
                                                             float* __restrict__ logp, int* __restrict__ finished,
                                                             int* __restrict__ ids_step, int* __restrict__ parents_step,
                                                             int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                            int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf) {
+                                                            int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf, DecAllow al) {
     __shared__ float lse[16];
     __shared__ float sel_v[16]; __shared__ int sel_i[16];
     __shared__ int fin_old[16];
@@ -1733,6 +1756,8 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
     __shared__ float wc_v[BS_NW * 16]; __shared__ int wc_i[BS_NW * 16];      // the waves' k best each
     int t0 = 0;                                                // PF: the image's prefix length (beam_step_kernel)
     if constexpr (PF) t0 = pfx_len(pf, b);
+    const unsigned* ar = nullptr;                              // AL: the image's allowed-token bits
+    if constexpr (AL) ar = alw_row(al, b);
     const int nb = time > t0 ? k : 1;
     const int total = nb * V;
     float raw[BS_NPT];                                         // raw logits of this thread's candidates (unconditional, clamped: requested before anything is waited for)
@@ -1751,6 +1776,9 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
         // for its two passes
         constexpr int RQ = 8 / BS_NW > 0 ? 8 / BS_NW : 1;
         float x[RQ][8];
+        bool ok8[8];                                           // AL: column lane + 64 u is allowed (the same for every hypothesis of the image)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { ok8[u] = true; if constexpr (AL) { const int c = lane + 64 * u; ok8[u] = alw_ok(ar, c < V ? c : V - 1); } }
 #pragma unroll
         for (int q = 0; q < RQ; ++q) {
             const int j = min(wave + BS_NW * q, k - 1);
@@ -1763,11 +1791,11 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
             const int j = wave + BS_NW * q;
             float m = -3.0e38f;
 #pragma unroll
-            for (int u = 0; u < 8; ++u) if (lane + 64 * u < V) m = fmaxf(m, x[q][u]);
+            for (int u = 0; u < 8; ++u) if (lane + 64 * u < V && ok8[u]) m = fmaxf(m, x[q][u]);
             m = wave_max(m);
             float l = 0.f;
 #pragma unroll
-            for (int u = 0; u < 8; ++u) if (lane + 64 * u < V) l += expf(x[q][u] - m);
+            for (int u = 0; u < 8; ++u) if (lane + 64 * u < V && ok8[u]) l += expf(x[q][u] - m);
             l = wave_sum(l);
             if (lane == 0 && j < k) lse[j] = m + logf(l);
         }
@@ -1780,18 +1808,18 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
 #pragma unroll
             for (int u = 0; u < 16; ++u) { const int c = lane + 64 * u; x[u] = lg[c < V ? c : V - 1]; }
 #pragma unroll
-            for (int u = 0; u < 16; ++u) if (lane + 64 * u < V) m = fmaxf(m, x[u]);
+            for (int u = 0; u < 16; ++u) if (lane + 64 * u < V && (!AL || alw_ok(ar, lane + 64 * u))) m = fmaxf(m, x[u]);
             m = wave_max(m);
             float l = 0.f;
 #pragma unroll
-            for (int u = 0; u < 16; ++u) if (lane + 64 * u < V) l += expf(x[u] - m);
+            for (int u = 0; u < 16; ++u) if (lane + 64 * u < V && (!AL || alw_ok(ar, lane + 64 * u))) l += expf(x[u] - m);
             l = wave_sum(l);
             if (lane == 0) lse[j] = m + logf(l);
         } else {
-            for (int c = lane; c < V; c += 64) m = fmaxf(m, lg[c]);
+            for (int c = lane; c < V; c += 64) if (!AL || alw_ok(ar, c)) m = fmaxf(m, lg[c]);
             m = wave_max(m);
             float l = 0.f;
-            for (int c = lane; c < V; c += 64) l += expf(lg[c] - m);
+            for (int c = lane; c < V; c += 64) if (!AL || alw_ok(ar, c)) l += expf(lg[c] - m);
             l = wave_sum(l);
             if (lane == 0) lse[j] = m + logf(l);
         }
@@ -1825,6 +1853,7 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
                 const float f = fin_old[j] ? 1.f : 0.f;
                 sl = (1.f - f) * sl + f * (c == id_end ? 0.f : FMIN);
                 val[u] = lp_old[j] + sl;
+                if constexpr (AL) { if (!alw_ok(ar, c)) val[u] = -INFINITY; }
             }
         }
     }
@@ -2369,18 +2398,25 @@ int lxo_k_init_bwd(const float* dcc, Slabs dxh, const float* c0, const float* re
     LAUNCH(init_bwd_kernel, grid1((long long)B * (2 * U + O)), dcc, dxh, c0, rec0, ldr, dpre, B, U, O);
     DONE;
 }
+// The decode kernels' compile-time flags from the call's nullable arguments: KERNEL<PF, AL> with PF = a forced prefix, AL = allowed-token sets
+#define DEC_VARIANT(KERNEL, grid, block, ...)                                                                         \
+    do {                                                                                                               \
+        if (prefix && allow) hipLaunchKernelGGL((KERNEL<true, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);    \
+        else if (prefix) hipLaunchKernelGGL((KERNEL<true, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);       \
+        else if (allow) hipLaunchKernelGGL((KERNEL<false, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);        \
+        else hipLaunchKernelGGL((KERNEL<false, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);                  \
+    } while (0)
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
-                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out, const DecPrefix* prefix) {
-    if (prefix)
-        LAUNCH(argmax_kernel<true>, cdiv(n, 4), logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, *prefix);
-    else
-    LAUNCH(argmax_kernel<false>, cdiv(n, 4), logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, DecPrefix{});
+                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out, const DecPrefix* prefix, const DecAllow* allow) {
+    const DecPrefix pf = prefix ? *prefix : DecPrefix{};
+    const DecAllow al = allow ? *allow : DecAllow{};
+    DEC_VARIANT(argmax_kernel, cdiv(n, 4), 256, logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, pf, al);
     DONE;
 }
 int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
                     float* scratch, float* logp, int* finished,
                     int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
-                    float* scores_out, const DecPrefix* prefix) {
+                    float* scores_out, const DecPrefix* prefix, const DecAllow* allow) {
     if (k > 16 || k > V) return -2;                            // k > V: at time 0 only V candidates exist -- a k-th selection would have no index
     DivPen dp = {0.f, 0u, (unsigned)div_seed, scratch};
     if (div_gamma > 0.f && div_gamma != 1.f && div_prob > 0.f) {      // the reference returns early for gamma == 1 or prob == 0
@@ -2390,15 +2426,11 @@ int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, i
     static int fast = -1;                                      // LXO_BEAM_FAST=0: the general kernel always (A/B)
     if (fast < 0) { const char* e = getenv("LXO_BEAM_FAST"); fast = (e && e[0] == '0') ? 0 : 1; }
     const DecPrefix pf = prefix ? *prefix : DecPrefix{};
+    const DecAllow al = allow ? *allow : DecAllow{};
     if (fast && dp.log_gamma == 0.f && (long long)k * V <= BS_TH * BS_NPT && k * BS_NW <= 64) {
-        if (prefix)
-            hipLaunchKernelGGL(beam_step_fast_kernel<true>, dim3(nimg), dim3(BS_TH), 0, st, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
-        else
-        hipLaunchKernelGGL(beam_step_fast_kernel<false>, dim3(nimg), dim3(BS_TH), 0, st, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
-    } else if (prefix)
-        LAUNCH(beam_step_kernel<true>, nimg, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
-    else
-    LAUNCH(beam_step_kernel<false>, nimg, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf);
+        DEC_VARIANT(beam_step_fast_kernel, nimg, BS_TH, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf, al);
+    } else
+        DEC_VARIANT(beam_step_kernel, nimg, 256, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf, al);
     DONE;
 }
 int lxo_k_beam_gather(float* rec, int ldr, int XH, float* cs, int U, const int* parents, int k, float* tmp_rec, float* tmp_cs, int n, void* recb, int ldrb, hipStream_t st) {

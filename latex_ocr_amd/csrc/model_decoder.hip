@@ -738,10 +738,11 @@ static Dec dec_of(const Plan& P, void* ws, int k, bool beam) {
     return d;
 }
 // The shapes and arguments every decode call refuses (-5): fewer record columns than steps, a beam the kernels do not take (k > V: fewer
-// first-step candidates than hypotheses), a prefix without its arrays
-static int decode_check(const Plan& P, int k, int steps_needed, const DecPrefix* prefix) {
+// first-step candidates than hypotheses), a prefix without its arrays, allowed-token sets without their words or with rows shorter than V bits
+static int decode_check(const Plan& P, int k, int steps_needed, const DecPrefix* prefix, const DecAllow* allow = nullptr) {
     if (P.s.max_steps < steps_needed || k < 1 || k > 16 || k > P.s.V) return -5;
     if (prefix && (!prefix->ids || !prefix->len || prefix->ld < 1)) return -5;
+    if (allow && (!allow->bits || (allow->ld != 0 && allow->ld < (P.s.V + 31) / 32))) return -5;
     return 0;
 }
 // Before step 0: initial state, cleared flags, and what is computed once per call.  `again` (the greedy chain's fall-back, behind a
@@ -765,11 +766,11 @@ static int decode_select(const Plan& P, const Dec& d, int id_end, int time, cons
     const int ms = P.s.max_steps, U = P.s.U, nv = d.nv, cur = (time + 1) & 1;
     if (o.alpha) HIPRC(hipMemcpyAsync(o.alpha + (size_t)time * nv * P.Rp, d.alpha, (size_t)nv * P.Rp * 4, hipMemcpyDeviceToDevice, st));
     if (!d.beam) {
-        RC(lxo_k_argmax(d.logits, P.Vp, P.s.V, nv, id_end, d.ids_step, o.ids, ms, time, d.finished, unfinished, st, o.scores, o.prefix));
+        RC(lxo_k_argmax(d.logits, P.Vp, P.s.V, nv, id_end, d.ids_step, o.ids, ms, time, d.finished, unfinished, st, o.scores, o.prefix, o.allow));
         return 0;
     }
     RC(lxo_k_beam_step(d.logits, P.Vp, P.s.V, P.s.B, d.k, id_end, time, P.s.div_gamma, P.s.div_prob, P.s.div_seed, d.tmp, d.logp, d.finished,
-                       d.ids_step, d.par_step, o.ids, o.parents, ms, unfinished, st, o.scores, o.prefix));
+                       d.ids_step, d.par_step, o.ids, o.parents, ms, unfinished, st, o.scores, o.prefix, o.allow));
     if (indirect) return 0;
     RC(lxo_k_beam_gather(d.rec + (size_t)cur * nv * P.REC, P.REC, P.XH, d.cs + (size_t)cur * nv * U, U, d.par_step, d.k,
                          d.tmp, d.tmp + (size_t)nv * P.XH, nv, d.recb ? d.recb + (size_t)cur * nv * P.RECB : nullptr, P.RECB, st));
@@ -780,7 +781,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
                            int* steps_out, hipStream_t st) {
     const int B = P.s.B, ms = P.s.max_steps;
     const DecPrefix* prefix = out.prefix;
-    RC(decode_check(P, 1, max_iter + 1, prefix));
+    RC(decode_check(P, 1, max_iter + 1, prefix, out.allow));
     const Dec d = dec_of(P, ws, 1, false);
     RC(decode_setup(P, prm, wp, ws, d, false, st));
     if (fused_steps(P) && P.bf && P.att_exp() && !out.alpha && P.s.step_kernels == 0) {
@@ -797,6 +798,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
         x.part = P.ws<float>(ws, W_APART); x.sync = P.ws<unsigned>(ws, W_XSYNC);
         x.ids_step = d.ids_step; x.ids_out = out.ids; x.logp_out = out.scores; x.finished = d.finished;
         if (prefix) { x.prefix = prefix->ids; x.prefix_len = prefix->len; x.prefix_ld = prefix->ld; x.prefix_lim = prefix->lim; }
+        if (out.allow) { x.allow = out.allow->bits; x.allow_ld = out.allow->ld; }
         x.B = B; x.R = P.R; x.REC = P.REC; x.RECB = P.RECB; x.V = P.s.V; x.id_end = id_end; x.max_steps = ms;
         x.t0 = 0; x.nsteps = 1; x.unfinished = d.flags;
         x.stop = d.ids_step + B;                            // one word behind the fed-back ids (region "dec_ids" holds B x max_steps ints)
@@ -897,7 +899,7 @@ int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* 
 
 int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out,
                          int* steps_out, hipStream_t st) {
-    RC(decode_check(P, P.s.beam, max_iter + 1, out.prefix));
+    RC(decode_check(P, P.s.beam, max_iter + 1, out.prefix, out.allow));
     const Dec d = dec_of(P, ws, P.s.beam, true);
     RC(decode_setup(P, prm, wp, ws, d, false, st));
     // the state of a step's rows is that of their PARENT hypotheses (beam_search_decoder_cell.py:176-178).  With the fused step kernels the next LSTM launch

@@ -63,6 +63,8 @@ struct XDecDec {
     const int* prefix;                // [B][prefix_ld] forced ids (nullable: the instantiation without a prefix runs); row b emits prefix[b][t] at the
     const int* prefix_len;            // steps t < prefix_len[b] (clamped into [0, prefix_lim], prefix_lim = min(prefix_ld, max_iter); an id outside
     int prefix_ld, prefix_lim;        // [0, V) is read as 0).  With logp_out the workgroup owning the forced column hands its logit over as a third word
+    const unsigned* allow;            // allowed-token bit sets (nullable: the instantiation without a constraint runs): bit v & 31 of word v >> 5 of
+    int allow_ld;                     // row b * allow_ld set = row b may emit token v (allow_ld 0: one row for all).  A banned column is masked as a column >= V is
 };
 int lxo_launch_xdec_dec(const XDecDec& p, int U, int O, int C, int E, hipStream_t st);
 

@@ -800,7 +800,9 @@ LXO_DEV int xdec_forced(const XDecDec& p, int bb, int step, int plen) {  // the 
     const int f = p.prefix[(long long)bb * p.prefix_ld + step];
     return (f >= 0 && f < p.V) ? f : 0;
 }
-template <int NB, bool SC, bool PF>
+// AL: allowed-token sets (p.allow).  A thread (row, column) of the logits tile holds one bit, read once per launch; a banned column is masked
+// exactly where a column >= V is (value -3.0e38, exp-sum term 0): no further hand-over word.  AL = false is the chain without a constraint.
+template <int NB, bool SC, bool PF, bool AL>
 __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     // 2 rows per wave and block in flight (the training chain: 4): the decode form carries more loop-invariant addresses (token table, ids,
     // arg-max words) and with 4 rows the allocator spills 55 dwords of them into the serial phases; with 2 it spills 9
@@ -905,6 +907,12 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
         if (tid < NB * 32) plen_m = xdec_plen(p, b0 + (tid >> 5));
         if constexpr (SC) { if (tid < NB * 16) plen_l = xdec_plen(p, b0 + (tid >> 4)); }
     }
+    // the first column this thread's logits column (tid & 15 of the workgroup's 16) may NOT take: V, or 0 for a column its row's set bans
+    int vlim = p.V;
+    if constexpr (AL) {
+        const int vc = v0 + (tid & 15);
+        if (tid < NB * 16 && vc < p.V && !((p.allow[(long long)(b0 + (tid >> 4)) * p.allow_ld + (vc >> 5)] >> (vc & 31)) & 1u)) vlim = 0;
+    }
     for (int t = 0; t <= T; ++t) {
         const int tg = p.t0 + t;                                 // global step index of the step this iteration runs
         const long long sp = (long long)(tg & 1) * B, sn = (long long)((tg + 1) & 1) * B;
@@ -958,7 +966,8 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
 #pragma unroll
                     for (int w = 0; w < XW; ++w) v += redl[w][erow][eu];
                     int vi = v0 + eu;
-                    if (vi >= p.V) v = -3.0e38f;
+                    const bool masked = AL ? vi >= vlim : vi >= p.V;      // a column outside the vocabulary, or a banned one
+                    if (masked) v = -3.0e38f;
                     const float vc = v;
 #pragma unroll
                     for (int o = 8; o > 0; o >>= 1) {
@@ -968,7 +977,7 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                     // (workgroup 0, row 0 carries the chain's STOP bit: what thread 0 probed at the previous boundary)
                     const unsigned stopbit = (rank == 0 && erow == 0 && pr_done == 8 && pr_unf == 0) ? 0x8000u : 0u;
                     if constexpr (SC) {
-                        float sr = v0 + eu < p.V ? expf(vc - v) : 0.f;   // columns >= V: 0
+                        float sr = (AL ? !masked : v0 + eu < p.V) ? expf(vc - v) : 0.f;   // columns >= V (and banned ones): 0
 #pragma unroll
                         for (int o = 8; o > 0; o >>= 1) sr += __shfl_xor(sr, o);
                         if (eu == 0) { const u32x2 ws = {__float_as_uint(sr), (unsigned)t << 16}; *reinterpret_cast<u32x2*>(ll_sm + ((b0 + erow) * 32 + rank) * 2) = ws; }
@@ -1337,18 +1346,20 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     if (tid == 0 && s_dead) *reinterpret_cast<volatile int*>(p.stop) = 1;
 }
 
-template <int NB, bool SC, bool PF>
+template <int NB, bool SC, bool PF, bool AL>
 int launch_dec_sc(const XDecDec& p, hipStream_t st) {
     constexpr int DYN = XW * 12 * 64 * 16;
     static bool attr_done = false;
-    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_dec_kernel<NB, SC, PF>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
-    hipLaunchKernelGGL((xdec_dec_kernel<NB, SC, PF>), dim3(256), dim3(512), DYN, st, p);
+    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_dec_kernel<NB, SC, PF, AL>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
+    hipLaunchKernelGGL((xdec_dec_kernel<NB, SC, PF, AL>), dim3(256), dim3(512), DYN, st, p);
     return (int)hipGetLastError();
 }
-template <int NB, bool PF>
-int launch_dec_pf(const XDecDec& p, hipStream_t st) { return p.logp_out ? launch_dec_sc<NB, true, PF>(p, st) : launch_dec_sc<NB, false, PF>(p, st); }
+template <int NB, bool PF, bool AL>
+int launch_dec_pf(const XDecDec& p, hipStream_t st) { return p.logp_out ? launch_dec_sc<NB, true, PF, AL>(p, st) : launch_dec_sc<NB, false, PF, AL>(p, st); }
+template <int NB, bool AL>
+int launch_dec_al(const XDecDec& p, hipStream_t st) { return p.prefix ? launch_dec_pf<NB, true, AL>(p, st) : launch_dec_pf<NB, false, AL>(p, st); }
 template <int NB>
-int launch_dec_nb(const XDecDec& p, hipStream_t st) { return p.prefix ? launch_dec_pf<NB, true>(p, st) : launch_dec_pf<NB, false>(p, st); }
+int launch_dec_nb(const XDecDec& p, hipStream_t st) { return p.allow ? launch_dec_al<NB, true>(p, st) : launch_dec_al<NB, false>(p, st); }
 
 // ------------------------------------------------------------------------------------------------ backward chain ----
 // Steps T-1 .. 0 of BPTT in one launch, same chains, same identity, same barrier.  Per step:

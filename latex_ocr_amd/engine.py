@@ -682,9 +682,39 @@ class Engine(object):
             return B
         return next(n for n in (8, 16, 32, 64) if B < n)
 
-    def _prefix_args(self, prefix, prefix_lengths, B0, Bp, id_end, max_iter):
+    def _allow_host(self, allowed, B0, id_end, beam_size):
+        """Checks allowed-token sets before any launch: -> bool [1 or B0, V].  allowed: boolean / 0-1 array [V] (one set for the batch) or
+        [B, V]; in every row END is allowed and at least max(1, beam_size) tokens are (a beam's first free step selects k candidates)."""
+        al = allowed.detach().cpu().numpy() if isinstance(allowed, torch.Tensor) else np.asarray(allowed)
+        if al.ndim == 1:
+            al = al[None]
+        if al.ndim != 2 or al.shape[1] != self.n_tok or al.shape[0] not in (1, B0):
+            raise ValueError("allowed must be [V] or [B, V] for B = %d images and V = %d tokens, got shape %s" % (B0, self.n_tok, np.shape(allowed)))
+        al = al.astype(bool)
+        if not 0 <= int(id_end) < self.n_tok:
+            raise ValueError("id_end = %d outside [0, %d)" % (int(id_end), self.n_tok))
+        if not al[:, int(id_end)].all():
+            raise ValueError("allowed rows %s ban id_end = %d" % (np.nonzero(~al[:, int(id_end)])[0].tolist(), int(id_end)))
+        need = max(1, int(beam_size))
+        if (al.sum(1) < need).any():
+            raise ValueError("allowed rows %s allow fewer than max(1, beam_size) = %d tokens" % (np.nonzero(al.sum(1) < need)[0].tolist(), need))
+        return al
+
+    def _allow_args(self, al, B0, Bp):
+        """Stages checked sets as device bit sets (lxo.h: bit v & 31 of word v >> 5): -> (uint32 words [rows, ld] as an int32 tensor, allow_ld);
+        one shared row goes as allow_ld = 0, else row r of a filled-up batch copies row r % B0."""
+        words = (self.n_tok + 31) // 32
+        bits = np.zeros((al.shape[0], words * 32), bool)
+        bits[:, :self.n_tok] = al
+        w = np.packbits(bits, axis=1, bitorder="little").view("<u4").astype(np.uint32).view(np.int32)
+        if al.shape[0] == 1:
+            return self._to_dev(w, torch.int32), 0
+        return self._to_dev(np.ascontiguousarray(w[np.arange(Bp) % B0]), torch.int32), words
+
+    def _prefix_args(self, prefix, prefix_lengths, B0, Bp, id_end, max_iter, al=None):
         """Checks a forced decode prefix before any launch and stages it on the device: -> (prefix int32 [Bp, ld], ld, lengths int32 [Bp]).
-        prefix: ids [B0, T] (None lengths: every row T long); rows >= B0 of a filled-up batch copy row index % B0, as their images do."""
+        prefix: ids [B0, T] (None lengths: every row T long); rows >= B0 of a filled-up batch copy row index % B0, as their images do.
+        al: the call's allowed-token sets (_allow_host) -- a forced token must be allowed in its row."""
         pf = prefix.detach().cpu().numpy() if isinstance(prefix, torch.Tensor) else np.asarray(prefix)
         pf = np.ascontiguousarray(pf, dtype=np.int64)
         if pf.ndim != 2 or pf.shape[0] != B0:
@@ -708,6 +738,11 @@ class Engine(object):
             if (v == int(id_end)).any():
                 rows = sorted(set(np.nonzero(live & (pf == int(id_end)))[0].tolist()))
                 raise ValueError("prefix rows %s contain id_end = %d" % (rows, int(id_end)))
+            if al is not None:
+                r, t = np.nonzero(live)
+                bad = ~al[r % al.shape[0], pf[r, t]]
+                if bad.any():
+                    raise ValueError("prefix rows %s force a token their allowed set bans" % sorted(set(r[bad].tolist())))
         pf = np.where(live, pf, 0)
         if T == 0:
             pf = np.zeros((B0, 1), np.int64)
@@ -730,9 +765,13 @@ class Engine(object):
                     self._stream()), what)
         return steps.value
 
-    def _greedy_entry(self, pfx, ids, logp, alpha):
-        """The entry point for the outputs that are present: _scores refuses a null logp_out, _prefix a null prefix; the plain call is bench.py's."""
+    def _greedy_entry(self, pfx, ids, logp, alpha, alw=None):
+        """The entry point for the outputs that are present: _scores refuses a null logp_out, _prefix a null prefix, _constrained a null set;
+        the plain call is bench.py's."""
         L = self.lib
+        if alw is not None:
+            pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
+            return L.lxo_greedy_decode_constrained, "greedy_decode_constrained", (_p(alw[0]), alw[1]) + pa + (_p(ids), _p(logp), _p(alpha))
         if pfx is not None:
             return L.lxo_greedy_decode_prefix, "greedy_decode_prefix", (_p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(logp), _p(alpha))
         if logp is not None:
@@ -741,7 +780,7 @@ class Engine(object):
             return L.lxo_greedy_decode_attn, "greedy_decode_attn", (_p(ids), _p(alpha))
         return L.lxo_greedy_decode, "greedy_decode", (_p(ids),)
 
-    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False, prefix=None, prefix_lengths=None):
+    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False, prefix=None, prefix_lengths=None, allowed=None):
         """ids int32 [B, T'] as pred_test.ids of the greedy graph (decoder.py:64,70).  With return_attention also the
         attention maps alpha f32 [B, T', H', W'] (what the reference collects through its py_func hook,
         attention_mechanism.py:96-105, for visualize_attention.py).
@@ -753,12 +792,18 @@ class Engine(object):
         prefix / prefix_lengths: decode from a given prefix (lxo_greedy_decode_prefix): ids [B, T_prefix] and lengths [B] (None: T_prefix
         each); row b emits prefix[b, :P_b] first -- its logp there is the model's log-prob of the forced tokens -- and decodes on from there.
         A ValueError before any launch for a shape mismatch, an id outside [0, V), id_end inside a prefix, or a length outside
-        [0, min(T_prefix, max_iter)]."""
+        [0, min(T_prefix, max_iter)].
+        allowed: a token constraint (lxo_greedy_decode_constrained): a boolean / 0-1 array [V] (one set for the batch) or [B, V]; a token
+        outside its image's set is never emitted -- the arg-max runs over the allowed columns and logp is renormalised over them (logit -
+        logsumexp of the allowed logits).  Combines with the other arguments.  A ValueError before any launch for a wrong shape, END banned
+        in a row, no token allowed in a row, or a forced prefix token banned in its row."""
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
         Bp = B0 if return_attention else self._decode_chain_batch(B0)
-        pfx = self._prefix_args(prefix, prefix_lengths, B0, Bp, id_end, max_iter) if prefix is not None else None
+        al = self._allow_host(allowed, B0, id_end, 1) if allowed is not None else None
+        pfx = self._prefix_args(prefix, prefix_lengths, B0, Bp, id_end, max_iter, al) if prefix is not None else None
+        alw = self._allow_args(al, B0, Bp) if al is not None else None
         if Bp != B0:
             img = self._to_dev(img, torch.uint8)
             img = img[torch.arange(Bp, device=img.device) % B0]
@@ -766,7 +811,7 @@ class Engine(object):
         ids = torch.zeros(B, self.max_steps, dtype=torch.int32, device=self.device)
         logp = torch.zeros(B, self.max_steps, dtype=torch.float32, device=self.device) if return_scores else None
         alpha, R, Hp, Wp = self._alpha_buf(B, img) if return_attention else (None, 0, 0, 0)
-        n = self._run_decode(self._greedy_entry(pfx, ids, logp, alpha), id_end, max_iter)
+        n = self._run_decode(self._greedy_entry(pfx, ids, logp, alpha, alw), id_end, max_iter)
         out = [ids[:B0, :n]]
         if return_attention:
             out.append(alpha[:n, :B0, :R].permute(1, 0, 2).reshape(B0, n, Hp, Wp))
@@ -853,9 +898,12 @@ class Engine(object):
         Vp = (self.n_tok + 31) // 32 * 32
         return self.region("dec_logits", "f32", (self._dec_rows(), Vp))[:, :self.n_tok].cpu().numpy()
 
-    def _beam_entry(self, pfx, ids, par, sc, alpha):
+    def _beam_entry(self, pfx, ids, par, sc, alpha, alw=None):
         """The entry point for the outputs that are present (as _greedy_entry; _attn refuses a null alpha_out too)."""
         L = self.lib
+        if alw is not None:
+            pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
+            return L.lxo_beam_decode_constrained, "beam_decode_constrained", (_p(alw[0]), alw[1]) + pa + (_p(ids), _p(par), _p(sc), _p(alpha))
         if pfx is not None:
             return L.lxo_beam_decode_prefix, "beam_decode_prefix", (_p(pfx[0]), pfx[1], _p(pfx[2]), _p(ids), _p(par), _p(sc), _p(alpha))
         if sc is not None:
@@ -865,7 +913,7 @@ class Engine(object):
         return L.lxo_beam_decode, "beam_decode", (_p(ids), _p(par))
 
     def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False,
-                    return_scores=False, prefix=None, prefix_lengths=None):
+                    return_scores=False, prefix=None, prefix_lengths=None, allowed=None):
         """ids int32 [B, T', k] as pred_test.ids of the beam graph before the transpose at img2seq.py:241.
         div_gamma / div_prob: add_div_penalty of beam_search_decoder_cell.py:258-287 (off at 1 / 0, the shipped values).
         return_attention: -> (ids, parents, alpha f32 [B, T', k, H', W']): alpha[b, t, j] = the map decoder row j of image b attended with at
@@ -873,19 +921,23 @@ class Engine(object):
         return_scores: -> (ids, parents, scores) or (ids, parents, alpha, scores), scores f32 [B, T', k] = the running log-prob of slot k after
         step t (the beam state's log_probs; lxo_beam_decode_scores): the log-prob of the sequence that back-traces from (t, k).
         prefix / prefix_lengths: per image, as in greedy_decode (lxo_beam_decode_prefix): every slot takes the forced tokens, the beam search
-        starts after them."""
+        starts after them.
+        allowed: per image, as in greedy_decode (lxo_beam_decode_constrained): log_softmax over the allowed columns, a banned candidate is
+        never selected, the diversity penalty ranks among the allowed columns.  Every row must allow at least beam_size tokens."""
         self._check_beam(beam_size)
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
-        pfx = self._prefix_args(prefix, prefix_lengths, B0, B0, id_end, max_iter) if prefix is not None else None
+        al = self._allow_host(allowed, B0, id_end, beam_size) if allowed is not None else None
+        pfx = self._prefix_args(prefix, prefix_lengths, B0, B0, id_end, max_iter, al) if prefix is not None else None
+        alw = self._allow_args(al, B0, B0) if al is not None else None
         B = self._encode_only(img, int(beam_size))
         self._set_diversity(div_gamma, div_prob, div_seed)
         ids = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         par = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device) if return_scores else None
         alpha, R, Hp, Wp = self._alpha_buf(B * beam_size, img) if return_attention else (None, 0, 0, 0)
-        n = self._run_decode(self._beam_entry(pfx, ids, par, sc, alpha), id_end, max_iter)
+        n = self._run_decode(self._beam_entry(pfx, ids, par, sc, alpha, alw), id_end, max_iter)
         out = [ids[:, :n]]
         if return_parents or return_attention or return_scores:
             out.append(par[:, :n])

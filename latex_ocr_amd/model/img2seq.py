@@ -137,19 +137,54 @@ class Img2SeqModel(BaseModel):
         self._div_calls = getattr(self, "_div_calls", 0) + 1
         return dict(div_gamma=getattr(cfg, "div_gamma", 1), div_prob=getattr(cfg, "div_prob", 0), div_seed=self._div_calls)
 
-    def _decode(self, img):
+    def _token_sets(self, n_images, banned, allowed):
+        """The allowed= argument of the Engine decodes from banned / allowed token lists: token strings or ids, one list for all images or
+        one list per image.  `banned` is the complement form; given both, a token must be allowed and not banned.  Unknown token strings
+        raise (a whitelist that silently drops a symbol is worse than none).  -> bool [V] or [B, V], None for no constraint."""
+        if banned is None and allowed is None:
+            return None
+        V = self._vocab.n_tok
+
+        def ids_of(toks):
+            out = []
+            for t in toks:
+                if isinstance(t, str):
+                    if t not in self._vocab.tok_to_id:
+                        raise ValueError("unknown token %r" % t)
+                    out.append(self._vocab.tok_to_id[t])
+                else:
+                    if not 0 <= int(t) < V:
+                        raise ValueError("token id %d outside [0, %d)" % (int(t), V))
+                    out.append(int(t))
+            return out
+
+        def mask(toks, fill):
+            toks = list(toks)
+            per_image = len(toks) > 0 and all(isinstance(t, (list, tuple, np.ndarray)) for t in toks)
+            if per_image and len(toks) != n_images:
+                raise ValueError("%d per-image token lists for %d images" % (len(toks), n_images))
+            m = np.full((n_images if per_image else 1, V), not fill, bool)
+            for b, row in enumerate(toks if per_image else [toks]):
+                m[b, ids_of(row)] = fill
+            return m
+        m = mask(allowed, True) if allowed is not None else np.ones((1, V), bool)
+        if banned is not None:
+            m = m & mask(banned, False)
+        return m[0] if m.shape[0] == 1 else m
+
+    def _decode(self, img, allowed=None):
         """pred_test.ids of the decode graph (decoder.py:60-70), shaped [B, k, T'] as after
         img2seq.py:238-241."""
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1          # decoder.py:70
         if getattr(cfg, "decoding", "greedy") == "beam_search":
             ids, par = self.engine.beam_decode(img, self._vocab.id_end, cfg.beam_size, max_iter=max_iter, return_parents=True,
-                                               **self._beam_kwargs())
+                                               allowed=allowed, **self._beam_kwargs())
             if getattr(cfg, "beam_backtrace", False):      # extension: follow parents (the reference never does, quirk C-1)
                 from .utils.text import beam_backtrace
                 ids = beam_backtrace(ids, par)
             return np.transpose(ids, [0, 2, 1])
-        ids = self.engine.greedy_decode(img, self._vocab.id_end, max_iter=max_iter)
+        ids = self.engine.greedy_decode(img, self._vocab.id_end, max_iter=max_iter, allowed=allowed)
         return np.expand_dims(ids, axis=1)
 
     def write_prediction(self, config, test_set):
@@ -171,18 +206,22 @@ class Img2SeqModel(BaseModel):
         perp = -np.exp(ce_words / float(n_words))
         return files, perp
 
-    def predict_batch(self, images, return_scores=False):
+    def predict_batch(self, images, return_scores=False, banned=None, allowed=None):
         """Reference: model/img2seq.py:256-276.
         return_scores: -> (hyps, scores), scores[i][b] = (sequence log-prob, [log-prob of each token up to and including the first END]) of
         hypothesis hyps[i][b]; the sequence log-prob is the sum of the token log-probs.  Greedy: the hypotheses are the default call's.
         Beam search: the hypotheses are the back-traced ones (utils/text.beam_backtrace) whatever config.beam_backtrace says -- the final
         running log-prob of slot i belongs to the token path that ends in slot i, not to the per-step columns of the reference's read-out
         (quirk C-1) -- and a token's log-prob is the difference of the running scores along that path (with the diversity penalty on, the
-        penalised scores)."""
+        penalised scores).
+        banned / allowed: a token constraint (Engine greedy_decode / beam_decode with allowed=): token strings or ids, one list for all
+        images or one list per image; a token outside an image's set is never emitted and the scores are renormalised over the set.
+        END must stay allowed.  E.g. banned=["_UNK", "_PAD"].  Nothing is banned by default."""
+        sets = self._token_sets(len(images), banned, allowed)
         if return_scores:
-            return self._predict_scored(images)
+            return self._predict_scored(images, allowed=sets)
         fd = self._get_feed_dict(images, dropout=1)
-        ids_eval = self._decode(fd["img"])
+        ids_eval = self._decode(fd["img"], sets)
         hyps = [[] for _ in range(ids_eval.shape[1])]
         for preds in ids_eval:
             for i, pred in enumerate(preds):
@@ -209,12 +248,13 @@ class Img2SeqModel(BaseModel):
             out.append((float(seq[b]), [float(x) for x in logp[b, :n]], int(diff[0]) if diff.size else -1))
         return out
 
-    def complete_batch(self, images, prefixes, return_scores=False):
+    def complete_batch(self, images, prefixes, return_scores=False, banned=None, allowed=None):
         """Decode each image from a given prefix (Engine greedy_decode / beam_decode with prefix=): the prefixes are token-id lists or
         space-separated token strings (Vocab.form_prepro, as score_batch takes them, but no END is appended), one per image; "" or []
         decodes from the start.  config.decoding chooses greedy or beam search; beam hypotheses are the back-traced ones, as
         predict_batch(return_scores=True) returns them.  -> hyps (hyps[i][b]: hypothesis i of image b, its prefix included), or
-        (hyps, scores) with return_scores, scores as in predict_batch (the forced tokens' log-probs included)."""
+        (hyps, scores) with return_scores, scores as in predict_batch (the forced tokens' log-probs included).
+        banned / allowed: as in predict_batch ("and not that token again"); a prefix token must be allowed for its image."""
         if len(images) != len(prefixes):
             raise ValueError("complete_batch: %d images but %d prefixes" % (len(images), len(prefixes)))
         prepro = self._vocab.form_prepro
@@ -223,10 +263,10 @@ class Img2SeqModel(BaseModel):
         pf = np.zeros((len(forms), max(1, int(ln.max()) if ln.size else 1)), np.int32)
         for b, f in enumerate(forms):
             pf[b, :len(f)] = f
-        hyps, scores = self._predict_scored(images, pf, ln)
+        hyps, scores = self._predict_scored(images, pf, ln, self._token_sets(len(images), banned, allowed))
         return (hyps, scores) if return_scores else hyps
 
-    def _predict_scored(self, images, prefix=None, prefix_lengths=None):
+    def _predict_scored(self, images, prefix=None, prefix_lengths=None, allowed=None):
         fd = self._get_feed_dict(images, dropout=1)
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1
@@ -234,12 +274,12 @@ class Img2SeqModel(BaseModel):
         if getattr(cfg, "decoding", "greedy") == "beam_search":
             from .utils.text import beam_backtrace
             ids, par, sc = self.engine.beam_decode(fd["img"], id_end, cfg.beam_size, max_iter=max_iter, return_scores=True,
-                                                   prefix=prefix, prefix_lengths=prefix_lengths, **self._beam_kwargs())
+                                                   prefix=prefix, prefix_lengths=prefix_lengths, allowed=allowed, **self._beam_kwargs())
             ids, run = beam_backtrace(ids, par), beam_backtrace(sc, par)          # token paths and their running log-probs
             tok = np.diff(run, axis=1, prepend=0.0)
         else:
             ids, tok = self.engine.greedy_decode(fd["img"], id_end, max_iter=max_iter, return_scores=True, prefix=prefix,
-                                                 prefix_lengths=prefix_lengths)
+                                                 prefix_lengths=prefix_lengths, allowed=allowed)
             ids, tok = ids[:, :, None], tok[:, :, None]
         k = ids.shape[2]
         hyps, scores = [[] for _ in range(k)], [[] for _ in range(k)]

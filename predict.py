@@ -5,7 +5,9 @@ pdf/LaTeX->PNG cropping helpers are out of scope).  --scores adds the hypothesis
 probability exp(log-prob / tokens) (Img2SeqModel.predict_batch(..., return_scores=True)).  --formula "<tokens>" (one image) scores
 that transcription instead of decoding: its log-prob (END included), geometric-mean token probability and the first position where
 the model's top-1 token differs from it (Img2SeqModel.score_batch).  --prefix "<tokens>" (one image) decodes from that prefix: the
-hypothesis keeps it and the model writes the rest (Img2SeqModel.complete_batch); it combines with --scores."""
+hypothesis keeps it and the model writes the rest (Img2SeqModel.complete_batch); it combines with --scores.  --ban "<tokens>" keeps those
+tokens out of every hypothesis (e.g. --ban "_UNK _PAD"), --allow-file FILE (one token per line; END is added) lets only those in; both
+combine with --scores and --prefix (predict_batch / complete_batch with banned= / allowed=)."""
 import argparse
 
 import numpy as np
@@ -22,6 +24,8 @@ def main(argv=None):
     ap.add_argument("--scores", action="store_true", help="print the log-prob and the geometric-mean token probability of each hypothesis")
     ap.add_argument("--formula", default=None, help="score this space-separated token sequence against the (single) image")
     ap.add_argument("--prefix", default=None, help="decode the (single) image from this space-separated token prefix")
+    ap.add_argument("--ban", default=None, help="space-separated tokens that must not be emitted")
+    ap.add_argument("--allow-file", default=None, help="file with one token per line: only these (and END) may be emitted")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     if a.formula is not None and len(a.images) != 1:
@@ -33,6 +37,14 @@ def main(argv=None):
     vocab = Vocab(config_vocab)
     model = Img2SeqModel(config_model, d, vocab)
     model.build_pred()
+    sets = {}
+    if a.ban is not None:
+        sets["banned"] = a.ban.split()
+    if a.allow_file is not None:
+        with open(a.allow_file) as f:
+            sets["allowed"] = [t for t in (line.strip() for line in f) if t] + [vocab.id_end]
+    if sets and a.formula is not None:
+        ap.error("--ban / --allow-file constrain a decode and do not combine with --formula")
     from PIL import Image
     out = []
     for path in a.images:
@@ -43,7 +55,7 @@ def main(argv=None):
             out.append((lp, toks, first))
             continue
         if a.prefix is not None:
-            hyps, scores = model.complete_batch([greyscale(img)], [a.prefix], return_scores=True)
+            hyps, scores = model.complete_batch([greyscale(img)], [a.prefix], return_scores=True, **sets)
             lp, toks = scores[0][0]
             if a.scores:
                 print(path, "=>", hyps[0][0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
@@ -52,13 +64,13 @@ def main(argv=None):
             out.append(([h[0] for h in hyps], [s[0] for s in scores]) if a.scores else [h[0] for h in hyps])
             continue
         if a.scores:
-            hyps, scores = model.predict_batch([greyscale(img)], return_scores=True)
+            hyps, scores = model.predict_batch([greyscale(img)], return_scores=True, **sets)
             hyps = [h[0] for h in hyps]
             lp, toks = scores[0][0]
             print(path, "=>", hyps[0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
             out.append((hyps, [s[0] for s in scores]))
             continue
-        hyps = model.predict(greyscale(img))
+        hyps = [h[0] for h in model.predict_batch([greyscale(img)], **sets)] if sets else model.predict(greyscale(img))
         print(path, "=>", hyps[0])
         out.append(hyps)
     return out

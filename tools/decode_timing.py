@@ -1,7 +1,8 @@
 """Greedy / beam decode latency on synthetic 128x512 crops (random-init weights never emit END, so every run decodes
 the full max_iter + 1 steps).  --scores: each decode once without and once with return_scores (token log-probs / hypothesis
 scores), interleaved over --reps rounds, for the A/B of the scored calls.  --prefix N: the same A/B of the calls without a prefix and
-with an N-token forced prefix on every row (prefix=, the decode still runs max_iter + 1 steps)."""
+with an N-token forced prefix on every row (prefix=, the decode still runs max_iter + 1 steps).  --ban N: the A/B of the calls without a
+constraint and with N random tokens banned in every row (allowed= as [B, V]: a set per image)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,6 +16,12 @@ scores_ab = "--scores" in sys.argv
 reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
 n_prefix = int(sys.argv[sys.argv.index("--prefix") + 1]) if "--prefix" in sys.argv else None
 prefix = torch.randint(0, V - 1, (B, n_prefix or 1), generator=torch.Generator().manual_seed(3)).to(torch.int32) if n_prefix else None
+n_ban = int(sys.argv[sys.argv.index("--ban") + 1]) if "--ban" in sys.argv else None
+allowed = None
+if n_ban:
+    allowed = torch.ones(B, V, dtype=torch.bool)
+    for b in range(B):
+        allowed[b, torch.randperm(V - 1, generator=torch.Generator().manual_seed(7 + b))[:n_ban]] = False      # END (V - 1) stays allowed
 
 
 def timed(fn, n=3):
@@ -35,7 +42,10 @@ for beam in (1, 5):
     if n_prefix is not None:
         arms = {False: arms[False], True: (lambda: eng.greedy_decode(img, V - 1, max_iter=100, prefix=prefix)) if beam == 1 else
                 (lambda: eng.beam_decode(img, V - 1, beam, max_iter=100, prefix=prefix))}
-    if not scores_ab and n_prefix is None:
+    if n_ban is not None:
+        arms = {False: arms[False], True: (lambda: eng.greedy_decode(img, V - 1, max_iter=100, allowed=allowed)) if beam == 1 else
+                (lambda: eng.beam_decode(img, V - 1, beam, max_iter=100, allowed=allowed))}
+    if not scores_ab and n_prefix is None and n_ban is None:
         arms[False]()
         dt, steps = timed(arms[False])
         print("beam %d: %d steps, %.1f ms per batch of %d (%.1f us per step, %.0f img/s)" % (beam, steps, dt * 1e3, B, dt * 1e6 / steps, B / dt))
@@ -48,5 +58,6 @@ for beam in (1, 5):
             per[sc].append(dt * 1e6 / steps)
     a, b = sorted(per[False]), sorted(per[True])
     print("beam %d: us per step (median of %d, min..max)  %s %.2f (%.2f..%.2f)  %s %.2f (%.2f..%.2f)  ratio %.4f"
-          % (beam, reps, "no prefix" if n_prefix else "ids only", a[reps // 2], a[0], a[-1],
-             ("prefix %d" % n_prefix) if n_prefix else "with scores", b[reps // 2], b[0], b[-1], b[reps // 2] / a[reps // 2]))
+          % (beam, reps, "no constraint" if n_ban else "no prefix" if n_prefix else "ids only", a[reps // 2], a[0], a[-1],
+             ("%d banned" % n_ban) if n_ban else ("prefix %d" % n_prefix) if n_prefix else "with scores", b[reps // 2], b[0], b[-1],
+             b[reps // 2] / a[reps // 2]))
