@@ -168,11 +168,10 @@ LXO_DEV bool ll_wait(u32x4 (&w)[N], rsrc_t r, const unsigned (&off)[N], unsigned
         for (int j = 0; j < N; ++j) { w[j] = l2_load16(r, off[j]); }
 #pragma unroll
         for (int j = 0; j < N; ++j) ok = ok && w[j][1] == tag && w[j][3] == tag;
-        if (__ballot(!ok) == 0ull) return true;
-        if (*s_dead || wall_clock64() - t0 > 20000000ull) {
-            if ((threadIdx.x & 63) == 0) { *s_dead = 1; *reinterpret_cast<volatile unsigned*>(err) = 3u; }
-            return false;
-        }
+        const bool all = __ballot(!ok) == 0ull;
+        const bool gave_up = !all && (*s_dead || wall_clock64() - t0 > 20000000ull);
+        if (gave_up && (threadIdx.x & 63) == 0) { *s_dead = 1; *reinterpret_cast<volatile unsigned*>(err) = 3u; }
+        if (all || gave_up) return all;                          // ONE way out of the loop: with two, every caller gets an if / else over them with a copy of w in each arm
     }
 }
 
@@ -198,11 +197,10 @@ LXO_DEV bool ll_wait8(u32x4 (&w)[N], rsrc_t r, const unsigned (&off)[N], unsigne
         for (int j = 0; j < N; ++j) { w[j] = l2_load16(r, off[j]); }
 #pragma unroll
         for (int j = 0; j < N; ++j) ok = ok && (w[j][1] >> 24) == tag8 && (w[j][3] >> 24) == tag8;
-        if (__ballot(!ok) == 0ull) return true;
-        if (*s_dead || wall_clock64() - t0 > 20000000ull) {
-            if ((threadIdx.x & 63) == 0) { *s_dead = 1; *reinterpret_cast<volatile unsigned*>(err) = 3u; }
-            return false;
-        }
+        const bool all = __ballot(!ok) == 0ull;
+        const bool gave_up = !all && (*s_dead || wall_clock64() - t0 > 20000000ull);
+        if (gave_up && (threadIdx.x & 63) == 0) { *s_dead = 1; *reinterpret_cast<volatile unsigned*>(err) = 3u; }
+        if (all || gave_up) return all;                          // ONE way out of the loop: with two, every caller gets an if / else over them with a copy of w in each arm
     }
 }
 
@@ -271,6 +269,427 @@ LXO_DEV void att_load(u32x4 (&xi)[ATT_U], u32x2 (&xa)[ATT_U], rsrc_t rim, rsrc_t
     }
 }
 
+// ------------------------------------------------------------------------------------------------ what the chains share ----
+// Identity of a chain workgroup: the XCD it runs on (read from the hardware), its rank there (a ticket on the XCD's counter), the first sample
+// of its chain and what a thread needs to find its place in an MFMA fragment.  All three kernels take theirs from here.
+struct XChain {
+    int tid, lane, wave;                                         // wave: known uniform (row arithmetic on the scalar ALU)
+    int r16, g4;                                                 // the lane in an MFMA fragment: (column, k group)
+    unsigned xcc;
+    int rank, b0;                                                // first sample of this chain
+    int arow;                                                    // A-fragment row of this lane (rows >= NB repeat the last one; their products are dropped)
+    unsigned* xsync; unsigned* err; int* s_dead;                 // the XCD's flag line, the launch's error word, the workgroup's "chain is broken" word
+};
+LXO_DEV XChain xchain_ticket(unsigned* sync, int nb, int* s_rank, int* s_dead) {
+    XChain c;
+    c.tid = threadIdx.x; c.lane = c.tid & 63; c.wave = __builtin_amdgcn_readfirstlane(c.tid >> 6);
+    c.r16 = c.lane & 15; c.g4 = c.lane >> 4;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(c.xcc));
+    c.xcc &= 7u;
+    c.xsync = sync + c.xcc * 64; c.err = sync + 8 * 64; c.s_dead = s_dead;
+    c.rank = 0; c.b0 = (int)c.xcc * nb; c.arow = min(c.r16, nb - 1);
+    if (c.tid == 0) { *s_dead = 0; *s_rank = (int)atomicAdd(c.xsync + 32, 1u); }
+    return c;
+}
+// behind the workgroup barrier that follows the ticket.  false: more than 32 workgroups on this XCD, not a chain (error word 2)
+LXO_DEV bool xchain_rank(XChain& c, const int* s_rank) {
+    c.rank = *s_rank;
+    if (c.rank < 32) return true;
+    if (c.tid == 0) *reinterpret_cast<volatile unsigned*>(c.err) = 2u;
+    return false;
+}
+
+// Attention role of a workgroup: (sample of the chain, chunk) = (rank / NQ, rank % NQ) and the two streams of that chunk.
+// The chunk is walked in blocks of XW * ATT_U rows, two blocks per loop trip (buffers A and B): block i+1 is in flight while block i is
+// computed, and the FIRST block of the next step is requested before this step's last block is computed -- it lands during P4 / P1 / P2,
+// so P3 starts on data that is already in registers.  An odd block count ends on an A half (no padded block: its clamped loads cost 1 / 8 of
+// the benchmark chunk's requests).  Blocks are walked in alternating directions from step to step (what this step read last is what the next
+// one reads first: L2 reuse).
+template <int ATT_U>
+struct XRole {
+    int as, aq, ab;                                              // sample of the chain, chunk, sample of the batch
+    int ar0, an;                                                 // the chunk's first row and row count (may be <= 0 for a trailing chunk)
+    int nblk, anq;                                               // blocks; rows the streams' descriptors cover (an empty trailing chunk still issues (masked) loads: row 0 of the first sample)
+    rsrc_t imq, aiq;                                             // the chunk's img rows and att_img (or e^{2 att_img}) rows
+    int wave;
+    // first row of this wave in block i of the walk (rv: the walk runs backwards)
+    LXO_DEV int XBASE(int i, int rv) const { return wave + XW * ATT_U * (rv ? nblk - 1 - i : i); }
+};
+template <int NB, int ATT_U>
+LXO_DEV XRole<ATT_U> xdec_role(const XChain& c, int R, const bf16_t* img, const bf16_t* ai) {
+    constexpr int NQ = 32 / NB;                                  // attention chunks per sample = workgroups per sample
+    XRole<ATT_U> ro;
+    ro.as = c.rank / NQ; ro.aq = c.rank - ro.as * NQ;
+    ro.ab = c.b0 + ro.as;
+    const int rows_per = (R + NQ - 1) / NQ;
+    ro.ar0 = ro.aq * rows_per;
+    ro.an = min(R, ro.ar0 + rows_per) - ro.ar0;
+    ro.nblk = ro.an > 0 ? (ro.an + XW * ATT_U - 1) / (XW * ATT_U) : 0;
+    ro.anq = ro.an > 0 ? ro.an : 1;
+    ro.imq = make_rsrc(ro.an > 0 ? img + ((long long)ro.ab * R + ro.ar0) * XC : img, (unsigned)ro.anq * XC * 2u);
+    ro.aiq = make_rsrc(ro.an > 0 ? ai + ((long long)ro.ab * R + ro.ar0) * XE : ai, (unsigned)ro.anq * XE * 2u);
+    ro.wave = c.wave;
+    return ro;
+}
+
+// P1's contraction index [o (512) | h (512)]: k-steps 0, 1 of a wave lie in o (polled hand-over words), 2, 3 in h (plain loads)
+LXO_DEV constexpr int P1K(int wave, int ks) { return ks < 2 ? wave * 64 + ks * 32 : XO + wave * 64 + (ks - 2) * 32; }
+
+// ---- resident weights of the forward and decode chains: this wave's eighth of every contraction, as MFMA B fragments (lane = (column r16, k group g4)) ----
+// K_LSTM_RT: gate i in registers, gates j, f, o in LDS (96 KB, fragment-shaped: [wave][gate][k-step][lane] x 16 B, read back by the
+// lane that wrote it) -- 88 resident VGPRs left no room for the attention stream's two row blocks in flight
+template <bool EXPD, class P>
+LXO_DEV void xdec_resident(const P& p, const XChain& c, u32x4 (&wrt0)[4], u32x4* wl, u32x4 (*wahs)[2][64], u32x4 (&wow)[4], float (&bt)[4]) {
+    const int u0 = c.rank * 16, e0 = c.rank * 8, o0 = c.rank * 16;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const u32x4 w = *reinterpret_cast<const u32x4*>(p.Wrt + (long long)(q * XU + u0 + c.r16) * p.ldrt + P1K(c.wave, ks) + c.g4 * 8);
+            if (q == 0) wrt0[ks] = w; else wl[((q - 1) * 4 + ks) * 64] = w;      // wl + (gate - 1) * 4 * 64 + ks * 64
+        }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        const u32x4 w = *reinterpret_cast<const u32x4*>(p.Wah + (long long)(e0 + (c.r16 & 7)) * p.ldah + c.wave * 64 + ks * 32 + c.g4 * 8);
+        const u32x4 z = {0u, 0u, 0u, 0u};
+        wahs[c.wave][ks][c.lane] = c.r16 < 8 ? w : z;            // an 8-column slice in a 16-column tile
+    }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+        wow[ks] = *reinterpret_cast<const u32x4*>(p.Wow + (long long)(o0 + c.r16) * p.ldow + c.wave * 128 + ks * 32 + c.g4 * 8);
+    const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.beta + c.lane * 4);
+    const float f = EXPD ? -2.f : 1.f;
+    bt[0] = f * b4[0]; bt[1] = f * b4[1]; bt[2] = f * b4[2]; bt[3] = f * b4[3];
+}
+
+// P1's A operand: this lane's row of [o | h]_{t-1} (record slot sp).  h comes from plain loads; o, when `polled`, from the hand-over words the
+// o projection of the previous step left (no barrier behind P4), tagged `tag`
+template <class P>
+LXO_DEV void xdec_p1_fetch(u32x4 (&a)[4], const P& p, const XChain& c, long long sp, bool polled, rsrc_t rll_o, unsigned tag) {
+    const rsrc_t rp = make_rsrc(p.recb + sp * p.RECB, (unsigned)p.B * p.RECB * 2u);
+#pragma unroll
+    for (int ks = 2; ks < 4; ++ks) a[ks] = l2_load16(rp, (unsigned)(((c.b0 + c.arow) * p.RECB + P1K(c.wave, ks) + c.g4 * 8) * 2));
+    if (polled) {
+        u32x4 w[4];
+        unsigned off[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) off[j] = (unsigned)(((c.b0 + c.arow) * 256 + ((P1K(c.wave, j >> 1) + c.g4 * 8) >> 1)) * 8 + (j & 1) * 16);
+        ll_wait<4>(w, rll_o, off, tag, c.err, c.s_dead);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) a[ks] = u32x4{w[2 * ks][0], w[2 * ks][2], w[2 * ks + 1][0], w[2 * ks + 1][2]};
+    } else {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) a[ks] = l2_load16(rp, (unsigned)(((c.b0 + c.arow) * p.RECB + P1K(c.wave, ks) + c.g4 * 8) * 2));
+    }
+}
+
+// TF-1.12 LSTMCell, gate order i, j, f, o, forget_bias 1.0 (attention_cell.py:71), of one element (row erow, unit eu) of the workgroup's tile.
+// g: in, the x-part of the pre-activation; out, the activated gates.  The recurrent part is the sum of the waves' partial tiles.
+LXO_DEV void xdec_lstm(float (&g)[4], const float (*red)[8][64], int erow, int eu, float c_prev, float& c, float& h) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float z = g[q];
+#pragma unroll
+        for (int w = 0; w < XW; ++w) z += red[w][erow][q * 16 + eu];
+        g[q] = (q == 1) ? tanh_x(z) : sigm_x(q == 2 ? z + 1.0f : z);
+    }
+    c = fmaf(g[2], c_prev, g[0] * g[1]);                         // written out: left to the compiler, WHICH product is fused changes with the code around it
+    h = g[3] * tanh_x(c);
+}
+
+// P2: att_h = h~ W, this workgroup's 8 columns of all NB rows, handed to the attention workgroups as polled words (no barrier).
+// POLL: h~ comes from the hand-over words P1 left, else from the record behind an XCD barrier.  ATTH: att_h is also kept (p.atth, step slot sp).
+template <int NB, bool POLL, bool ATTH, class P>
+LXO_DEV void xdec_p2(const P& p, const XChain& c, long long sp, long long sn, int t, rsrc_t rll_ht, unsigned* ll_ah, float (*red)[8][64], const u32x4 (*wahs)[2][64]) {
+    u32x4 a[2];
+    if constexpr (POLL) {
+        u32x4 w[4];
+        unsigned off[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) off[j] = (unsigned)(((c.b0 + c.arow) * 256 + ((c.wave * 64 + (j >> 1) * 32 + c.g4 * 8) >> 1)) * 8 + (j & 1) * 16);
+        ll_wait<4>(w, rll_ht, off, (unsigned)(t + 1), c.err, c.s_dead);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) a[ks] = u32x4{w[2 * ks][0], w[2 * ks][2], w[2 * ks + 1][0], w[2 * ks + 1][2]};
+    } else {
+        const rsrc_t rn = make_rsrc(p.recb + sn * p.RECB, (unsigned)p.B * p.RECB * 2u);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) a[ks] = l2_load16(rn, (unsigned)(((c.b0 + c.arow) * p.RECB + OFF_HT + c.wave * 64 + ks * 32 + c.g4 * 8) * 2));
+    }
+    v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) acc = mfma16(a[ks], wahs[c.wave][ks][c.lane], acc);
+    if (c.g4 * 4 < NB) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[c.wave][c.g4 * 4 + i][c.r16] = acc[i];
+    }
+    __syncthreads();
+    if (c.tid < NB * 8) {
+        const int row = c.tid >> 3, e = c.tid & 7, e0 = c.rank * 8;
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < XW; ++w) v += red[w][row][e];
+        if constexpr (ATTH) p.atth[(sp + c.b0 + row) * XE + e0 + e] = v;
+        const u32x2 wv = {__float_as_uint(v), (unsigned)(t + 1)};
+        *reinterpret_cast<u32x2*>(ll_ah + ((c.b0 + row) * XE + e0 + e) * 2) = wv;      // the attention workgroups poll these words: no barrier
+    }
+}
+
+// P3's att_h of this workgroup's sample, polled from P2's words (behind a barrier the tags already match: one pass).  EXPD: as E_a = e^{2 att_h}
+template <bool EXPD>
+LXO_DEV void xdec_att_h(float (&ah)[4], const XChain& c, int ab, rsrc_t rll_ah, unsigned tag) {
+    u32x4 aw[2];
+    const unsigned off[2] = {(unsigned)((ab * XE + c.lane * 4) * 8), (unsigned)((ab * XE + c.lane * 4) * 8 + 16)};
+    ll_wait<2>(aw, rll_ah, off, tag, c.err, c.s_dead);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        ah[j] = __uint_as_float(aw[j >> 1][(j & 1) * 2]);
+        if constexpr (EXPD) ah[j] = __builtin_amdgcn_exp2f(fminf(fmaxf(ah[j] * 2.8853900817779268f, -60.f), 60.f));      // E_a
+    }
+}
+
+// P3's walk over the chunk, direction rev.  Entering: block 0 in A and block 1 in B (requested at the end of the previous step's P3).  Each
+// buffer is refilled right after its block is computed -- with the block two ahead, or, at the end of the chunk, with the NEXT STEP's first two
+// blocks (its direction is the other one): they land during P4 / P1 / P2
+template <int ATT_U, bool EXPD>
+LXO_DEV void xdec_walk(u32x4 (&xiA)[ATT_U], u32x2 (&xaA)[ATT_U], u32x4 (&xiB)[ATT_U], u32x2 (&xaB)[ATT_U], const XRole<ATT_U>& ro, int rev,
+                       const float (&ah)[4], const float (&bt)[4], float& m, float& l, float (&acc)[8], float* sc, int lane) {
+    const int nblk = ro.nblk;
+    for (int it = 0; it < nblk; it += 2) {
+        att_block<ATT_U, EXPD>(xiA, xaA, ro.XBASE(it, rev), ro.an, ah, bt, m, l, acc, sc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        att_load<ATT_U>(xiA, xaA, ro.imq, ro.aiq, (it + 2 < nblk) ? ro.XBASE(it + 2, rev) : ro.XBASE(0, rev ^ 1), ro.anq, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (it + 1 < nblk) {                                     // (an odd block count ends on an A half: B already holds the next step's block 1)
+            att_block<ATT_U, EXPD>(xiB, xaB, ro.XBASE(it + 1, rev), ro.an, ah, bt, m, l, acc, sc, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            att_load<ATT_U>(xiB, xaB, ro.imq, ro.aiq, (it + 3 < nblk) ? ro.XBASE(it + 3, rev) : ro.XBASE(1, rev ^ 1), ro.anq, lane);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+// P3's end: merge the 8 waves' (max, sum, context) and publish the chunk's partial for P4 -- PP: as polled words (tags of step t), else plain
+// floats in front of an XCD barrier
+template <int NQ, bool PP>
+LXO_DEV void xdec_p3_publish(float m, float l, const float (&acc)[8], const XChain& c, int ab, int aq, int t, float* part, float* wred, float (*redc)[XC]) {
+    const int tid = c.tid, lane = c.lane, wave = c.wave, c0 = lane * 8;
+    if (lane == 0) wred[wave] = m;
+    __syncthreads();
+    float mc = wred[0];
+#pragma unroll
+    for (int w = 1; w < XW; ++w) mc = fmaxf(mc, wred[w]);
+    const float sw = (l > 0.f) ? __expf(m - mc) : 0.f;
+    if (lane == 0) wred[XW + wave] = l * sw;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) redc[wave][c0 + e] = acc[e] * sw;
+    __syncthreads();
+    if constexpr (PP) {
+        unsigned* pw = reinterpret_cast<unsigned*>(part) + ((long long)ab * NQ + aq) * (PLW * 2);
+        if (tid == 0) {
+            float lt = 0.f;
+#pragma unroll
+            for (int w = 0; w < XW; ++w) lt += wred[XW + w];
+            const u32x4 st4 = {__float_as_uint(mc), (unsigned)(t + 1), __float_as_uint(lt), (unsigned)(t + 1)};
+            *reinterpret_cast<u32x4*>(pw + 256 * 2) = st4;
+        }
+        float tsum = 0.f;
+#pragma unroll
+        for (int w = 0; w < XW; ++w) tsum += redc[w][tid];
+        const float other = __shfl_xor(tsum, 1);
+        if (!(tid & 1)) *reinterpret_cast<u32x2*>(pw + (tid >> 1) * 2) = pack28(tsum, other, tag8_of(t));
+    } else {
+        float* pout = part + ((long long)ab * NQ + aq) * PST;
+        if (tid == 0) {
+            float lt = 0.f;
+#pragma unroll
+            for (int w = 0; w < XW; ++w) lt += wred[XW + w];
+            pout[XC] = mc; pout[XC + 1] = lt;
+        }
+        float tsum = 0.f;
+#pragma unroll
+        for (int w = 0; w < XW; ++w) tsum += redc[w][tid];
+        pout[tid] = tsum;
+    }
+}
+
+// P4's first request: the h~ half of the o projection's A operand (waves 0..3), asked for in front of the chunk partials -- all of P4's
+// requests go out up front, 16 bytes each
+template <class P>
+LXO_DEV void xdec_o_fetch(u32x4 (&a)[4], const P& p, const XChain& c, long long sn) {
+    if (c.wave < 4) {
+        const rsrc_t rn = make_rsrc(p.recb + sn * p.RECB, (unsigned)p.B * p.RECB * 2u);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) a[ks] = l2_load16(rn, (unsigned)(((c.b0 + c.arow) * p.RECB + OFF_HT + c.wave * 128 + ks * 32 + c.g4 * 8) * 2));
+    }
+}
+
+// P4: merge the chunk partials of the chain's samples into ctx -- the A tile of the o projection (actx) and, for the 16 channels this
+// workgroup owns, the record (slot sn).  Four groups of 128 threads split the NB samples; a thread holds 4 channels.
+// SM: the samples' softmax max and 1 / sum are kept too (smax, sinv: what alpha needs).  arrived: measurement only (null = off), stamped once the polled partials are there
+template <int NB, bool PP, bool SM, class P>
+LXO_DEV void xdec_p4_merge(const P& p, const XChain& c, long long sn, int t, float (*wgt)[32 / NB], float* smax, float* sinv, float (*redc)[XC],
+                           bf16_t (*actx)[XC + 8], unsigned long long* arrived) {
+    constexpr int NQ = 32 / NB;
+    const int tid = c.tid, wave = c.wave, b0 = c.b0;
+    const rsrc_t rpart = PP ? make_rsrc(reinterpret_cast<const unsigned*>(p.part) + (long long)b0 * NQ * (PLW * 2), (unsigned)(NB * NQ * PLW) * 8u)
+                            : make_rsrc(p.part + (long long)b0 * NQ * PST, (unsigned)(NB * NQ * PST) * 4u);
+    constexpr int SPG = NB >= 4 ? NB / 4 : 1, NG = NB / SPG;      // samples per thread group, groups that have samples
+    // chains of one or two samples: the 32 / 16 chunk partials of a sample are split over the 4 / 2 thread groups (8 chunks each = two rounds of
+    // four requests; one group per sample walked them in eight / four dependent rounds: P4 5.6 us of a 12.2 us step at B = 8) and the groups' sums meet in LDS
+    constexpr int GPS = NB >= 4 ? 1 : 4 / NB, CPG = NQ / GPS;
+    const int tg = tid >> 7, c4 = (tid & 127) * 4;
+    const int gsm = tg / GPS, cb = (tg - gsm * GPS) * CPG;      // this thread group's sample (block) and first chunk
+    // chunks requested at a time per sample.  Every request in flight pins four destination registers, and this merge is where the
+    // kernel's register demand peaks: with 8 x 16 bytes in flight per thread the allocator kept 17 dwords of loop-invariant
+    // addresses in scratch and reloaded them (behind `vmcnt(0)`) in every serial phase -- 4 in flight (2 samples x 2 chunks at
+    // B = 64) costs the merge one more L2 round trip and the step 1 us less: decoder forward 2.40 -> 2.30 ms
+    constexpr int QG = NB >= 4 ? 2 : 4;
+    u32x4 pc[SPG][QG];
+    float st_m = 0.f, st_l = 0.f;                               // wave 0: {max, sum} of (sample, chunk) = lane (lanes 32 .. 63 repeat lane 31's)
+    if constexpr (PP) {
+        // polled: the words of this thread's channel pair pairs ({28 bits x 2, tag} x 2 per 16 bytes) of the first chunk group, and -- wave 0 -- the
+        // {max, tag, sum, tag} words of every (sample, chunk) of the chain (NB * NQ = 32 of them: lanes 32 .. 63 repeat lane 31's)
+        if (wave == 0) {
+            u32x4 w1[1];
+            const unsigned off1[1] = {(unsigned)((min(tid, NB * NQ - 1) * PLW + 256) * 8)};
+            ll_wait<1>(w1, rpart, off1, (unsigned)(t + 1), c.err, c.s_dead);
+            st_m = __uint_as_float(w1[0][0]); st_l = __uint_as_float(w1[0][2]);
+        }
+        if (gsm < NG) {
+            u32x4 wq[SPG * QG];
+            unsigned offq[SPG * QG];
+#pragma unroll
+            for (int si = 0; si < SPG; ++si)
+#pragma unroll
+                for (int q = 0; q < QG; ++q) offq[si * QG + q] = (unsigned)((((gsm * SPG + si) * NQ + cb + q) * PLW + (c4 >> 1)) * 8);
+            ll_wait8<SPG * QG>(wq, rpart, offq, tag8_of(t), c.err, c.s_dead);
+#pragma unroll
+            for (int si = 0; si < SPG; ++si)
+#pragma unroll
+                for (int q = 0; q < QG; ++q) pc[si][q] = wq[si * QG + q];
+        }
+        if (arrived && tid == 0) *arrived = wall_clock64();
+    } else {
+        if (gsm < NG) {
+#pragma unroll
+            for (int si = 0; si < SPG; ++si)
+#pragma unroll
+                for (int q = 0; q < QG; ++q) pc[si][q] = l2_load16(rpart, (unsigned)((((gsm * SPG + si) * NQ + cb + q) * PST + c4) * 4));
+        }
+        if (wave == 0) {
+            const unsigned o = (unsigned)((min(tid, NB * NQ - 1) * PST + XC) * 4);
+            st_m = l2_load4(rpart, o); st_l = l2_load4(rpart, o + 4);
+        }
+    }
+    // softmax over the chunks of a sample, one lane per (sample, chunk) -- NB * NQ = 32 lanes of wave 0, log2(NQ) exchange rounds (one thread per
+    // sample walked its NQ chunks three times: ~2 us of serial code per step at NQ = 32, the chains of one sample)
+    if (wave == 0) {
+        float mm = st_l > 0.f ? st_m : -3.0e38f;
+#pragma unroll
+        for (int o = NQ / 2; o > 0; o >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o));
+        const float w = st_l > 0.f ? __expf(st_m - mm) : 0.f;
+        float ll = st_l * w;
+#pragma unroll
+        for (int o = NQ / 2; o > 0; o >>= 1) ll += __shfl_xor(ll, o);
+        const float inv = 1.0f / ll;
+        if (tid < NB * NQ) {
+            (&wgt[0][0])[tid] = w * inv;
+            if constexpr (SM) { if ((tid & (NQ - 1)) == 0) { smax[tid / NQ] = mm; sinv[tid / NQ] = inv; } }
+        }
+    }
+    __syncthreads();
+    // ctx[s][c4 .. c4+3]: A tile of the o projection; the 16 channels this workgroup owns also go to the record
+    if (gsm < NG) {
+#pragma unroll
+        for (int si = 0; si < SPG; ++si) {
+            const int sidx = gsm * SPG + si;
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int q0 = 0; q0 < CPG; q0 += QG) {
+#pragma unroll
+                for (int q = 0; q < QG; ++q) {
+                    const float w = wgt[sidx][cb + q0 + q];
+                    if constexpr (PP) {
+                        v[0] = fmaf(unpack28_lo(pc[si][q][0]), w, v[0]); v[1] = fmaf(unpack28_hi(pc[si][q][0], pc[si][q][1]), w, v[1]);
+                        v[2] = fmaf(unpack28_lo(pc[si][q][2]), w, v[2]); v[3] = fmaf(unpack28_hi(pc[si][q][2], pc[si][q][3]), w, v[3]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = fmaf(__uint_as_float(pc[si][q][e]), w, v[e]);
+                    }
+                }
+                if (q0 + QG < CPG) {                             // next group of chunks (compile-time condition: NQ, QG are constants)
+                    if constexpr (PP) {
+                        u32x4 wq[QG];
+                        unsigned offq[QG];
+#pragma unroll
+                        for (int q = 0; q < QG; ++q) offq[q] = (unsigned)(((sidx * NQ + cb + q0 + QG + q) * PLW + (c4 >> 1)) * 8);
+                        ll_wait8<QG>(wq, rpart, offq, tag8_of(t), c.err, c.s_dead);
+#pragma unroll
+                        for (int q = 0; q < QG; ++q) pc[si][q] = wq[q];
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < QG; ++q) pc[si][q] = l2_load16(rpart, (unsigned)(((sidx * NQ + cb + q0 + QG + q) * PST + c4) * 4));
+                    }
+                }
+            }
+            if constexpr (GPS > 1) {                             // the groups of a sample meet in LDS (the waves' partial-context buffer of P3 is free here)
+                *reinterpret_cast<f32x4*>(&redc[tg][c4]) = f32x4{v[0], v[1], v[2], v[3]};
+                __syncthreads();
+                if (cb == 0) {
+#pragma unroll
+                    for (int g = 1; g < GPS; ++g) { const f32x4 o4 = *reinterpret_cast<const f32x4*>(&redc[tg + g][c4]); v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3]; }
+                }
+            }
+            if (GPS > 1 && cb != 0) continue;
+            const u32x2 vb = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+            *reinterpret_cast<u32x2*>(&actx[sidx][c4]) = vb;
+            if ((c4 >> 4) == c.rank) {
+                const f32x4 vf = {v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<f32x4*>(p.rec + (sn + b0 + sidx) * p.REC + OFF_CTX + c4) = vf;
+                *reinterpret_cast<u32x2*>(p.recb + (sn + b0 + sidx) * p.RECB + OFF_CTX + c4) = vb;
+            }
+        }
+    }
+}
+
+// P4's end, behind the workgroup barrier that follows the merge: o = dropout(tanh([h~ | ctx] o_W)) (attention_cell.py:82-83), this workgroup's 16
+// columns, into the record (slot sn) and as hand-over words for the next step's P1 (two columns per word, tag t + 1).  a: waves 0..3 come with
+// their h~ fragments (xdec_o_fetch), waves 4..7 take ctx from the A tile -- of 16 rows (rows >= NB are zero) or of 8 (AROWS: the lanes of
+// rows >= NB repeat the last one).  dr: the dropout of o, null = none.
+template <int NB, int AROWS, class P>
+LXO_DEV void xdec_o_proj(u32x4 (&a)[4], const P& p, const XChain& c, long long sn, int t, const Drop* dr, const u32x4 (&wow)[4],
+                         const bf16_t (*actx)[XC + 8], float (*red)[8][64], unsigned* ll_o) {
+    if (c.wave >= 4) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const u32x4*>(&actx[AROWS == 16 ? c.r16 : c.arow][(c.wave - 4) * 128 + ks * 32 + c.g4 * 8]);
+    }
+    v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) acc = mfma16(a[ks], wow[ks], acc);
+    if (c.g4 * 4 < NB) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[c.wave][c.g4 * 4 + i][c.r16] = acc[i];
+    }
+    __syncthreads();
+    if (c.tid < NB * 16) {
+        const int row = c.tid >> 4, cc = c.tid & 15;
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < XW; ++w) v += red[w][row][cc];
+        const int bb = c.b0 + row, n = c.rank * 16 + cc;
+        v = tanh_x(v);
+        if (dr) v *= drop_scale(*dr, 2u, bb, n, XO);
+        p.rec[(sn + bb) * p.REC + n] = v;
+        const bf16_t vb = f2bf(v);
+        p.recb[(sn + bb) * p.RECB + n] = vb;
+        const unsigned mine = (unsigned)vb, other = (unsigned)__shfl_xor((int)mine, 1);
+        if (!(cc & 1)) { const u32x2 wv = {mine | (other << 16), (unsigned)(t + 1)}; *reinterpret_cast<u32x2*>(ll_o + ((bb * 256 + (n >> 1)) * 2)) = wv; }
+    }
+}
+
+// measurement aid of the forward and backward kernels (p.dbg, null = off): thread 0 stamps slot i of the launch's step-th step
+#define XSTAMP(step, i) do { if (dbg && tid == 0) dbg[(step) * 16 + (i)] = wall_clock64(); } while (0)
+
 template <int NB, int ATT_U, bool EXPD>
 __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
     constexpr int NQ = 32 / NB;                                  // attention chunks per sample = workgroups per sample
@@ -288,72 +707,37 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
     __shared__ float wred[2 * XW];
     __shared__ int s_rank, s_dead;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave: known uniform (row arithmetic on the scalar ALU)
-    const int r16 = lane & 15, g4 = lane >> 4;
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7u;
-    unsigned* xsync = p.sync + xcc * 64;
-    unsigned* err = p.sync + 8 * 64;
-    if (tid == 0) { s_dead = 0; s_rank = (int)atomicAdd(xsync + 32, 1u); }
+    // A forward-chain workgroup of two and more samples must allocate all 256 VGPRs per lane (granules of 8: v254 named = 256), so that
+    // 8 waves x 256 fill the CU's register file and no foreign wave fits beside it: one that did would stretch this member's phases and with
+    // them every step of its chain.  A chain that cannot get a whole CU does not assemble and gives up after 200 ms (tests/test_gpu_xdec.py).
+    // Exempt: the chains of one sample (225 VGPRs), the decode kernels and the backward kernels (up to 241).  They leave room for a small
+    // foreign wave and run beside it; claiming the file for them would turn a shared CU, which they tolerate, into a dropped step or decode.
+    if constexpr (NB >= 2) asm volatile("" ::: "v254");
+    XChain c = xchain_ticket(p.sync, NB, &s_rank, &s_dead);
+    const int tid = c.tid, lane = c.lane, wave = c.wave, r16 = c.r16, g4 = c.g4;
     for (int i = tid; i < 16 * (XC + 8); i += 512) (&actx[0][0])[i] = 0;     // rows >= NB of the A tile stay zero
     __syncthreads();
-    const int rank = s_rank;
-    if (rank >= 32) { if (tid == 0) *reinterpret_cast<volatile unsigned*>(err) = 2u; return; }   // more than 32 workgroups on this XCD: not a chain
+    if (!xchain_rank(c, &s_rank)) return;
+    const int rank = c.rank, b0 = c.b0, u0 = rank * 16;
+    unsigned* xsync = c.xsync; unsigned* err = c.err;
     const int B = p.B, T = p.T;
-    const int b0 = (int)xcc * NB;                                // first sample of this chain
-    const int u0 = rank * 16, e0 = rank * 8, o0 = rank * 16;
 
-    // ---- resident weights: this wave's eighth of every contraction, as MFMA B fragments (lane = (column r16, k group g4)) ----
-    // K_LSTM_RT: gate i in registers, gates j, f, o in LDS (96 KB, fragment-shaped: [wave][gate][k-step][lane] x 16 B, read back by the
-    // lane that wrote it) -- 88 resident VGPRs left no room for the attention stream's two row blocks in flight
-    // P1's contraction index [o (512) | h (512)]: k-steps 0, 1 of a wave lie in o (polled hand-over words), 2, 3 in h (plain loads)
-#define P1K(ks) ((ks) < 2 ? wave * 64 + (ks) * 32 : XO + wave * 64 + ((ks) - 2) * 32)
     u32x4 wrt0[4], wow[4];
-    u32x4* wl = reinterpret_cast<u32x4*>(xdec_dyn_lds) + (wave * 12) * 64 + lane;       // + (gate - 1) * 4 * 64 + ks * 64
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const u32x4 w = *reinterpret_cast<const u32x4*>(p.Wrt + (long long)(q * XU + u0 + r16) * p.ldrt + P1K(ks) + g4 * 8);
-            if (q == 0) wrt0[ks] = w; else wl[((q - 1) * 4 + ks) * 64] = w;
-        }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const u32x4 w = *reinterpret_cast<const u32x4*>(p.Wah + (long long)(e0 + (r16 & 7)) * p.ldah + wave * 64 + ks * 32 + g4 * 8);
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        wahs[wave][ks][lane] = r16 < 8 ? w : z;                  // an 8-column slice in a 16-column tile
-    }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-        wow[ks] = *reinterpret_cast<const u32x4*>(p.Wow + (long long)(o0 + r16) * p.ldow + wave * 128 + ks * 32 + g4 * 8);
+    u32x4* wl = reinterpret_cast<u32x4*>(xdec_dyn_lds) + (wave * 12) * 64 + lane;
     float bt[4];
-    { const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.beta + lane * 4); const float f = EXPD ? -2.f : 1.f; bt[0] = f * b4[0]; bt[1] = f * b4[1]; bt[2] = f * b4[2]; bt[3] = f * b4[3]; }
+    xdec_resident<EXPD>(p, c, wrt0, wl, wahs, wow, bt);
     if (tid < NB * 16) cst[tid >> 4][tid & 15] = p.cs[(long long)(b0 + (tid >> 4)) * XU + u0 + (tid & 15)];
 
-    // attention role of this workgroup
-    const int as = rank / NQ, aq = rank - as * NQ;               // (sample of the chain, chunk)
-    const int ab = b0 + as;
-    const int rows_per = (p.R + NQ - 1) / NQ;
-    const int ar0 = aq * rows_per;
-    const int an = min(p.R, ar0 + rows_per) - ar0;               // may be <= 0 for a trailing chunk
-    const bf16_t* ai = (EXPD ? p.att_exp : p.att_img) + ((long long)ab * p.R + ar0) * XE;
-    const bf16_t* im = p.img + ((long long)ab * p.R + ar0) * XC;
-    float* pout = p.part + ((long long)ab * NQ + aq) * PST;
-    const int arow = min(r16, NB - 1);                           // A-fragment row of this lane (rows >= NB repeat the last one; their products are dropped)
+    const XRole<ATT_U> ro = xdec_role<NB, ATT_U>(c, p.R, p.img, EXPD ? p.att_exp : p.att_img);
     Drop dr = p.dr;
     unsigned ph = 0;
-    // The chunk is walked in blocks of XW * ATT_U rows, two blocks per loop trip (buffers A and B): block i+1 is in flight while block i is
-    // computed, and the FIRST block of the next step is requested before this step's last block is computed -- it lands during P4 / P1 / P2,
-    // so P3 starts on data that is already in registers.  An odd block count ends on an A half (no padded block: its clamped loads cost 1 / 8 of
-    // the benchmark chunk's requests).
-    const int nblk = an > 0 ? (an + XW * ATT_U - 1) / (XW * ATT_U) : 0;
-    const int anq = an > 0 ? an : 1;                             // an empty trailing chunk still issues (masked) loads: row 0 of the first sample
-    const rsrc_t imq = make_rsrc(an > 0 ? im : p.img, (unsigned)anq * XC * 2u);
-    const rsrc_t aiq = make_rsrc(an > 0 ? ai : (EXPD ? p.att_exp : p.att_img), (unsigned)anq * XE * 2u);
     u32x4 xiA[ATT_U], xiB[ATT_U]; u32x2 xaA[ATT_U], xaB[ATT_U];
-    att_load<ATT_U>(xiA, xaA, imq, aiq, wave, anq, lane);        // step 0 walks forward: its first blocks are blocks 0 and 1
-    att_load<ATT_U>(xiB, xaB, imq, aiq, wave + XW * ATT_U, anq, lane);
+    // the first two row blocks of step `ts`'s walk (direction ts & 1) into the two buffers
+    auto prefetch = [&](int ts) {
+        att_load<ATT_U>(xiA, xaA, ro.imq, ro.aiq, ro.XBASE(0, ts & 1), ro.anq, lane);
+        att_load<ATT_U>(xiB, xaB, ro.imq, ro.aiq, ro.XBASE(1, ts & 1), ro.anq, lane);
+    };
+    prefetch(0);                                                 // step 0 walks forward: its first blocks are blocks 0 and 1
 
     // x-part of the LSTM pre-activation of this thread's epilogue element (threads < NB * 16: row tid >> 4, unit tid & 15), one step ahead
     float pzn[4];
@@ -369,47 +753,25 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
     const rsrc_t rll_ah = make_rsrc(ll_ah, (unsigned)B * XE * 8u);
     const rsrc_t rll_ht = make_rsrc(ll_ht, (unsigned)B * 256u * 8u);
     const rsrc_t rll_o = make_rsrc(ll_o, (unsigned)B * 256u * 8u);
-    unsigned long long* dbg = p.dbg ? p.dbg + ((long long)(xcc * 32 + rank) * T) * 16 : nullptr;
-#define XSTAMP(i) do { if (dbg && tid == 0) dbg[t * 16 + (i)] = wall_clock64(); } while (0)
-    // the first two row blocks of step `ts`'s walk (direction ts & 1) into the two buffers
-    auto prefetch = [&](int ts) {
-        const int rv = ts & 1;
-        att_load<ATT_U>(xiA, xaA, imq, aiq, wave + XW * ATT_U * (rv ? nblk - 1 : 0), anq, lane);
-        att_load<ATT_U>(xiB, xaB, imq, aiq, wave + XW * ATT_U * (rv ? nblk - 2 : 1), anq, lane);
-    };
+    unsigned long long* dbg = p.dbg ? p.dbg + ((long long)(c.xcc * 32 + rank) * T) * 16 : nullptr;
     for (int t = 0; t < T; ++t) {
         dr.t = t;
-        XSTAMP(0);
+        XSTAMP(t, 0);
         const long long sp = (long long)t * B, sn = (long long)(t + 1) * B;       // row blocks of the previous / this state
         // =========================== P1: LSTM cell ===========================
         {
-            const rsrc_t rp = make_rsrc(p.recb + sp * p.RECB, (unsigned)B * p.RECB * 2u);
             u32x4 a[4];
-            if ((kLL & 8) && t > 0) {
-                // o_{t-1}: polled from the hand-over words the o projection of the previous step left (no barrier behind P4)
-#pragma unroll
-                for (int ks = 2; ks < 4; ++ks) a[ks] = l2_load16(rp, (unsigned)(((b0 + arow) * p.RECB + P1K(ks) + g4 * 8) * 2));
-                u32x4 w[4];
-                unsigned off[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) off[j] = (unsigned)(((b0 + arow) * 256 + ((P1K(j >> 1) + g4 * 8) >> 1)) * 8 + (j & 1) * 16);
-                ll_wait<4>(w, rll_o, off, (unsigned)t, err, &s_dead);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) a[ks] = u32x4{w[2 * ks][0], w[2 * ks][2], w[2 * ks + 1][0], w[2 * ks + 1][2]};
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) a[ks] = l2_load16(rp, (unsigned)(((b0 + arow) * p.RECB + P1K(ks) + g4 * 8) * 2));
-            }
+            xdec_p1_fetch(a, p, c, sp, (kLL & 8) && t > 0, rll_o, (unsigned)t);
             // the x-part of this thread's epilogue element: requested one step ahead (at the start of the previous step's P3) -- zx_t was
             // written before the launch and comes from HBM, 2 us away; asked for here it was the critical path of the phase
-            float pz[4];
+            float g[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) pz[q] = pzn[q];
+            for (int q = 0; q < 4; ++q) g[q] = pzn[q];
             const int erow = tid >> 4, eu = tid & 15;
             v4f acc[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[q] = v4f{0.f, 0.f, 0.f, 0.f};
-            if (dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); XSTAMP(9); }      // measurement only: when the A operand has arrived
+            if (dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); XSTAMP(t, 9); }      // measurement only: when the A operand has arrived
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 acc[0] = mfma16(a[ks], wrt0[ks], acc[0]);
@@ -423,29 +785,20 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[wave][g4 * 4 + i][q * 16 + r16] = acc[q][i];
             }
-            XSTAMP(10);
+            XSTAMP(t, 10);
             __syncthreads();
-            XSTAMP(11);
+            XSTAMP(t, 11);
             if (kPF == 1 && t > 0 && wave >= 2) prefetch(t);      // (step 0's blocks were requested in the prologue)
             if (tid < NB * 16) {
-                // TF-1.12 LSTMCell, gate order i, j, f, o, forget_bias 1.0 (attention_cell.py:71)
-                float g[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float z = pz[q];
-#pragma unroll
-                    for (int w = 0; w < XW; ++w) z += red[w][erow][q * 16 + eu];
-                    g[q] = (q == 1) ? tanh_x(z) : sigm_x(q == 2 ? z + 1.0f : z);
-                }
-                const float c = g[2] * cst[erow][eu] + g[0] * g[1];
-                const float h = g[3] * tanh_x(c);
+                float cn, h;
+                xdec_lstm(g, red, erow, eu, cst[erow][eu], cn, h);
                 const int bb = b0 + erow, u = u0 + eu;
                 const float ht = h * drop_scale(dr, 1u, bb, u, XU);          // h~ = dropout(h) (attention_cell.py:72)
-                cst[erow][eu] = c;
+                cst[erow][eu] = cn;
                 float* gr = p.gates + (sp + bb) * 4 * XU + u;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) gr[q * XU] = g[q];
-                p.cs[(sn + bb) * XU + u] = c;
+                p.cs[(sn + bb) * XU + u] = cn;
                 float* rr = p.rec + (sn + bb) * p.REC;
                 bf16_t* rb = p.recb + (sn + bb) * p.RECB;
                 rr[OFF_H + u] = h; rr[OFF_HT + u] = ht;
@@ -457,48 +810,16 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
             }
             if (kPF == 1 && t > 0 && wave < 2) prefetch(t);
         }
-        XSTAMP(1);
+        XSTAMP(t, 1);
         if (kLL & 1) __syncthreads();                       // (the partial tiles in LDS are rewritten by P2)
         else xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(2);
+        XSTAMP(t, 2);
         // =========================== P2: att_h = h~ W ===========================
-        const rsrc_t rn = make_rsrc(p.recb + sn * p.RECB, (unsigned)B * p.RECB * 2u);
-        {
-            u32x4 a[2];
-            if (kLL & 1) {
-                u32x4 w[4];
-                unsigned off[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) off[j] = (unsigned)(((b0 + arow) * 256 + ((wave * 64 + (j >> 1) * 32 + g4 * 8) >> 1)) * 8 + (j & 1) * 16);
-                ll_wait<4>(w, rll_ht, off, (unsigned)(t + 1), err, &s_dead);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) a[ks] = u32x4{w[2 * ks][0], w[2 * ks][2], w[2 * ks + 1][0], w[2 * ks + 1][2]};
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) a[ks] = l2_load16(rn, (unsigned)(((b0 + arow) * p.RECB + OFF_HT + wave * 64 + ks * 32 + g4 * 8) * 2));
-            }
-            v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) acc = mfma16(a[ks], wahs[wave][ks][lane], acc);
-            if (g4 * 4 < NB) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[wave][g4 * 4 + i][r16] = acc[i];
-            }
-            __syncthreads();
-            if (tid < NB * 8) {
-                const int row = tid >> 3, e = tid & 7;
-                float v = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) v += red[w][row][e];
-                p.atth[(sp + b0 + row) * XE + e0 + e] = v;
-                const u32x2 wv = {__float_as_uint(v), (unsigned)(t + 1)};
-                *reinterpret_cast<u32x2*>(ll_ah + ((b0 + row) * XE + e0 + e) * 2) = wv;      // the attention workgroups poll these words: no barrier
-            }
-            if (kPF == 2 && t > 0) prefetch(t);
-        }
-        XSTAMP(3);
+        xdec_p2<NB, (kLL & 1) != 0, true>(p, c, sp, sn, t, rll_ht, ll_ah, red, wahs);
+        if (kPF == 2 && t > 0) prefetch(t);
+        XSTAMP(t, 3);
         if (!(kLL & 2)) xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(4);
+        XSTAMP(t, 4);
         // =========================== P3: attention chunk (scores, online softmax, context) ===========================
         {
             {   // next step's x-part (unconditional: the last step re-reads its own)
@@ -507,282 +828,76 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) pzn[q] = zr[q * XU];
             }
-            u32x4 aw[2];
-            { const unsigned off[2] = {(unsigned)((ab * XE + lane * 4) * 8), (unsigned)((ab * XE + lane * 4) * 8 + 16)}; ll_wait<2>(aw, rll_ah, off, (unsigned)(t + 1), err, &s_dead); }
             float ah[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ah[j] = __uint_as_float(aw[j >> 1][(j & 1) * 2]);      // (behind a barrier the tags already match: one pass)
-                if constexpr (EXPD) ah[j] = __builtin_amdgcn_exp2f(fminf(fmaxf(ah[j] * 2.8853900817779268f, -60.f), 60.f));      // E_a
-            }
-            const int c0 = lane * 8;
+            xdec_att_h<EXPD>(ah, c, ro.ab, rll_ah, (unsigned)(t + 1));
             float m = -3.0e38f, l = 0.f, acc[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-            // blocks walked in alternating directions from step to step (what this step read last is what the next one reads first: L2 reuse)
             const int rev = t & 1;
-#define XBASE(i, rv) (wave + XW * ATT_U * ((rv) ? nblk - 1 - (i) : (i)))
-            // entering: block 0 in A and block 1 in B (requested at the end of the previous step's P3).  Each buffer is refilled right
-            // after its block is computed -- with the block two ahead, or, at the end of the chunk, with the NEXT STEP's first two blocks
-            // (its direction is the other one): they land during P4 / P1 / P2
-            if constexpr (kPF == 0) {
-            for (int it = 0; it < nblk; it += 2) {
-                att_block<ATT_U, EXPD>(xiA, xaA, XBASE(it, rev), an, ah, bt, m, l, acc, sc, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                att_load<ATT_U>(xiA, xaA, imq, aiq, (it + 2 < nblk) ? XBASE(it + 2, rev) : XBASE(0, rev ^ 1), anq, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                if (it + 1 < nblk) {                              // (an odd block count ends on an A half: B already holds the next step's block 1)
-                    att_block<ATT_U, EXPD>(xiB, xaB, XBASE(it + 1, rev), an, ah, bt, m, l, acc, sc, lane);
+            if constexpr (kPF == 0) xdec_walk<ATT_U, EXPD>(xiA, xaA, xiB, xaB, ro, rev, ah, bt, m, l, acc, sc, lane);
+            else {
+                // the chunk ends with nothing in flight (the next step's first blocks are requested elsewhere: kPF).  Peeled so that every load is
+                // unconditional on its path (a load behind a branch makes hipcc wait vmcnt(0) at the join)
+                const int nblk = ro.nblk, an = ro.an, anq = ro.anq;
+                int it = 0;
+                for (; it + 3 < nblk; it += 2) {
+                    att_block<ATT_U, EXPD>(xiA, xaA, ro.XBASE(it, rev), an, ah, bt, m, l, acc, sc, lane);
                     __builtin_amdgcn_sched_barrier(0);
-                    att_load<ATT_U>(xiB, xaB, imq, aiq, (it + 3 < nblk) ? XBASE(it + 3, rev) : XBASE(1, rev ^ 1), anq, lane);
+                    att_load<ATT_U>(xiA, xaA, ro.imq, ro.aiq, ro.XBASE(it + 2, rev), anq, lane);
+                    __builtin_amdgcn_sched_barrier(0);
+                    att_block<ATT_U, EXPD>(xiB, xaB, ro.XBASE(it + 1, rev), an, ah, bt, m, l, acc, sc, lane);
+                    __builtin_amdgcn_sched_barrier(0);
+                    att_load<ATT_U>(xiB, xaB, ro.imq, ro.aiq, ro.XBASE(it + 3, rev), anq, lane);
                     __builtin_amdgcn_sched_barrier(0);
                 }
+                const int rem = nblk - it;                       // 0 (empty chunk) .. 3
+                if (rem >= 1) att_block<ATT_U, EXPD>(xiA, xaA, ro.XBASE(it, rev), an, ah, bt, m, l, acc, sc, lane);
+                if (rem == 3) { __builtin_amdgcn_sched_barrier(0); att_load<ATT_U>(xiA, xaA, ro.imq, ro.aiq, ro.XBASE(it + 2, rev), anq, lane); __builtin_amdgcn_sched_barrier(0); }
+                if (rem >= 2) att_block<ATT_U, EXPD>(xiB, xaB, ro.XBASE(it + 1, rev), an, ah, bt, m, l, acc, sc, lane);
+                if (rem == 3) att_block<ATT_U, EXPD>(xiA, xaA, ro.XBASE(it + 2, rev), an, ah, bt, m, l, acc, sc, lane);
             }
-            } else {
-            // the chunk ends with nothing in flight (the next step's first blocks are requested elsewhere: kPF).  Peeled so that every load is
-            // unconditional on its path (a load behind a branch makes hipcc wait vmcnt(0) at the join)
-            int it = 0;
-            for (; it + 3 < nblk; it += 2) {
-                att_block<ATT_U, EXPD>(xiA, xaA, XBASE(it, rev), an, ah, bt, m, l, acc, sc, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                att_load<ATT_U>(xiA, xaA, imq, aiq, XBASE(it + 2, rev), anq, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                att_block<ATT_U, EXPD>(xiB, xaB, XBASE(it + 1, rev), an, ah, bt, m, l, acc, sc, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                att_load<ATT_U>(xiB, xaB, imq, aiq, XBASE(it + 3, rev), anq, lane);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const int rem = nblk - it;                           // 0 (empty chunk) .. 3
-            if (rem >= 1) att_block<ATT_U, EXPD>(xiA, xaA, XBASE(it, rev), an, ah, bt, m, l, acc, sc, lane);
-            if (rem == 3) { __builtin_amdgcn_sched_barrier(0); att_load<ATT_U>(xiA, xaA, imq, aiq, XBASE(it + 2, rev), anq, lane); __builtin_amdgcn_sched_barrier(0); }
-            if (rem >= 2) att_block<ATT_U, EXPD>(xiB, xaB, XBASE(it + 1, rev), an, ah, bt, m, l, acc, sc, lane);
-            if (rem == 3) att_block<ATT_U, EXPD>(xiA, xaA, XBASE(it + 2, rev), an, ah, bt, m, l, acc, sc, lane);
-            }
-#undef XBASE
-            // merge the 8 waves
-            if (lane == 0) wred[wave] = m;
-            __syncthreads();
-            float mc = wred[0];
-#pragma unroll
-            for (int w = 1; w < XW; ++w) mc = fmaxf(mc, wred[w]);
-            const float sw = (l > 0.f) ? __expf(m - mc) : 0.f;
-            if (lane == 0) wred[XW + wave] = l * sw;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) redc[wave][c0 + e] = acc[e] * sw;
-            __syncthreads();
-            if constexpr (PP) {
-                unsigned* pw = reinterpret_cast<unsigned*>(p.part) + ((long long)ab * NQ + aq) * (PLW * 2);
-                if (tid == 0) {
-                    float lt = 0.f;
-#pragma unroll
-                    for (int w = 0; w < XW; ++w) lt += wred[XW + w];
-                    const u32x4 st4 = {__float_as_uint(mc), (unsigned)(t + 1), __float_as_uint(lt), (unsigned)(t + 1)};
-                    *reinterpret_cast<u32x4*>(pw + 256 * 2) = st4;
-                }
-                float tsum = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) tsum += redc[w][tid];
-                const float other = __shfl_xor(tsum, 1);
-                if (!(tid & 1)) *reinterpret_cast<u32x2*>(pw + (tid >> 1) * 2) = pack28(tsum, other, tag8_of(t));
-            } else {
-            if (tid == 0) {
-                float lt = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) lt += wred[XW + w];
-                pout[XC] = mc; pout[XC + 1] = lt;
-            }
-            {
-                float tsum = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) tsum += redc[w][tid];
-                pout[tid] = tsum;
-            }
-            }
+            xdec_p3_publish<NQ, PP>(m, l, acc, c, ro.ab, ro.aq, t, p.part, wred, redc);
         }
-        XSTAMP(5);
+        XSTAMP(t, 5);
         if constexpr (!PP) xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(6);
+        XSTAMP(t, 6);
         // =========================== P4: merge the chunks; alpha; ctx; o projection ===========================
         {
-            const rsrc_t rpart = PP ? make_rsrc(reinterpret_cast<const unsigned*>(p.part) + (long long)b0 * NQ * (PLW * 2), (unsigned)(NB * NQ * PLW) * 8u)
-                                           : make_rsrc(p.part + (long long)b0 * NQ * PST, (unsigned)(NB * NQ * PST) * 4u);
-            // the h~ half of the A operand (waves 0..3) and the chunk partials of this thread's 4 channels for its thread group's samples
-            // (four groups of 128 threads split the NB samples): all requested up front, 16 bytes per request
             u32x4 a[4];
-            if (wave < 4) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) a[ks] = l2_load16(rn, (unsigned)(((b0 + arow) * p.RECB + OFF_HT + wave * 128 + ks * 32 + g4 * 8) * 2));
-            }
-            constexpr int SPG = NB >= 4 ? NB / 4 : 1, NG = NB / SPG;      // samples per thread group, groups that have samples
-            // chains of one or two samples: the 32 / 16 chunk partials of a sample are split over the 4 / 2 thread groups (8 chunks each = two rounds of
-            // four requests; one group per sample walked them in eight / four dependent rounds: P4 5.6 us of a 12.2 us step at B = 8) and the groups' sums meet in LDS
-            constexpr int GPS = NB >= 4 ? 1 : 4 / NB, CPG = NQ / GPS;
-            const int tg = tid >> 7, c4 = (tid & 127) * 4;
-            const int gsm = tg / GPS, cb = (tg - gsm * GPS) * CPG;      // this thread group's sample (block) and first chunk
-            // chunks requested at a time per sample.  Every request in flight pins four destination registers, and this merge is where the
-            // kernel's register demand peaks: with 8 x 16 bytes in flight per thread the allocator kept 17 dwords of loop-invariant
-            // addresses in scratch and reloaded them (behind `vmcnt(0)`) in every serial phase -- 4 in flight (2 samples x 2 chunks at
-            // B = 64) costs the merge one more L2 round trip and the step 1 us less: decoder forward 2.40 -> 2.30 ms
-            constexpr int QG = NB >= 4 ? 2 : 4;
-            u32x4 pc[SPG][QG];
-            float st_m = 0.f, st_l = 0.f;                       // wave 0: {max, sum} of (sample, chunk) = lane (lanes 32 .. 63 repeat lane 31's)
-            if constexpr (PP) {
-                // polled: the words of this thread's channel pair pairs ({bf16 x 2, tag} x 2 per 16 bytes) of the first chunk group, and -- wave 0 -- the
-                // {max, tag, sum, tag} words of every (sample, chunk) of the chain (NB * NQ = 32 of them: lanes 32 .. 63 repeat lane 31's)
-                if (wave == 0) {
-                    u32x4 w1[1];
-                    const unsigned off1[1] = {(unsigned)((min(tid, NB * NQ - 1) * PLW + 256) * 8)};
-                    ll_wait<1>(w1, rpart, off1, (unsigned)(t + 1), err, &s_dead);
-                    st_m = __uint_as_float(w1[0][0]); st_l = __uint_as_float(w1[0][2]);
-                }
-                if (gsm < NG) {
-                    u32x4 wq[SPG * QG];
-                    unsigned offq[SPG * QG];
-#pragma unroll
-                    for (int si = 0; si < SPG; ++si)
-#pragma unroll
-                        for (int q = 0; q < QG; ++q) offq[si * QG + q] = (unsigned)((((gsm * SPG + si) * NQ + cb + q) * PLW + (c4 >> 1)) * 8);
-                    ll_wait8<SPG * QG>(wq, rpart, offq, tag8_of(t), err, &s_dead);
-#pragma unroll
-                    for (int si = 0; si < SPG; ++si)
-#pragma unroll
-                        for (int q = 0; q < QG; ++q) pc[si][q] = wq[si * QG + q];
-                }
-                XSTAMP(12);                                       // measurement only: the polled partials have arrived (stamp 6 -> 12 = the wait that used to sit at the barrier behind P3)
-            } else {
-            if (gsm < NG) {
-#pragma unroll
-                for (int si = 0; si < SPG; ++si)
-#pragma unroll
-                    for (int q = 0; q < QG; ++q) pc[si][q] = l2_load16(rpart, (unsigned)((((gsm * SPG + si) * NQ + cb + q) * PST + c4) * 4));
-            }
-            if (wave == 0) {
-                const unsigned o = (unsigned)((min(tid, NB * NQ - 1) * PST + XC) * 4);
-                st_m = l2_load4(rpart, o); st_l = l2_load4(rpart, o + 4);
-            }
-            }
-            // softmax over the chunks of a sample, one lane per (sample, chunk) -- NB * NQ = 32 lanes of wave 0, log2(NQ) exchange rounds (one thread per
-            // sample walked its NQ chunks three times: ~2 us of serial code per step at NQ = 32, the chains of one sample)
-            if (wave == 0) {
-                float mm = st_l > 0.f ? st_m : -3.0e38f;
-#pragma unroll
-                for (int o = NQ / 2; o > 0; o >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o));
-                const float w = st_l > 0.f ? __expf(st_m - mm) : 0.f;
-                float ll = st_l * w;
-#pragma unroll
-                for (int o = NQ / 2; o > 0; o >>= 1) ll += __shfl_xor(ll, o);
-                const float inv = 1.0f / ll;
-                if (tid < NB * NQ) {
-                    (&wgt[0][0])[tid] = w * inv;
-                    if ((tid & (NQ - 1)) == 0) { smax[tid / NQ] = mm; sinv[tid / NQ] = inv; }
-                }
-            }
-            __syncthreads();
-            // ctx[s][c4 .. c4+3]: A tile of the o projection; the 16 channels this workgroup owns also go to the record
-            if (gsm < NG) {
-#pragma unroll
-                for (int si = 0; si < SPG; ++si) {
-                    const int sidx = gsm * SPG + si;
-                    float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int q0 = 0; q0 < CPG; q0 += QG) {
-#pragma unroll
-                        for (int q = 0; q < QG; ++q) {
-                            const float w = wgt[sidx][cb + q0 + q];
-                            if constexpr (PP) {
-                                v[0] = fmaf(unpack28_lo(pc[si][q][0]), w, v[0]); v[1] = fmaf(unpack28_hi(pc[si][q][0], pc[si][q][1]), w, v[1]);
-                                v[2] = fmaf(unpack28_lo(pc[si][q][2]), w, v[2]); v[3] = fmaf(unpack28_hi(pc[si][q][2], pc[si][q][3]), w, v[3]);
-                            } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaf(__uint_as_float(pc[si][q][e]), w, v[e]);
-                            }
-                        }
-                        if (q0 + QG < CPG) {                       // next group of chunks (compile-time condition: NQ, QG are constants)
-                            if constexpr (PP) {
-                                u32x4 wq[QG];
-                                unsigned offq[QG];
-#pragma unroll
-                                for (int q = 0; q < QG; ++q) offq[q] = (unsigned)(((sidx * NQ + cb + q0 + QG + q) * PLW + (c4 >> 1)) * 8);
-                                ll_wait8<QG>(wq, rpart, offq, tag8_of(t), err, &s_dead);
-#pragma unroll
-                                for (int q = 0; q < QG; ++q) pc[si][q] = wq[q];
-                            } else {
-#pragma unroll
-                            for (int q = 0; q < QG; ++q) pc[si][q] = l2_load16(rpart, (unsigned)(((sidx * NQ + cb + q0 + QG + q) * PST + c4) * 4));
-                            }
-                        }
-                    }
-                    if constexpr (GPS > 1) {                      // the groups of a sample meet in LDS (the waves' partial-context buffer of P3 is free here)
-                        *reinterpret_cast<f32x4*>(&redc[tg][c4]) = f32x4{v[0], v[1], v[2], v[3]};
-                        __syncthreads();
-                        if (cb == 0) {
-#pragma unroll
-                            for (int g = 1; g < GPS; ++g) { const f32x4 o4 = *reinterpret_cast<const f32x4*>(&redc[tg + g][c4]); v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3]; }
-                        }
-                    }
-                    if (GPS > 1 && cb != 0) continue;
-                    const u32x2 vb = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-                    *reinterpret_cast<u32x2*>(&actx[sidx][c4]) = vb;
-                    if ((c4 >> 4) == rank) {
-                        const f32x4 vf = {v[0], v[1], v[2], v[3]};
-                        *reinterpret_cast<f32x4*>(p.rec + (sn + b0 + sidx) * p.REC + OFF_CTX + c4) = vf;
-                        *reinterpret_cast<u32x2*>(p.recb + (sn + b0 + sidx) * p.RECB + OFF_CTX + c4) = vb;
-                    }
-                }
-            }
+            xdec_o_fetch(a, p, c, sn);
+            // (stamp 6 -> 12 = the wait for the polled partials, which used to sit at the barrier behind P3)
+            xdec_p4_merge<NB, PP, true>(p, c, sn, t, wgt, smax, sinv, redc, actx, dbg ? dbg + t * 16 + 12 : nullptr);
             if (kPF == 3) prefetch(t + 1);
             // alpha of this workgroup's chunk (what the reference hands to its visualisation hook, attention_mechanism.py:96-105)
             {
-                const float mm = smax[as], inv = sinv[as];
-                float* al = p.alpha + (sp + ab) * p.Rp + ar0;
-                for (int r = tid; r < an; r += 512) al[r] = __expf(sc[r] - mm) * inv;
+                const float mm = smax[ro.as], inv = sinv[ro.as];
+                float* al = p.alpha + (sp + ro.ab) * p.Rp + ro.ar0;
+                for (int r = tid; r < ro.an; r += 512) al[r] = __expf(sc[r] - mm) * inv;
             }
             __syncthreads();
-            if (wave >= 4) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const u32x4*>(&actx[r16][(wave - 4) * 128 + ks * 32 + g4 * 8]);
-            }
-            v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) acc = mfma16(a[ks], wow[ks], acc);
-            if (g4 * 4 < NB) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[wave][g4 * 4 + i][r16] = acc[i];
-            }
-            __syncthreads();
-            if (tid < NB * 16) {
-                const int row = tid >> 4, cc = tid & 15;
-                float v = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) v += red[w][row][cc];
-                const int bb = b0 + row, n = o0 + cc;
-                v = tanh_x(v) * drop_scale(dr, 2u, bb, n, XO);            // o = dropout(tanh(.)) (attention_cell.py:82-83)
-                p.rec[(sn + bb) * p.REC + n] = v;
-                const bf16_t vb = f2bf(v);
-                p.recb[(sn + bb) * p.RECB + n] = vb;
-                const unsigned mine = (unsigned)vb, other = (unsigned)__shfl_xor((int)mine, 1);
-                if (!(cc & 1)) { const u32x2 wv = {mine | (other << 16), (unsigned)(t + 1)}; *reinterpret_cast<u32x2*>(ll_o + ((bb * 256 + (n >> 1)) * 2)) = wv; }
-            }
+            xdec_o_proj<NB, 16>(a, p, c, sn, t, &dr, wow, actx, red, ll_o);
         }
-        XSTAMP(7);
+        XSTAMP(t, 7);
         if (kLL & 8) __syncthreads();                       // (the partial tiles in LDS are rewritten by the next step's P1)
         else xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(8);
+        XSTAMP(t, 8);
     }
-#undef XSTAMP
+}
+
+// One launch of a chain kernel: 256 workgroups (one per CU) of 512 threads, the LDS-resident part of the LSTM weights (96 KB) as dynamic LDS
+template <auto KERNEL, class P>
+int xdec_launch(const P& p, hipStream_t st) {
+    constexpr int DYN = XW * 12 * 64 * 16;
+    static bool attr_done = false;
+    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
+    hipLaunchKernelGGL(KERNEL, dim3(256), dim3(512), DYN, st, p);
+    return (int)hipGetLastError();
 }
 
 template <int NB>
 int launch_nb(const XDecFwd& p, int att_u, hipStream_t st) {
-    constexpr int DYN = XW * 12 * 64 * 16;                        // the LDS-resident part of the LSTM weights: 96 KB
-#define XLAUNCH(U_, X_) do { \
-        static bool attr_done = false; \
-        if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_fwd_kernel<NB, U_, X_>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; } \
-        hipLaunchKernelGGL((xdec_fwd_kernel<NB, U_, X_>), dim3(256), dim3(512), DYN, st, p); } while (0)
     (void)att_u;
-    if (p.att_exp) XLAUNCH(4, true); else XLAUNCH(4, false);
-#undef XLAUNCH
-    return (int)hipGetLastError();
+    return p.att_exp ? xdec_launch<xdec_fwd_kernel<NB, 4, true>>(p, st) : xdec_launch<xdec_fwd_kernel<NB, 4, false>>(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------ greedy-decode chain ----
@@ -821,68 +936,38 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
     __shared__ int ids_l[8], unf_l[8];
     __shared__ int s_rank, s_dead, s_stop;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r16 = lane & 15, g4 = lane >> 4;
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7u;
-    unsigned* xsync = p.sync + xcc * 64;
-    unsigned* err = p.sync + 8 * 64;
-    if (tid == 0) { s_dead = 0; s_stop = 0; s_rank = (int)atomicAdd(xsync + 32, 1u); }
+    XChain c = xchain_ticket(p.sync, NB, &s_rank, &s_dead);
+    const int tid = c.tid, lane = c.lane, wave = c.wave, r16 = c.r16, g4 = c.g4;
+    if (tid == 0) s_stop = 0;
     for (int i = tid; i < 8 * (XC + 8); i += 512) (&actx[0][0])[i] = 0;
     __syncthreads();
-    const int rank = s_rank;
-    if (rank >= 32) { if (tid == 0) { *reinterpret_cast<volatile unsigned*>(err) = 2u; *reinterpret_cast<volatile int*>(p.stop) = 1; } return; }
+    if (!xchain_rank(c, &s_rank)) { if (tid == 0) *reinterpret_cast<volatile int*>(p.stop) = 1; return; }
+    const int rank = c.rank, b0 = c.b0, u0 = rank * 16, v0 = rank * 16;
+    const unsigned xcc = c.xcc;                                  // (the LXO_TEST_DEC_FAULT build names it)
+    unsigned* xsync = c.xsync; unsigned* err = c.err;
     const int B = p.B, T = p.nsteps;
-    const int b0 = (int)xcc * NB;
-    const int u0 = rank * 16, e0 = rank * 8, o0 = rank * 16, v0 = rank * 16;
     // the decode is over (an earlier launch saw every row finished): a speculative launch has nothing to do.  Every workgroup reads the same
     // word, written before this kernel started.
     if (*reinterpret_cast<volatile const int*>(p.stop) != 0) return;
 
-#define P1K(ks) ((ks) < 2 ? wave * 64 + (ks) * 32 : XO + wave * 64 + ((ks) - 2) * 32)
     u32x4 wrt0[4], wow[4];
     u32x4* wl = reinterpret_cast<u32x4*>(xdec_dyn_lds) + (wave * 12) * 64 + lane;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const u32x4 w = *reinterpret_cast<const u32x4*>(p.Wrt + (long long)(q * XU + u0 + r16) * p.ldrt + P1K(ks) + g4 * 8);
-            if (q == 0) wrt0[ks] = w; else wl[((q - 1) * 4 + ks) * 64] = w;
-        }
+    float bt[4];
+    xdec_resident<true>(p, c, wrt0, wl, wahs, wow, bt);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-        const u32x4 w = *reinterpret_cast<const u32x4*>(p.Wah + (long long)(e0 + (r16 & 7)) * p.ldah + wave * 64 + ks * 32 + g4 * 8);
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        wahs[wave][ks][lane] = r16 < 8 ? w : z;
         // y_W_o rows v0 .. v0 + 15 (rows >= V: zeros, their logits are masked anyway), this wave's k range = P1's first two k-steps (o)
         const int vr = v0 + r16;
         const u32x4 y = *reinterpret_cast<const u32x4*>(p.Wyo + (long long)min(vr, p.V - 1) * p.ldyo + wave * 64 + ks * 32 + g4 * 8);
+        const u32x4 z = {0u, 0u, 0u, 0u};
         wyos[wave][ks][lane] = vr < p.V ? y : z;
     }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-        wow[ks] = *reinterpret_cast<const u32x4*>(p.Wow + (long long)(o0 + r16) * p.ldow + wave * 128 + ks * 32 + g4 * 8);
-    float bt[4];
-    { const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.beta + lane * 4); bt[0] = -2.f * b4[0]; bt[1] = -2.f * b4[1]; bt[2] = -2.f * b4[2]; bt[3] = -2.f * b4[3]; }
     if (tid < NB * 16) cst[tid >> 4][tid & 15] = p.cs[((long long)(p.t0 & 1) * B + b0 + (tid >> 4)) * XU + u0 + (tid & 15)];
 
-    const int as = rank / NQ, aq = rank - as * NQ;
-    const int ab = b0 + as;
-    const int rows_per = (p.R + NQ - 1) / NQ;
-    const int ar0 = aq * rows_per;
-    const int an = min(p.R, ar0 + rows_per) - ar0;
-    const bf16_t* ai = p.att_exp + ((long long)ab * p.R + ar0) * XE;
-    const bf16_t* im = p.img + ((long long)ab * p.R + ar0) * XC;
-    float* pout = p.part + ((long long)ab * NQ + aq) * PST;
-    const int arow = min(r16, NB - 1);
-    const int nblk = an > 0 ? (an + XW * ATT_U - 1) / (XW * ATT_U) : 0;
-    const int anq = an > 0 ? an : 1;
-    const rsrc_t imq = make_rsrc(an > 0 ? im : p.img, (unsigned)anq * XC * 2u);
-    const rsrc_t aiq = make_rsrc(an > 0 ? ai : p.att_exp, (unsigned)anq * XE * 2u);
+    const XRole<ATT_U> ro = xdec_role<NB, ATT_U>(c, p.R, p.img, p.att_exp);
     u32x4 xiA[ATT_U], xiB[ATT_U]; u32x2 xaA[ATT_U], xaB[ATT_U];
-    att_load<ATT_U>(xiA, xaA, imq, aiq, wave + XW * ATT_U * ((p.t0 & 1) ? nblk - 1 : 0), anq, lane);
-    att_load<ATT_U>(xiB, xaB, imq, aiq, wave + XW * ATT_U * ((p.t0 & 1) ? nblk - 2 : 1), anq, lane);
+    att_load<ATT_U>(xiA, xaA, ro.imq, ro.aiq, ro.XBASE(0, p.t0 & 1), ro.anq, lane);
+    att_load<ATT_U>(xiB, xaB, ro.imq, ro.aiq, ro.XBASE(1, p.t0 & 1), ro.anq, lane);
 
     unsigned* ll_ah = p.sync + kXDecSyncBytes / 4 + kLLFwdAh / 4;
     unsigned* ll_ht = p.sync + kXDecSyncBytes / 4 + kLLFwdHt / 4;
@@ -918,22 +1003,8 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
         const long long sp = (long long)(tg & 1) * B, sn = (long long)((tg + 1) & 1) * B;
         // =========================== boundary (logits, arg-max of step t - 1) + P1: LSTM cell ===========================
         {
-            const rsrc_t rp = make_rsrc(p.recb + sp * p.RECB, (unsigned)B * p.RECB * 2u);
             u32x4 a[4];
-            if (t > 0) {
-#pragma unroll
-                for (int ks = 2; ks < 4; ++ks) a[ks] = l2_load16(rp, (unsigned)(((b0 + arow) * p.RECB + P1K(ks) + g4 * 8) * 2));
-                u32x4 w[4];
-                unsigned off[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) off[j] = (unsigned)(((b0 + arow) * 256 + ((P1K(j >> 1) + g4 * 8) >> 1)) * 8 + (j & 1) * 16);
-                ll_wait<4>(w, rll_o, off, (unsigned)t, err, &s_dead);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) a[ks] = u32x4{w[2 * ks][0], w[2 * ks][2], w[2 * ks + 1][0], w[2 * ks + 1][2]};
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) a[ks] = l2_load16(rp, (unsigned)(((b0 + arow) * p.RECB + P1K(ks) + g4 * 8) * 2));
-            }
+            xdec_p1_fetch(a, p, c, sp, t > 0, rll_o, (unsigned)t);
             v4f acc[4], accl = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[q] = v4f{0.f, 0.f, 0.f, 0.f};
@@ -1076,17 +1147,10 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
                 float g[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) g[q] = zr[q * XU];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float z = g[q];
-#pragma unroll
-                    for (int w = 0; w < XW; ++w) z += red[w][erow][q * 16 + eu];
-                    g[q] = (q == 1) ? tanh_x(z) : sigm_x(q == 2 ? z + 1.0f : z);
-                }
-                const float c = g[2] * cst[erow][eu] + g[0] * g[1];
-                const float h = g[3] * tanh_x(c);
-                cst[erow][eu] = c;
-                p.cs[(sn + bb) * XU + u] = c;
+                float cn, h;
+                xdec_lstm(g, red, erow, eu, cst[erow][eu], cn, h);
+                cst[erow][eu] = cn;
+                p.cs[(sn + bb) * XU + u] = cn;
                 float* rr = p.rec + (sn + bb) * p.REC;
                 bf16_t* rb = p.recb + (sn + bb) * p.RECB;
                 rr[OFF_H + u] = h; rr[OFF_HT + u] = h;
@@ -1098,97 +1162,16 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
         }
         __syncthreads();
         // =========================== P2: att_h = h~ W ===========================
-        const rsrc_t rn = make_rsrc(p.recb + sn * p.RECB, (unsigned)B * p.RECB * 2u);
-        {
-            u32x4 a[2];
-            u32x4 w[4];
-            unsigned off[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) off[j] = (unsigned)(((b0 + arow) * 256 + ((wave * 64 + (j >> 1) * 32 + g4 * 8) >> 1)) * 8 + (j & 1) * 16);
-            ll_wait<4>(w, rll_ht, off, (unsigned)(t + 1), err, &s_dead);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) a[ks] = u32x4{w[2 * ks][0], w[2 * ks][2], w[2 * ks + 1][0], w[2 * ks + 1][2]};
-            v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) acc = mfma16(a[ks], wahs[wave][ks][lane], acc);
-            if (g4 * 4 < NB) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[wave][g4 * 4 + i][r16] = acc[i];
-            }
-            __syncthreads();
-            if (tid < NB * 8) {
-                const int row = tid >> 3, e = tid & 7;
-                float v = 0.f;
-#pragma unroll
-                for (int w2 = 0; w2 < XW; ++w2) v += red[w2][row][e];
-                const u32x2 wv = {__float_as_uint(v), (unsigned)(t + 1)};
-                *reinterpret_cast<u32x2*>(ll_ah + ((b0 + row) * XE + e0 + e) * 2) = wv;
-            }
-        }
+        xdec_p2<NB, true, false>(p, c, sp, sn, t, rll_ht, ll_ah, red, wahs);
         // =========================== P3: attention chunk ===========================
         {
-            u32x4 aw[2];
-            { const unsigned off[2] = {(unsigned)((ab * XE + lane * 4) * 8), (unsigned)((ab * XE + lane * 4) * 8 + 16)}; ll_wait<2>(aw, rll_ah, off, (unsigned)(t + 1), err, &s_dead); }
             float ah[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ah[j] = __builtin_amdgcn_exp2f(fminf(fmaxf(__uint_as_float(aw[j >> 1][(j & 1) * 2]) * 2.8853900817779268f, -60.f), 60.f));
-            const int c0 = lane * 8;
+            xdec_att_h<true>(ah, c, ro.ab, rll_ah, (unsigned)(t + 1));
             float m = -3.0e38f, l = 0.f, acc[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-            const int rev = tg & 1;
-#define XBASE(i, rv) (wave + XW * ATT_U * ((rv) ? nblk - 1 - (i) : (i)))
-            for (int it = 0; it < nblk; it += 2) {
-                att_block<ATT_U, true>(xiA, xaA, XBASE(it, rev), an, ah, bt, m, l, acc, nullptr, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                att_load<ATT_U>(xiA, xaA, imq, aiq, (it + 2 < nblk) ? XBASE(it + 2, rev) : XBASE(0, rev ^ 1), anq, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                if (it + 1 < nblk) {
-                    att_block<ATT_U, true>(xiB, xaB, XBASE(it + 1, rev), an, ah, bt, m, l, acc, nullptr, lane);
-                    __builtin_amdgcn_sched_barrier(0);
-                    att_load<ATT_U>(xiB, xaB, imq, aiq, (it + 3 < nblk) ? XBASE(it + 3, rev) : XBASE(1, rev ^ 1), anq, lane);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#undef XBASE
-            if (lane == 0) wred[wave] = m;
-            __syncthreads();
-            float mc = wred[0];
-#pragma unroll
-            for (int w = 1; w < XW; ++w) mc = fmaxf(mc, wred[w]);
-            const float sw = (l > 0.f) ? __expf(m - mc) : 0.f;
-            if (lane == 0) wred[XW + wave] = l * sw;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) redc[wave][c0 + e] = acc[e] * sw;
-            __syncthreads();
-            if constexpr (PP) {
-                unsigned* pw = reinterpret_cast<unsigned*>(p.part) + ((long long)ab * NQ + aq) * (PLW * 2);
-                if (tid == 0) {
-                    float lt = 0.f;
-#pragma unroll
-                    for (int w = 0; w < XW; ++w) lt += wred[XW + w];
-                    const u32x4 st4 = {__float_as_uint(mc), (unsigned)(t + 1), __float_as_uint(lt), (unsigned)(t + 1)};
-                    *reinterpret_cast<u32x4*>(pw + 256 * 2) = st4;
-                }
-                float tsum = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) tsum += redc[w][tid];
-                const float other = __shfl_xor(tsum, 1);
-                if (!(tid & 1)) *reinterpret_cast<u32x2*>(pw + (tid >> 1) * 2) = pack28(tsum, other, tag8_of(t));
-            } else {
-            if (tid == 0) {
-                float lt = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) lt += wred[XW + w];
-                pout[XC] = mc; pout[XC + 1] = lt;
-            }
-            {
-                float tsum = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) tsum += redc[w][tid];
-                pout[tid] = tsum;
-            }
-            }
+            xdec_walk<ATT_U, true>(xiA, xaA, xiB, xaB, ro, tg & 1, ah, bt, m, l, acc, nullptr, lane);      // (no raw scores: the decode keeps no alpha)
+            xdec_p3_publish<NQ, PP>(m, l, acc, c, ro.ab, ro.aq, t, p.part, wred, redc);
         }
         if constexpr (!PP) xbar(xsync, rank, ++ph, err, &s_dead);
 #ifdef LXO_TEST_DEC_FAULT          // diagnostic build only (never in liblxo.so): chain 3 declares itself broken in step 21 -- profiles/r05_dec_fault_fallback.txt
@@ -1196,164 +1179,21 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
 #endif
         // =========================== P4: merge the chunks; ctx; o projection ===========================
         {
-            const rsrc_t rpart = PP ? make_rsrc(reinterpret_cast<const unsigned*>(p.part) + (long long)b0 * NQ * (PLW * 2), (unsigned)(NB * NQ * PLW) * 8u)
-                                    : make_rsrc(p.part + (long long)b0 * NQ * PST, (unsigned)(NB * NQ * PST) * 4u);
             u32x4 a[4];
-            if (wave < 4) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) a[ks] = l2_load16(rn, (unsigned)(((b0 + arow) * p.RECB + OFF_HT + wave * 128 + ks * 32 + g4 * 8) * 2));
-            }
-            constexpr int SPG = NB >= 4 ? NB / 4 : 1, NG = NB / SPG;
-            // chains of one or two samples: the 32 / 16 chunk partials of a sample are split over the 4 / 2 thread groups (8 chunks each = two rounds of
-            // four requests; one group per sample walked them in eight / four dependent rounds: P4 5.6 us of a 12.2 us step at B = 8) and the groups' sums meet in LDS
-            constexpr int GPS = NB >= 4 ? 1 : 4 / NB, CPG = NQ / GPS;
-            const int tg4 = tid >> 7, c4 = (tid & 127) * 4;
-            const int gsm = tg4 / GPS, cb = (tg4 - gsm * GPS) * CPG;      // this thread group's sample (block) and first chunk
-            constexpr int QG = NB >= 4 ? 2 : 4;
-            u32x4 pc[SPG][QG];
-            float st_m = 0.f, st_l = 0.f;                       // wave 0: {max, sum} of (sample, chunk) = lane (lanes 32 .. 63 repeat lane 31's)
-            if constexpr (PP) {
-                if (wave == 0) {
-                    u32x4 w1[1];
-                    const unsigned off1[1] = {(unsigned)((min(tid, NB * NQ - 1) * PLW + 256) * 8)};
-                    ll_wait<1>(w1, rpart, off1, (unsigned)(t + 1), err, &s_dead);
-                    st_m = __uint_as_float(w1[0][0]); st_l = __uint_as_float(w1[0][2]);
-                }
-                if (gsm < NG) {
-                    u32x4 wq[SPG * QG];
-                    unsigned offq[SPG * QG];
-#pragma unroll
-                    for (int si = 0; si < SPG; ++si)
-#pragma unroll
-                        for (int q = 0; q < QG; ++q) offq[si * QG + q] = (unsigned)((((gsm * SPG + si) * NQ + cb + q) * PLW + (c4 >> 1)) * 8);
-                    ll_wait8<SPG * QG>(wq, rpart, offq, tag8_of(t), err, &s_dead);
-#pragma unroll
-                    for (int si = 0; si < SPG; ++si)
-#pragma unroll
-                        for (int q = 0; q < QG; ++q) pc[si][q] = wq[si * QG + q];
-                }
-            } else {
-            if (gsm < NG) {
-#pragma unroll
-                for (int si = 0; si < SPG; ++si)
-#pragma unroll
-                    for (int q = 0; q < QG; ++q) pc[si][q] = l2_load16(rpart, (unsigned)((((gsm * SPG + si) * NQ + cb + q) * PST + c4) * 4));
-            }
-            if (wave == 0) {
-                const unsigned o = (unsigned)((min(tid, NB * NQ - 1) * PST + XC) * 4);
-                st_m = l2_load4(rpart, o); st_l = l2_load4(rpart, o + 4);
-            }
-            }
-            // softmax over the chunks of a sample, one lane per (sample, chunk) -- NB * NQ = 32 lanes of wave 0, log2(NQ) exchange rounds (one thread per
-            // sample walked its NQ chunks three times: ~2 us of serial code per step at NQ = 32, the chains of one sample)
-            if (wave == 0) {
-                float mm = st_l > 0.f ? st_m : -3.0e38f;
-#pragma unroll
-                for (int o = NQ / 2; o > 0; o >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o));
-                const float w = st_l > 0.f ? __expf(st_m - mm) : 0.f;
-                float ll = st_l * w;
-#pragma unroll
-                for (int o = NQ / 2; o > 0; o >>= 1) ll += __shfl_xor(ll, o);
-                const float inv = 1.0f / ll;
-                if (tid < NB * NQ) {
-                    (&wgt[0][0])[tid] = w * inv;
-                }
-            }
+            xdec_o_fetch(a, p, c, sn);
+            xdec_p4_merge<NB, PP, false>(p, c, sn, t, wgt, nullptr, nullptr, redc, actx, nullptr);
             __syncthreads();
-            if (gsm < NG) {
-#pragma unroll
-                for (int si = 0; si < SPG; ++si) {
-                    const int sidx = gsm * SPG + si;
-                    float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int q0 = 0; q0 < CPG; q0 += QG) {
-#pragma unroll
-                        for (int q = 0; q < QG; ++q) {
-                            const float w = wgt[sidx][cb + q0 + q];
-                            if constexpr (PP) {
-                                v[0] = fmaf(unpack28_lo(pc[si][q][0]), w, v[0]); v[1] = fmaf(unpack28_hi(pc[si][q][0], pc[si][q][1]), w, v[1]);
-                                v[2] = fmaf(unpack28_lo(pc[si][q][2]), w, v[2]); v[3] = fmaf(unpack28_hi(pc[si][q][2], pc[si][q][3]), w, v[3]);
-                            } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaf(__uint_as_float(pc[si][q][e]), w, v[e]);
-                            }
-                        }
-                        if (q0 + QG < CPG) {
-                            if constexpr (PP) {
-                                u32x4 wq[QG];
-                                unsigned offq[QG];
-#pragma unroll
-                                for (int q = 0; q < QG; ++q) offq[q] = (unsigned)(((sidx * NQ + cb + q0 + QG + q) * PLW + (c4 >> 1)) * 8);
-                                ll_wait8<QG>(wq, rpart, offq, tag8_of(t), err, &s_dead);
-#pragma unroll
-                                for (int q = 0; q < QG; ++q) pc[si][q] = wq[q];
-                            } else {
-#pragma unroll
-                            for (int q = 0; q < QG; ++q) pc[si][q] = l2_load16(rpart, (unsigned)(((sidx * NQ + cb + q0 + QG + q) * PST + c4) * 4));
-                            }
-                        }
-                    }
-                    if constexpr (GPS > 1) {                      // the groups of a sample meet in LDS (the waves' partial-context buffer of P3 is free here)
-                        *reinterpret_cast<f32x4*>(&redc[tg4][c4]) = f32x4{v[0], v[1], v[2], v[3]};
-                        __syncthreads();
-                        if (cb == 0) {
-#pragma unroll
-                            for (int g = 1; g < GPS; ++g) { const f32x4 o4 = *reinterpret_cast<const f32x4*>(&redc[tg4 + g][c4]); v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3]; }
-                        }
-                    }
-                    if (GPS > 1 && cb != 0) continue;
-                    const u32x2 vb = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-                    *reinterpret_cast<u32x2*>(&actx[sidx][c4]) = vb;
-                    if ((c4 >> 4) == rank) {
-                        const f32x4 vf = {v[0], v[1], v[2], v[3]};
-                        *reinterpret_cast<f32x4*>(p.rec + (sn + b0 + sidx) * p.REC + OFF_CTX + c4) = vf;
-                        *reinterpret_cast<u32x2*>(p.recb + (sn + b0 + sidx) * p.RECB + OFF_CTX + c4) = vb;
-                    }
-                }
-            }
-            __syncthreads();
-            if (wave >= 4) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const u32x4*>(&actx[arow][(wave - 4) * 128 + ks * 32 + g4 * 8]);
-            }
-            v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) acc = mfma16(a[ks], wow[ks], acc);
-            if (g4 * 4 < NB) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[wave][g4 * 4 + i][r16] = acc[i];
-            }
-            __syncthreads();
-            if (tid < NB * 16) {
-                const int row = tid >> 4, cc = tid & 15;
-                float v = 0.f;
-#pragma unroll
-                for (int w = 0; w < XW; ++w) v += red[w][row][cc];
-                const int bb = b0 + row, n = o0 + cc;
-                v = tanh_x(v);
-                p.rec[(sn + bb) * p.REC + n] = v;
-                const bf16_t vb = f2bf(v);
-                p.recb[(sn + bb) * p.RECB + n] = vb;
-                const unsigned mine = (unsigned)vb, other = (unsigned)__shfl_xor((int)mine, 1);
-                if (!(cc & 1)) { const u32x2 wv = {mine | (other << 16), (unsigned)(t + 1)}; *reinterpret_cast<u32x2*>(ll_o + ((bb * 256 + (n >> 1)) * 2)) = wv; }
-            }
+            xdec_o_proj<NB, 8>(a, p, c, sn, t, nullptr, wow, actx, red, ll_o);
         }
         __syncthreads();
     }
-#undef P1K
     // a hand-over that timed out: the ids are garbage from here on; later launches of this decode return at once, the host reads the error word
     // (which the launcher leaves alone: it is cleared once per decode) and repeats the decode on the launch-per-step kernels
     if (tid == 0 && s_dead) *reinterpret_cast<volatile int*>(p.stop) = 1;
 }
 
 template <int NB, bool SC, bool PF, bool AL>
-int launch_dec_sc(const XDecDec& p, hipStream_t st) {
-    constexpr int DYN = XW * 12 * 64 * 16;
-    static bool attr_done = false;
-    if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_dec_kernel<NB, SC, PF, AL>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; }
-    hipLaunchKernelGGL((xdec_dec_kernel<NB, SC, PF, AL>), dim3(256), dim3(512), DYN, st, p);
-    return (int)hipGetLastError();
-}
+int launch_dec_sc(const XDecDec& p, hipStream_t st) { return xdec_launch<xdec_dec_kernel<NB, SC, PF, AL>>(p, st); }
 template <int NB, bool PF, bool AL>
 int launch_dec_pf(const XDecDec& p, hipStream_t st) { return p.logp_out ? launch_dec_sc<NB, true, PF, AL>(p, st) : launch_dec_sc<NB, false, PF, AL>(p, st); }
 template <int NB, bool AL>
@@ -1426,22 +1266,16 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
     __shared__ float cst[8][16];                                 // d_c of this workgroup's 16 units (lives here for all T steps)
     __shared__ int s_rank, s_dead;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r16 = lane & 15, g4 = lane >> 4;
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7u;
-    unsigned* xsync = p.sync + xcc * 64;
-    unsigned* err = p.sync + 8 * 64;
-    if (tid == 0) { s_dead = 0; s_rank = (int)atomicAdd(xsync + 32, 1u); }
+    XChain c = xchain_ticket(p.sync, NB, &s_rank, &s_dead);
+    const int tid = c.tid, lane = c.lane, wave = c.wave, r16 = c.r16, g4 = c.g4;
     for (int i = tid; i < 16 * (XE + 8); i += 512) (&adh[0][0])[i] = 0;      // rows >= NB of the A tile stay zero
     if (tid < 128) (&cst[0][0])[tid] = 0.f;
     __syncthreads();
-    const int rank = s_rank;
-    if (rank >= 32) { if (tid == 0) *reinterpret_cast<volatile unsigned*>(err) = 2u; return; }
+    if (!xchain_rank(c, &s_rank)) return;
+    const int rank = c.rank, b0 = c.b0, arow = c.arow, u0 = rank * 16, n0 = rank * 32;
+    const unsigned xcc = c.xcc;
+    unsigned* xsync = c.xsync; unsigned* err = c.err;
     const int B = p.B, T = p.T;
-    const int b0 = (int)xcc * NB;
-    const int u0 = rank * 16, n0 = rank * 32;
 
     // ---- resident weights (MFMA B fragments: lane = (output column r16, k group g4)) ----
     u32x4 wow[2][2], wahb, wk0[4];
@@ -1464,26 +1298,17 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
     { const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.beta + lane * 4); bt[0] = b4[0]; bt[1] = b4[1]; bt[2] = b4[2]; bt[3] = b4[3]; }
 
     // attention role of this workgroup (as in the forward chain)
-    const int as = rank / NQ, aq = rank - as * NQ;
-    const int ab = b0 + as;
-    const int rows_per = (p.R + NQ - 1) / NQ;
-    const int ar0 = aq * rows_per;
-    const int an = min(p.R, ar0 + rows_per) - ar0;
-    const int arow = min(r16, NB - 1);
+    const XRole<ATT_U> ro = xdec_role<NB, ATT_U>(c, p.R, p.img, EXPD ? p.att_exp : p.att_img);
+    const int ab = ro.ab, aq = ro.aq, ar0 = ro.ar0, an = ro.an, nblk = ro.nblk, anq = ro.anq;
+    const rsrc_t imq = ro.imq, aiq = ro.aiq;
     Drop dr = p.dr;
     unsigned ph = 0;
-    const int nblk = an > 0 ? (an + XW * ATT_U - 1) / (XW * ATT_U) : 0;
-    const int anq = an > 0 ? an : 1;
-    const bf16_t* aibase = EXPD ? p.att_exp : p.att_img;
-    const rsrc_t imq = make_rsrc(an > 0 ? p.img + ((long long)ab * p.R + ar0) * XC : p.img, (unsigned)anq * XC * 2u);
-    const rsrc_t aiq = make_rsrc(an > 0 ? aibase + ((long long)ab * p.R + ar0) * XE : aibase, (unsigned)anq * XE * 2u);
     const long long al_off = an > 0 ? (long long)ab * p.Rp + ar0 : 0;     // + t * B * Rp: this chunk's alpha rows of step t
-#define XBASE(i, rv) (wave + XW * ATT_U * ((rv) ? nblk - 1 - (i) : (i)))
     u32x4 xiA[ATT_U], xiB[ATT_U]; u32x2 xaA[ATT_U], xaB[ATT_U]; float alA[ATT_U], alB[ATT_U];
     {
         const rsrc_t ral = make_rsrc(p.alpha + (long long)(T - 1) * B * p.Rp + al_off, (unsigned)anq * 4u);
-        attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ral, XBASE(0, (T - 1) & 1), anq, lane);
-        attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, ral, XBASE(1, (T - 1) & 1), anq, lane);
+        attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ral, ro.XBASE(0, (T - 1) & 1), anq, lane);
+        attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, ral, ro.XBASE(1, (T - 1) & 1), anq, lane);
     }
     // forward values the phases of a step need, requested a few phases ahead (they come from HBM): this lane's 8 channels of ctx_t and
     // 4 columns of att_h_t (Q2); gates, c_t, c_{t-1} of this thread's LSTM element (Q3); d_o(logits) and o of step t-1 (Q4)
@@ -1503,7 +1328,6 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
     const rsrc_t rll_gb = make_rsrc(ll_gb, (unsigned)B * 256u * 8u);
     const rsrc_t rll_dc = make_rsrc(ll_dc, (unsigned)B * XC * 8u);
     unsigned long long* dbg = p.dbg ? p.dbg + ((long long)(xcc * 32 + rank) * T) * 16 : nullptr;
-#define XSTAMP(i) do { if (dbg && tid == 0) dbg[(T - 1 - t) * 16 + (i)] = wall_clock64(); } while (0)
     // forward values the phases behind Q2 of step ts need (gates, c_ts, c_{ts-1}: Q3 of step ts; d_o(logits), o of step ts - 1: Q4) and the next
     // Q2's ctx / att_h (step ts - 1)
     auto fwd_values = [&](int ts) {
@@ -1530,7 +1354,7 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
     };
     for (int t = T - 1; t >= 0; --t) {
         dr.t = t;
-        XSTAMP(0);
+        XSTAMP(T - 1 - t, 0);
         const long long sp = (long long)t * B;
         const rsrc_t rdh = make_rsrc(p.dhc + sp * XHC, (unsigned)B * XHC * 4u);
         // =========================== Q1: [d_h~ | d_ctx] = g o_W^T ===========================
@@ -1571,9 +1395,9 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
                 }
             }
         }
-        XSTAMP(1);
+        XSTAMP(T - 1 - t, 1);
         if (!(kLLB & 2)) xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(2);
+        XSTAMP(T - 1 - t, 2);
         // =========================== Q2: attention stream ===========================
         {
             float dc[8], ah[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1607,14 +1431,14 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
             if constexpr (kPFB == 0) {
             for (int it = 0; it < nblk; it += 2) {
                 const bool moreA = it + 2 < nblk, moreB = it + 3 < nblk;
-                attb_block<ATT_U, EXPD>(xiA, xaA, alA, XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
+                attb_block<ATT_U, EXPD>(xiA, xaA, alA, ro.XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
                 __builtin_amdgcn_sched_barrier(0);
-                attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, moreA ? ral : raln, moreA ? XBASE(it + 2, rev) : XBASE(0, rev ^ 1), anq, lane);
+                attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, moreA ? ral : raln, moreA ? ro.XBASE(it + 2, rev) : ro.XBASE(0, rev ^ 1), anq, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 if (it + 1 < nblk) {                              // (an odd block count ends on an A half: B already holds the next step's block 1)
-                    attb_block<ATT_U, EXPD>(xiB, xaB, alB, XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
+                    attb_block<ATT_U, EXPD>(xiB, xaB, alB, ro.XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
                     __builtin_amdgcn_sched_barrier(0);
-                    attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, moreB ? ral : raln, moreB ? XBASE(it + 3, rev) : XBASE(1, rev ^ 1), anq, lane);
+                    attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, moreB ? ral : raln, moreB ? ro.XBASE(it + 3, rev) : ro.XBASE(1, rev ^ 1), anq, lane);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -1622,20 +1446,20 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
             // the chunk ends with nothing in flight (kPFB: the next step's first blocks are requested in Q3 / Q4); peeled as in the forward chain
             int it = 0;
             for (; it + 3 < nblk; it += 2) {
-                attb_block<ATT_U, EXPD>(xiA, xaA, alA, XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
+                attb_block<ATT_U, EXPD>(xiA, xaA, alA, ro.XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
                 __builtin_amdgcn_sched_barrier(0);
-                attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ral, XBASE(it + 2, rev), anq, lane);
+                attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ral, ro.XBASE(it + 2, rev), anq, lane);
                 __builtin_amdgcn_sched_barrier(0);
-                attb_block<ATT_U, EXPD>(xiB, xaB, alB, XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
+                attb_block<ATT_U, EXPD>(xiB, xaB, alB, ro.XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
                 __builtin_amdgcn_sched_barrier(0);
-                attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, ral, XBASE(it + 3, rev), anq, lane);
+                attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, ral, ro.XBASE(it + 3, rev), anq, lane);
                 __builtin_amdgcn_sched_barrier(0);
             }
             const int rem = nblk - it;
-            if (rem >= 1) attb_block<ATT_U, EXPD>(xiA, xaA, alA, XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
-            if (rem == 3) { __builtin_amdgcn_sched_barrier(0); attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ral, XBASE(it + 2, rev), anq, lane); __builtin_amdgcn_sched_barrier(0); }
-            if (rem >= 2) attb_block<ATT_U, EXPD>(xiB, xaB, alB, XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
-            if (rem == 3) attb_block<ATT_U, EXPD>(xiA, xaA, alA, XBASE(it + 2, rev), an, dc, ah, s, acc, de_row, lane);
+            if (rem >= 1) attb_block<ATT_U, EXPD>(xiA, xaA, alA, ro.XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
+            if (rem == 3) { __builtin_amdgcn_sched_barrier(0); attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ral, ro.XBASE(it + 2, rev), anq, lane); __builtin_amdgcn_sched_barrier(0); }
+            if (rem >= 2) attb_block<ATT_U, EXPD>(xiB, xaB, alB, ro.XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
+            if (rem == 3) attb_block<ATT_U, EXPD>(xiA, xaA, alA, ro.XBASE(it + 2, rev), an, dc, ah, s, acc, de_row, lane);
             }
             // forward values of the coming phases (unconditional, clamped indices)
             fwd_values(t);
@@ -1653,13 +1477,13 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
                 } else p.part[((long long)ab * NQ + aq) * XE + tid] = v;
             }
         }
-        XSTAMP(3);
+        XSTAMP(T - 1 - t, 3);
         // (kLLB & 4: no barrier here.  Q3 also reads d_h~ (Q1 of other workgroups) and the carried d_h (Q4 of the previous step): both were stored in front of a
         // workgroup barrier -- on gfx950 a wait for the store acknowledgements -- that their producers passed before they stored the partial / d_ctx words Q3's
         // and Q2's polls have seen; and nobody rewrites the partial words of this step before every workgroup has read them: the next Q2 needs d_ctx of
         // workgroups that are past this step's Q3.)
         if constexpr (!(kLLB & 4)) xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(4);
+        XSTAMP(T - 1 - t, 4);
         // =========================== Q3: d_att_h; d_h; LSTM cell backward ===========================
         {
             const rsrc_t rpart = make_rsrc(p.part + (long long)b0 * NQ * XE, (unsigned)(NB * NQ * XE) * 4u);      // (kLLB & 4: 128 pack28 words per partial = the same kilobyte)
@@ -1672,7 +1496,7 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) off[j] = (unsigned)((((srow * NQ + sqg * 4 + j) * (XE / 2)) + lane * 2) * 8);
                 ll_wait8<4>(pc, rpart, off, tag8_of(t), err, &s_dead);
-                XSTAMP(12);                                       // measurement only: the polled d_att_h partials have arrived
+                XSTAMP(T - 1 - t, 12);                                       // measurement only: the polled d_att_h partials have arrived
             } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) pc[j] = l2_load16(rpart, (unsigned)((((srow * NQ + sqg * 4 + j) * XE) + lane * 4) * 4));
@@ -1737,9 +1561,9 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
                 db[0] = f2bf(dzi); db[XU] = f2bf(dzj); db[2 * XU] = f2bf(dzf); db[3 * XU] = f2bf(dzo);
             }
         }
-        XSTAMP(5);
+        XSTAMP(T - 1 - t, 5);
         xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(6);
+        XSTAMP(T - 1 - t, 6);
         // =========================== Q4: carries = d_z K[D:]^T; g_{t-1} ===========================
         {
             const rsrc_t rdz = make_rsrc(p.dzb + sp * p.DZBP, (unsigned)B * p.DZBP * 2u);
@@ -1782,52 +1606,52 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
                 } else p.carry_h[(long long)bb * XU + (n - XO)] = v;
             }
         }
-        XSTAMP(7);
+        XSTAMP(T - 1 - t, 7);
         if (kLLB & 1) __syncthreads();                           // (the partial tiles in LDS are rewritten by the next step's Q1)
         else xbar(xsync, rank, ++ph, err, &s_dead);
-        XSTAMP(8);
+        XSTAMP(T - 1 - t, 8);
     }
-#undef XSTAMP
-#undef XBASE
     if (tid < NB * 16) p.dcc[(long long)(b0 + e3r) * XU + u0 + e3u] = cst[e3r][e3u];
 }
 
 template <int NB>
 int launch_bwd_nb(const XDecBwd& p, hipStream_t st) {
-    constexpr int DYN = XW * 12 * 64 * 16;
-#define XLAUNCH(X_) do { \
-        static bool attr_done = false; \
-        if (!attr_done) { HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(xdec_bwd_kernel<NB, 4, X_>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN)); attr_done = true; } \
-        hipLaunchKernelGGL((xdec_bwd_kernel<NB, 4, X_>), dim3(256), dim3(512), DYN, st, p); } while (0)
-    if (p.att_exp) XLAUNCH(true); else XLAUNCH(false);
-#undef XLAUNCH
-    return (int)hipGetLastError();
+    return p.att_exp ? xdec_launch<xdec_bwd_kernel<NB, 4, true>>(p, st) : xdec_launch<xdec_bwd_kernel<NB, 4, false>>(p, st);
 }
 }  // namespace
+
+// What the three launchers ask alike.  Returns NB = B / 8 (1, 2, 4 or 8), or 0: the shape does not qualify or the chain is switched off, and
+// the launcher answers -2.  `on` is the launcher's own cached switch: LXO_XDEC=0 sends everything to the launch-per-step kernels, the launcher's
+// `own` variable (null: none) set to 0 that chain alone (A/B runs).  Only the shipped sizes run here, in chains of 1, 2, 4 or 8 samples with
+// attention chunks of 1 .. rows_max rows, and the chain needs 8 XCDs x 32 CUs (MI355X).
+static int xdec_gate(int& on, const char* own, int U, int O, int C, int E, int B, int R, int rows_max) {
+    if (on < 0) { const char* e = own ? getenv(own) : nullptr; const char* f = getenv("LXO_XDEC"); on = ((e && e[0] == '0') || (f && f[0] == '0')) ? 0 : 1; }
+    if (!on) return 0;
+    if (U != XU || O != XO || C != XC || E != XE) return 0;
+    if (B % 8 != 0 || B > 64) return 0;
+    const int nb = B / 8;
+    if (nb != 1 && nb != 2 && nb != 4 && nb != 8) return 0;
+    const int nq = 32 / nb, rows_per = (R + nq - 1) / nq;
+    if (rows_per > rows_max || rows_per < 1) return 0;
+    static int dev_ok = -1;
+    if (dev_ok < 0) {
+        int dev = 0; hipDeviceProp_t pr;
+        dev_ok = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount == 256) ? 1 : 0;
+    }
+    return dev_ok ? nb : 0;
+}
 
 static thread_local unsigned long long* g_xdbg = nullptr;
 extern "C" int lxo_xdec_debug(unsigned long long* buf) { g_xdbg = buf; return 0; }
 int lxo_launch_xdec_fwd(const XDecFwd& p0, int U, int O, int C, int E, hipStream_t st) {
     XDecFwd p = p0;
     p.dbg = g_xdbg;
-    static int on = -1;                                          // LXO_XDEC=0: the launch-per-step chain everywhere (A/B runs)
-    if (on < 0) { const char* e = getenv("LXO_XDEC"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on) return -2;
-    if (U != XU || O != XO || C != XC || E != XE) return -2;
-    if (p.B % 8 != 0 || p.B > 64 || p.T < 1) return -2;
-    const int nb = p.B / 8;
-    if (nb != 1 && nb != 2 && nb != 4 && nb != 8) return -2;
-    const int nq = 32 / nb, rows_per = (p.R + nq - 1) / nq;
-    if (rows_per > SCMAX || rows_per < 1) return -2;
+    static int on = -1;
+    const int nb = xdec_gate(on, nullptr, U, O, C, E, p.B, p.R, SCMAX);       // (the raw scores of a chunk stay in LDS)
+    if (!nb || p.T < 1) return -2;
     if ((long long)p.B * p.RECB * 2 >= (1LL << 31) || p.ldrt % 8 || p.ldah % 8 || p.ldow % 8 || p.RECB % 8) return -2;
-    static int dev_ok = -1;                                      // the chain needs 8 XCDs x 32 CUs (MI355X); anything else: launch chain
-    if (dev_ok < 0) {
-        int dev = 0; hipDeviceProp_t pr;
-        dev_ok = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount == 256) ? 1 : 0;
-    }
-    if (!dev_ok) return -2;
     HIPRC(hipMemsetAsync(p.sync, 0, kXDecBlockBytes, st));
-    if (kLL & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * nq * PLW * 8, st));      // the polled chunk partials: no tag of an earlier launch may pass
+    if (kLL & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * (32 / nb) * PLW * 8, st));      // the polled chunk partials: no tag of an earlier launch may pass
 
     // rows per wave and block (two blocks in flight).  4: the largest count whose two blocks + the resident weights fit the register file
     // without spills (5 .. 7 spill 68 .. 208 bytes per lane into the serial phases and lose more there than their fewer padded rows gain:
@@ -1836,37 +1660,23 @@ int lxo_launch_xdec_fwd(const XDecFwd& p0, int U, int O, int C, int E, hipStream
     if (forced < 0) { const char* e = getenv("LXO_XDEC_U"); forced = e ? atoi(e) : 0; }
     int att_u = 4;
     if (forced >= 4 && forced <= 7) att_u = forced;
-    int rc;
     switch (nb) {
-    case 1: rc = launch_nb<1>(p, att_u, st); break;
-    case 2: rc = launch_nb<2>(p, att_u, st); break;
-    case 4: rc = launch_nb<4>(p, att_u, st); break;
-    default: rc = launch_nb<8>(p, att_u, st); break;
+    case 1: return launch_nb<1>(p, att_u, st);
+    case 2: return launch_nb<2>(p, att_u, st);
+    case 4: return launch_nb<4>(p, att_u, st);
+    default: return launch_nb<8>(p, att_u, st);
     }
-    return rc;
 }
 int lxo_launch_xdec_dec(const XDecDec& p, int U, int O, int C, int E, hipStream_t st) {
-    static int on = -1;                                          // LXO_XDEC_DEC=0: greedy decode on the launch-per-step kernels (A/B); LXO_XDEC=0 switches every chain off
-    if (on < 0) { const char* e = getenv("LXO_XDEC_DEC"); const char* f = getenv("LXO_XDEC"); on = ((e && e[0] == '0') || (f && f[0] == '0')) ? 0 : 1; }
-    if (!on) return -2;
-    if (U != XU || O != XO || C != XC || E != XE) return -2;
-    if (p.B % 8 != 0 || p.B > 64 || p.nsteps < 1 || p.nsteps > 16 || p.V < 1 || p.V > 512 || !p.stop) return -2;      // 32 workgroups x 16 vocabulary columns; one counter word per step and launch
-    const int nb = p.B / 8;
-    if (nb != 1 && nb != 2 && nb != 4 && nb != 8) return -2;
-    const int nq = 32 / nb, rows_per = (p.R + nq - 1) / nq;
-    if (rows_per < 1) return -2;
+    static int on = -1;
+    const int nb = xdec_gate(on, "LXO_XDEC_DEC", U, O, C, E, p.B, p.R, 1 << 30);     // (no raw scores are kept: any chunk length)
+    if (!nb || p.nsteps < 1 || p.nsteps > 16 || p.V < 1 || p.V > 512 || !p.stop) return -2;      // 32 workgroups x 16 vocabulary columns; one counter word per step and launch
     if ((long long)p.B * p.RECB * 2 >= (1LL << 31) || p.ldrt % 8 || p.ldah % 8 || p.ldow % 8 || p.ldyo % 8 || p.RECB % 8 || !p.att_exp) return -2;
-    static int dev_ok = -1;
-    if (dev_ok < 0) {
-        int dev = 0; hipDeviceProp_t pr;
-        dev_ok = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount == 256) ? 1 : 0;
-    }
-    if (!dev_ok) return -2;
     // tickets / flags and the hand-over area, but NOT the error word (int 512): an error of an earlier launch of this decode stays visible
     HIPRC(hipMemsetAsync(p.sync, 0, 8 * 64 * 4, st));
     HIPRC(hipMemsetAsync(p.sync + 8 * 64 + 1, 0, kXDecBlockBytes - (8 * 64 + 1) * 4, st));
     HIPRC(hipMemsetAsync(p.sync + kXDecBlockBytes / 4 + kXDecSyncBytes / 4, 0, (size_t)p.B * 32 * 8 * (p.logp_out ? (p.prefix ? 3 : 2) : 1), st));      // the arg-max words (block 1's hand-over area; + the exponential sums, + the forced logits)
-    if (kLL & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * nq * PLW * 8, st));               // the polled chunk partials (tags restart with every launch)
+    if (kLL & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * (32 / nb) * PLW * 8, st));               // the polled chunk partials (tags restart with every launch)
     switch (nb) {
     case 1: return launch_dec_nb<1>(p, st);
     case 2: return launch_dec_nb<2>(p, st);
@@ -1879,29 +1689,17 @@ extern "C" int lxo_xdec_debug_bwd(unsigned long long* buf) { g_xdbg_b = buf; ret
 int lxo_launch_xdec_bwd(const XDecBwd& p0, int U, int O, int C, int E, hipStream_t st) {
     XDecBwd p = p0;
     p.dbg = g_xdbg_b;
-    static int on = -1;                                          // LXO_XDEC_BWD=0: forward chain only (A/B runs); LXO_XDEC=0 switches both off
-    if (on < 0) { const char* e = getenv("LXO_XDEC_BWD"); const char* f = getenv("LXO_XDEC"); on = ((e && e[0] == '0') || (f && f[0] == '0')) ? 0 : 1; }
-    if (!on) return -2;
-    if (U != XU || O != XO || C != XC || E != XE) return -2;
-    if (p.B % 8 != 0 || p.B > 64 || p.T < 1) return -2;
-    const int nb = p.B / 8;
-    if (nb != 1 && nb != 2 && nb != 4 && nb != 8) return -2;
-    const int nq = 32 / nb, rows_per = (p.R + nq - 1) / nq;
-    if (rows_per > SCMAX || rows_per < 1) return -2;
+    static int on = -1;
+    const int nb = xdec_gate(on, "LXO_XDEC_BWD", U, O, C, E, p.B, p.R, SCMAX);       // (the forward chain must have run the same shape)
+    if (!nb || p.T < 1) return -2;
     if (p.ldow % 8 || p.ldah % 8 || p.ldk % 8 || p.GBP % 8 || p.DZBP % 8 || p.REC % 4 || (long long)p.B * p.DZBP * 2 >= (1LL << 31)) return -2;
-    int dev = 0; hipDeviceProp_t pr;
-    static int dev_ok = -1;
-    if (dev_ok < 0) dev_ok = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount == 256) ? 1 : 0;
-    if (!dev_ok) return -2;
     HIPRC(hipMemsetAsync(p.sync, 0, kXDecBlockBytes, st));
-    if (kLLB & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * nq * XE * 4, st));      // the polled d_att_h partials (the forward chain's words lie there: no tag of theirs may pass)
-    int rc;
+    if (kLLB & 4) HIPRC(hipMemsetAsync(p.part, 0, (size_t)p.B * (32 / nb) * XE * 4, st));      // the polled d_att_h partials (the forward chain's words lie there: no tag of theirs may pass)
     switch (nb) {
-    case 1: rc = launch_bwd_nb<1>(p, st); break;
-    case 2: rc = launch_bwd_nb<2>(p, st); break;
-    case 4: rc = launch_bwd_nb<4>(p, st); break;
-    default: rc = launch_bwd_nb<8>(p, st); break;
+    case 1: return launch_bwd_nb<1>(p, st);
+    case 2: return launch_bwd_nb<2>(p, st);
+    case 4: return launch_bwd_nb<4>(p, st);
+    default: return launch_bwd_nb<8>(p, st);
     }
-    return rc;
 }
 #endif
