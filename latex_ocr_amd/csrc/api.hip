@@ -109,7 +109,7 @@ extern "C" int lxo_encoder_bwd_ready(const lxo_shape* s, const float* params, co
     return 0;
 }
 
-#include "decoder_kernels.h"
+#include "head_kernels.h"
 extern "C" int lxo_decoder_train_fwd(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                                      const int32_t* formula, void* stream) {
     MAKE_PLAN(P, s);
@@ -193,7 +193,7 @@ extern "C" int lxo_greedy_decode_scores(const lxo_shape* s, const float* params,
     CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_scores");
     return 0;
 }
-// the forced prefix of the _prefix calls (decoder_kernels.h); false: an array is missing or prefix_ld < 1
+// the forced prefix of the _prefix calls (head_kernels.h); false: an array is missing or prefix_ld < 1
 static bool make_prefix(DecPrefix* pf, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len, int max_iter) {
     *pf = DecPrefix{prefix, prefix_len, prefix_ld, prefix_ld < max_iter ? prefix_ld : max_iter};
     return prefix && prefix_len && prefix_ld >= 1;
@@ -208,7 +208,7 @@ extern "C" int lxo_greedy_decode_prefix(const lxo_shape* s, const float* params,
     CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_prefix");
     return 0;
 }
-// the _constrained calls' sets (decoder_kernels.h) and optional prefix; what is refused, or null
+// the _constrained calls' sets (head_kernels.h) and optional prefix; what is refused, or null
 static const char* make_constraint(DecAllow* al, DecPrefix* pf, bool* has_prefix, int V, const uint32_t* allow, int allow_ld,
                                    const int32_t* prefix, int prefix_ld, const int32_t* prefix_len, int max_iter) {
     *al = DecAllow{allow, allow_ld};

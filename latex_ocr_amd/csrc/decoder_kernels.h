@@ -1,4 +1,4 @@
-// Launchers of the non-GEMM decoder / loss / optimizer / decode kernels.
+// Launchers of the non-GEMM decoder / optimizer kernels (the output head: head_kernels.h).
 #pragma once
 #include "lxo_common.h"
 // split-K partial products of gemm_slab_kernel: value(row, col) = sum_{s<n} p[s*stride + row*ld + col]
@@ -32,31 +32,10 @@ int lxo_k_attn_bwd(int dt, const void* att_img, const void* att_exp, const void*
 int lxo_k_datt_img(int dt, const void* att_img, const float* att_h, const float* beta, const float* de, void* dout, float* dbeta,
                    int T, int B, int R, int Rp, int E, DetScratch det, hipStream_t st);
 int lxo_k_add_mean_grad(float* dimg, const float* dmean, int B, int R, int C, hipStream_t st);
-// ntok_dev (nullable): device scalar holding the global token count; when set the kernel uses 1 / *ntok_dev instead of inv_ntok
-int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
-                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st);      // chain_err (nullable): error word of the persistent decoder chain; non-zero poisons the loss (NaN)
-// teacher-forced scoring: logp_out [B][T] (logits[t * B + b][formula[b][t]] - lse), top1_out [B][T] (nullable), seq_out [B] (nullable, ordered f32
-// sum); rows t >= lengths[b]: 0 / -1; chain_err set: NaN / -1.  Reads the logits only.
-int lxo_k_score(int dt, const float* logits, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out,
-                const unsigned* chain_err, int B, int T, int V, int Vp, hipStream_t st);
 int lxo_k_colsum_det(const void* a, int bf16, long long lda, float* out, long long M, int N, DetScratch det, hipStream_t st);      // ordered column sums of an f32 / bf16 matrix (no atomics)
 int lxo_k_colsum(const float* a, long long lda, float* out, long long M, int N, DetScratch det, hipStream_t st);
 int lxo_k_embed_scatter(const float* demb, const int* formula, float* dtable, float* dstart, int B, int T, int D, int V, int det, hipStream_t st);
 int lxo_k_init_bwd(const float* dcc, Slabs dxh, const float* c0, const float* rec0, int ldr, float* dpre, int B, int U, int O, hipStream_t st);
-// A forced decode prefix (lxo_greedy_decode_prefix / lxo_beam_decode_prefix), device arrays: row (greedy) or image (beam) r emits ids[r][t] at
-// steps t < len[r]; lim = min(ld, max_iter) bounds a length (decoder_kernels.hip: how out-of-range values are read)
-struct DecPrefix { const int* ids; const int* len; int ld; int lim; };
-// Allowed-token sets (lxo_greedy_decode_constrained / lxo_beam_decode_constrained), device bit sets: bit v & 31 of word v >> 5 of row b set = image b
-// may emit token v; ld words per row, 0 = one row shared by every image.  A banned column is read as a column outside the vocabulary
-struct DecAllow { const unsigned* bits; int ld; };
-int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
-                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out = nullptr,      // logp_out (nullable): [n][max_steps] log-prob of the id
-                 const DecPrefix* prefix = nullptr, const DecAllow* allow = nullptr);
-int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
-                    float* scratch, float* logp, int* finished,
-                    int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
-                    float* scores_out = nullptr,      // scores_out (nullable): [nimg][max_steps][k] the running log-probs after the step
-                    const DecPrefix* prefix = nullptr, const DecAllow* allow = nullptr);      // allow: one row per IMAGE
 int lxo_k_beam_gather(float* rec, int ldr, int XH, float* cs, int U, const int* parents, int k, float* tmp_rec, float* tmp_cs, int n, void* recb, int ldrb, hipStream_t st);      // recb (nullable): bf16 mirror of the re-ordered [o | h] rows
 int lxo_k_tile_rows(const float* src, int lds, float* dst, int ldd, int n, int k, int cols, hipStream_t st);
 int lxo_k_global_norm_scale(long long n, const float* g, float clip, float* sumsq_tmp, float* out, hipStream_t st);

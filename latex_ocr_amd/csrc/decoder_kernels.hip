@@ -1,6 +1,7 @@
-// Decoder kernels that are not GEMMs.  One workgroup of 4 waves per sample for the
-// attention stream (attention_mechanism.py:46-94): scores, softmax over the R regions
-// and the context sum in ONE launch, att_img and img each read exactly once.
+// Decoder kernels that are neither GEMMs nor the output head (head_kernels.hip): row mean, embeddings, the LSTM cell, attention forward and
+// backward, column sums, the beam re-ordering of the carried state, global-norm clipping, the chain guards and the optimizers.  Attention
+// (attention_mechanism.py:46-94): one workgroup per sample -- scores, softmax over the R regions and the context sum in ONE launch, att_img
+// and img each read exactly once.
 #include "decoder_kernels.h"
 #include "api_util.h"
 #include "drop.h"
@@ -1194,116 +1195,6 @@ __global__ __launch_bounds__(256) void add_mean_grad_kernel(float* __restrict__ 
     }
 }
 
-// loss of img2seq.py:68-75 + gradient; one wave per (t, b) row, rows strided over the grid; the two loss statistics
-// are summed per workgroup first (one atomic pair per workgroup instead of one per token: the tokens all hit the same
-// two addresses)
-template <typename CT>
-__global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
-                                                     const int* __restrict__ lengths, CT* __restrict__ dlogits,
-                                                     float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
-                                                     const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
-    __shared__ float red[8];
-    // the persistent decoder chain (xdec.hip) flags a barrier that timed out: its logits are then garbage -- make the loss say so (NaN)
-    // instead of training on them silently
-    if (chain_err && blockIdx.x == 0 && threadIdx.x == 0 && chain_err[0] != 0u) atomicAdd(&loss_acc[0], __uint_as_float(0x7fc00000u));
-    if (ntok_dev) inv_ntok = 1.0f / ntok_dev[0];      // data parallel: the global token count arrives by all-reduce, never through the host
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float ce_sum = 0.f, n_sum = 0.f;
-    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
-        const int t = row / B, b = row - t * B;
-        const float* lg = logits + (long long)row * Vp;
-        CT* dl = dlogits + (long long)row * Vp;
-        const bool valid = t < lengths[b];
-        int tgt = formula[(long long)b * T + t];
-        tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
-        float m = -3.0e38f;
-        for (int j = lane; j < V; j += 64) m = fmaxf(m, lg[j]);
-        m = wave_max(m);
-        float l = 0.f;
-        for (int j = lane; j < V; j += 64) l += expf(lg[j] - m);
-        l = wave_sum(l);
-        const float lse = m + logf(l);
-        const float scale = valid ? inv_ntok : 0.f;
-        for (int j = lane; j < Vp; j += 64) {
-            float g = 0.f;
-            if (j < V) g = (expf(lg[j] - lse) - (j == tgt ? 1.f : 0.f)) * scale;
-            dl[j] = from_f32<CT>(g);
-        }
-        if (valid) { ce_sum += lse - lg[tgt]; n_sum += 1.0f; }      // wave-uniform values
-    }
-    if (lane == 0) { red[wave] = ce_sum; red[4 + wave] = n_sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float c = red[0] + red[1] + red[2] + red[3], n = red[4] + red[5] + red[6] + red[7];
-        if (loss_part) { loss_part[2 * blockIdx.x] = c; loss_part[2 * blockIdx.x + 1] = n; }     // f32 parity mode: summed in workgroup order by lxo_k_det_reduce
-        else if (n > 0.f) { atomicAdd(&loss_acc[0], c); atomicAdd(&loss_acc[1], n); }
-    }
-}
-
-// The same with the row held in registers (Vp <= 64 * KV): ONE pass over the logits -- 16-byte loads, a lane owns 4 consecutive columns per
-// quarter of KV -- instead of three passes of 4-byte loads, and every row has its own wave from the start (the three-pass kernel: 31 us for
-// 13 MB at the benchmark shape, a chain of dependent passes per row; this one 8).  bf16 mode: v_exp_f32 (1 ulp); f32 parity mode: expf.
-template <typename CT, int KV>
-__global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
-                                                          const int* __restrict__ lengths, CT* __restrict__ dlogits,
-                                                          float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
-                                                          const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
-    __shared__ float red[8];
-    if (chain_err && blockIdx.x == 0 && threadIdx.x == 0 && chain_err[0] != 0u) atomicAdd(&loss_acc[0], __uint_as_float(0x7fc00000u));
-    if (ntok_dev) inv_ntok = 1.0f / ntok_dev[0];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float ce_sum = 0.f, n_sum = 0.f;
-    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
-        const int t = row / B, b = row - t * B;
-        const float* lg = logits + (long long)row * Vp;
-        CT* dl = dlogits + (long long)row * Vp;
-        const bool valid = t < lengths[b];
-        int tgt = formula[(long long)b * T + t];
-        tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
-        const float xt = lg[tgt];
-        float x[KV];
-#pragma unroll
-        for (int q = 0; q < KV / 4; ++q) {
-            const int j0 = 4 * (lane + 64 * q);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(lg + (j0 < Vp ? j0 : 0));          // unconditional (clamped) load
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[4 * q + e] = (j0 + e < V) ? v[e] : -3.0e38f;
-        }
-        float m = x[0];
-#pragma unroll
-        for (int e = 1; e < KV; ++e) m = fmaxf(m, x[e]);
-        m = wave_max(m);
-        float l = 0.f;
-#pragma unroll
-        for (int e = 0; e < KV; ++e) l += is_bf16<CT>::value ? __expf(x[e] - m) : expf(x[e] - m);
-        l = wave_sum(l);
-        const float lse = m + logf(l);
-        const float scale = valid ? inv_ntok : 0.f;
-#pragma unroll
-        for (int q = 0; q < KV / 4; ++q) {
-            const int j0 = 4 * (lane + 64 * q);
-            if (j0 >= Vp) continue;
-            float g[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = j0 + e;
-                const float pr = is_bf16<CT>::value ? __expf(x[4 * q + e] - lse) : expf(x[4 * q + e] - lse);
-                g[e] = j < V ? (pr - (j == tgt ? 1.f : 0.f)) * scale : 0.f;
-            }
-            if constexpr (is_bf16<CT>::value) { const u32x2 pk = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])}; *reinterpret_cast<u32x2*>(dl + j0) = pk; }
-            else { const f32x4 gv = {g[0], g[1], g[2], g[3]}; *reinterpret_cast<f32x4*>(dl + j0) = gv; }
-        }
-        if (valid) { ce_sum += lse - xt; n_sum += 1.0f; }
-    }
-    if (lane == 0) { red[wave] = ce_sum; red[4 + wave] = n_sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float c = red[0] + red[1] + red[2] + red[3], n = red[4] + red[5] + red[6] + red[7];
-        if (loss_part) { loss_part[2 * blockIdx.x] = c; loss_part[2 * blockIdx.x + 1] = n; }
-        else if (n > 0.f) { atomicAdd(&loss_acc[0], c); atomicAdd(&loss_acc[1], n); }
-    }
-}
-
 // out[n] += sum_m a[m][n]
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a, int lda, float* __restrict__ out, int M, int N, int rows_per_block) {
     const int n = blockIdx.x * 256 + threadIdx.x;
@@ -1498,519 +1389,6 @@ __global__ __launch_bounds__(256) void init_bwd_kernel(const float* __restrict__
         else { d = slab_sum(dxh, b, k - 2 * U); s = rec0[(long long)b * ldr + (k - 2 * U)]; }
         dpre[i] = d * (1.f - s * s);
     }
-}
-
-// ---- decode ----
-// Forced prefix (PF instantiations of the decode kernels, DecPrefix in decoder_kernels.h): row r emits ids[r][t] at steps t < len[r].  What
-// the device holds is read defensively -- a length is clamped into [0, lim], lim = min(ld, max_iter), and an id outside [0, V) is read as
-// 0 -- so that no caller error faults.
-LXO_DEV int pfx_len(const DecPrefix& q, int r) { return min(max(q.len[r], 0), q.lim); }
-LXO_DEV int pfx_id(const DecPrefix& q, int r, int t, int V) { const int f = q.ids[(long long)r * q.ld + t]; return (f >= 0 && f < V) ? f : 0; }
-// Allowed-token sets (AL instantiations, DecAllow in decoder_kernels.h): a banned column is a column outside the vocabulary -- its logit is
-// -inf before anything else happens in the select step.  The words of a row are read inside [0, (V + 31) / 32): nothing faults on any content.
-LXO_DEV const unsigned* alw_row(const DecAllow& q, int r) { return q.bits + (long long)r * q.ld; }
-LXO_DEV bool alw_ok(const unsigned* row, int v) { return (row[v >> 5] >> (v & 31)) & 1u; }
-
-// greedy_decoder_cell.py:58-64: id = argmax (first max), finished |= id == END; one wave per row.
-// logp_out (nullable) [n][max_steps]: log_softmax(logits)[id] = logits[id] - lse, the log-sum-exp from one more pass over the row the wave has read
-// PF: at a step inside its prefix a row emits the forced id f (logp: logits[f] - lse) and stays unfinished
-// AL: banned columns are skipped in the max pass and in the exp-sum pass (a forced id's log-prob is taken under the same renormalised distribution)
-template <bool PF, bool AL>
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int Vp, int V, int n, int id_end,
-                                                    int* __restrict__ ids_step, int* __restrict__ ids_out, int max_steps, int step,
-                                                    int* __restrict__ finished, int* __restrict__ n_unfinished, float* __restrict__ logp_out,
-                                                    DecPrefix pf, DecAllow al) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    const float* lg = logits + (long long)row * Vp;
-    float best = -3.0e38f; int bi = 0x7fffffff;
-    const unsigned* ar = nullptr;
-    if constexpr (AL) ar = alw_row(al, row);
-    if constexpr (AL) { for (int j = lane; j < V; j += 64) { const float x = lg[j]; if (alw_ok(ar, j) && x > best) { best = x; bi = j; } } }
-    else
-    for (int j = lane; j < V; j += 64) { const float x = lg[j]; if (x > best) { best = x; bi = j; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    int fi = -1;                                               // PF: the forced id of this step (-1: a free step)
-    if constexpr (PF) { if (step < pfx_len(pf, row)) fi = pfx_id(pf, row, step, V); }
-    float lp = 0.f;
-    if (logp_out) {
-        float l = 0.f;
-        if constexpr (AL) { for (int j = lane; j < V; j += 64) if (alw_ok(ar, j)) l += expf(lg[j] - best); }
-        else
-        for (int j = lane; j < V; j += 64) l += expf(lg[j] - best);
-        lp = -logf(wave_sum(l));                               // logits[id] - (best + log l), logits[id] = best
-        if constexpr (PF) { if (fi >= 0) lp += lg[fi] - best; }
-    }
-    if (lane == 0) {
-        if (bi >= V) bi = 0;
-        if constexpr (PF) { if (fi >= 0) bi = fi; }
-        if (logp_out) logp_out[(long long)row * max_steps + step] = lp;
-        ids_step[row] = bi;
-        ids_out[(long long)row * max_steps + step] = bi;
-        const int f = finished[row] | (bi == id_end && fi < 0 ? 1 : 0);
-        finished[row] = f;
-        if (!f) atomicAdd(n_unfinished, 1);
-    }
-}
-
-// One block per image: beam_search_decoder_cell.py:146-187.
-//  log_softmax, mask finished beams (0 at END, f32 lowest elsewhere), add running log-probs,
-//  top-k over k*V (beam 0 only at time 0), ids = idx % V, parents = idx / V, gather finished.
-// add_div_penalty (beam_search_decoder_cell.py:258-287, Li et al. 2016): score += log(div_gamma) * rank * bernoulli(div_prob),
-// rank = position of the entry in the descending sort of its hypothesis' V scores (ties: lower id first, as
-// tf.nn.top_k orders them).  Bernoulli draws: the counter hash of drop_scale on (time, image, beam, id).
-struct DivPen { float log_gamma; unsigned thr; unsigned seed; float* scratch; };   // log_gamma == 0 or thr == 0: off
-// PF (both beam kernels): at a step t < P inside image b's prefix every slot j takes the forced id with parent j, its running log-prob grows by
-// that id's log-prob, no diversity penalty -- the k slots stay identical, as in the initial state.  Step P selects over slot 0 alone (what
-// time 0 does without a prefix), later steps over all k V candidates.
-LXO_DEV void beam_forced_out(int b, int k, int tid, int time, int id, float v, int fin, int* ids_step, int* parents_step, int* ids_out, int* par_out,
-                             int max_steps, float* scores_out, float* logp, int* finished, int* n_unfinished) {
-    ids_step[b * k + tid] = id;
-    parents_step[b * k + tid] = tid;
-    ids_out[((long long)b * max_steps + time) * k + tid] = id;
-    if (par_out) par_out[((long long)b * max_steps + time) * k + tid] = tid;
-    if (scores_out) scores_out[((long long)b * max_steps + time) * k + tid] = v;
-    logp[b * k + tid] = v;
-    finished[b * k + tid] = fin;
-    if (!fin) atomicAdd(n_unfinished, 1);
-}
-// AL (both beam kernels): the log-sum-exp runs over image b's allowed columns; a banned candidate (slot, token) scores -inf, also for a finished
-// hypothesis, and is never selected while an allowed one is left; the diversity rank of an allowed column counts the allowed columns ahead of it.
-template <bool PF, bool AL>
-__global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logits, int Vp, int V, int k, int id_end, int time, DivPen dp,
-                                                       float* __restrict__ logp, int* __restrict__ finished,
-                                                       int* __restrict__ ids_step, int* __restrict__ parents_step,
-                                                       int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                       int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf, DecAllow al) {
-    __shared__ float lse[16];
-    __shared__ float cand_v[16 * 4]; __shared__ int cand_i[16 * 4];
-    __shared__ float sel_v[16]; __shared__ int sel_i[16];
-    __shared__ int fin_old[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float FMIN = -3.40282347e38f;
-    const unsigned* ar = nullptr;
-    if constexpr (AL) ar = alw_row(al, b);
-    // log-sum-exp per beam (one wave per beam, round-robin)
-    for (int j = wave; j < k; j += 4) {
-        const float* lg = logits + ((long long)b * k + j) * Vp;
-        float m = -3.0e38f;
-        float l = 0.f;
-        if constexpr (AL) {
-            for (int c = lane; c < V; c += 64) if (alw_ok(ar, c)) m = fmaxf(m, lg[c]);
-            m = wave_max(m);
-            for (int c = lane; c < V; c += 64) if (alw_ok(ar, c)) l += expf(lg[c] - m);
-        } else {
-        for (int c = lane; c < V; c += 64) m = fmaxf(m, lg[c]);
-        m = wave_max(m);
-        for (int c = lane; c < V; c += 64) l += expf(lg[c] - m);
-        }
-        l = wave_sum(l);
-        if (lane == 0) lse[j] = m + logf(l);
-    }
-    if (tid < k) fin_old[tid] = finished[b * k + tid];
-    __syncthreads();
-    int t0 = 0;                                                // PF: the image's prefix length -- its beam search starts there
-    if constexpr (PF) {
-        t0 = pfx_len(pf, b);
-        if (time < t0) {
-            if (tid < k) {
-                const int id = pfx_id(pf, b, time, V);
-                beam_forced_out(b, k, tid, time, id, logp[b * k + tid] + (logits[((long long)b * k + tid) * Vp + id] - lse[tid]), fin_old[tid],
-                                ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
-            }
-            return;
-        }
-    }
-    const int nb = time > t0 ? k : 1;
-    const int total = nb * V;
-    const bool div = dp.log_gamma != 0.f && dp.thr != 0u;
-    float* pen = dp.scratch + (long long)b * k * Vp;
-    if (div) {
-        float* row0 = logits + (long long)b * k * Vp;
-        for (int i = tid; i < k * V; i += 256) {            // scores of every hypothesis, in place of its logits
-            const int j = i / V, c = i - j * V;
-            float sl = row0[j * Vp + c] - lse[j];
-            const float f = fin_old[j] ? 1.f : 0.f;
-            sl = (1.f - f) * sl + f * (c == id_end ? 0.f : FMIN);
-            row0[j * Vp + c] = logp[b * k + j] + sl;
-            if constexpr (AL) { if (!alw_ok(ar, c)) row0[j * Vp + c] = -INFINITY; }
-        }
-        __syncthreads();
-        for (int i = tid; i < k * V; i += 256) {
-            const int j = i / V, c = i - j * V;
-            const float* row = row0 + j * Vp;
-            const float v = row[c];
-            int rank = 0;
-            for (int q = 0; q < V; ++q) { const float w = row[q]; rank += (w > v || (w == v && q < c)) ? 1 : 0; }
-            const Drop dd = {dp.thr, 1.f, dp.seed, time, b * k + j, (int)gridDim.x * k};
-            pen[j * Vp + c] = v + dp.log_gamma * (float)rank * drop_scale(dd, 3u, 0, c, V);
-            if constexpr (AL) { if (!alw_ok(ar, c)) pen[j * Vp + c] = -INFINITY; }
-        }
-        __syncthreads();
-    }
-    for (int sel = 0; sel < k; ++sel) {
-        float best = -INFINITY; int bi = 0x7fffffff;
-        for (int i = tid; i < total; i += 256) {
-            const int j = i / V, c = i - j * V;
-            bool taken = false;
-            for (int q = 0; q < sel; ++q) taken |= (sel_i[q] == i);
-            if (taken) continue;
-            float val;
-            if (div) val = pen[j * Vp + c];
-            else {
-                float sl = logits[((long long)b * k + j) * Vp + c] - lse[j];
-                const float f = fin_old[j] ? 1.f : 0.f;
-                sl = (1.f - f) * sl + f * (c == id_end ? 0.f : FMIN);
-                val = logp[b * k + j] + sl;
-                if constexpr (AL) { if (!alw_ok(ar, c)) val = -INFINITY; }
-            }
-            if (val > best || (val == best && i < bi)) { best = val; bi = i; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
-        if (lane == 0) { cand_v[wave] = best; cand_i[wave] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            float bv = cand_v[0]; int bx = cand_i[0];
-            for (int w = 1; w < 4; ++w)
-                if (cand_v[w] > bv || (cand_v[w] == bv && cand_i[w] < bx)) { bv = cand_v[w]; bx = cand_i[w]; }
-            sel_v[sel] = bv; sel_i[sel] = bx;
-        }
-        __syncthreads();
-    }
-    if (tid < k) {
-        const int idx = sel_i[tid];
-        const int id = idx % V, par = idx / V;
-        const int f = fin_old[par] | (id == id_end ? 1 : 0);
-        ids_step[b * k + tid] = id;
-        parents_step[b * k + tid] = par;
-        ids_out[((long long)b * max_steps + time) * k + tid] = id;
-        if (par_out) par_out[((long long)b * max_steps + time) * k + tid] = par;
-        if (scores_out) scores_out[((long long)b * max_steps + time) * k + tid] = sel_v[tid];      // the running log-prob after the step (state.log_probs)
-        logp[b * k + tid] = sel_v[tid];
-        finished[b * k + tid] = f;
-        if (!f) atomicAdd(n_unfinished, 1);
-    }
-}
-
-// The same step with every candidate score held in REGISTERS (k * V <= BS_TH * BS_NPT = 4096, k <= 64 / BS_NW, no diversity penalty): beam_step_kernel re-reads and
-// re-forms all k * V scores (an integer division each) for every one of its k selections and makes two passes over a row for its
-// log-sum-exp -- 31 us of a 161 us beam-5 step at B = 64, on 64 workgroups.  Here a lane loads its share of a row ONCE (max, then the
-// exponentials, from registers), a thread forms its <= BS_NPT scores ONCE, and a selection is a register scan + the block-wide arg-max.
-// Same expressions, same summation order inside a wave, same tie rule (lower flat index first): the ids and parents are the slow kernel's.
-constexpr int BS_TH = 512, BS_NW = BS_TH / 64, BS_NPT = 4096 / BS_TH;      // 8 waves x 8 candidates per thread (it was 4 x 16: a selection round scans a thread's candidates, k rounds per step)
-// (value, index) arg-max over the 64 lanes of a wave -- value descending, index ascending -- every lane ends with the winner.  The four steps inside a
-// row of 16 lanes are DPP moves, the two across rows permlane swaps (as bm_wave_sum_dpp: no LDS crossbar round trips).
-#ifdef LXO_HIPSIM
-LXO_DEV void wave_argmax(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(i, o);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-}
-#else
-template <int CTRL> LXO_DEV void amax_dpp(float& v, int& i) {
-    const float ov = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-    const int oi = __builtin_amdgcn_update_dpp(0, i, CTRL, 0xf, 0xf, true);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
-LXO_DEV void wave_argmax(float& v, int& i) {
-    amax_dpp<0xB1>(v, i); amax_dpp<0x4E>(v, i); amax_dpp<0x141>(v, i); amax_dpp<0x140>(v, i);
-    {
-        const auto rv = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        const auto ri = __builtin_amdgcn_permlane16_swap((unsigned)i, (unsigned)i, false, false);
-        const float v0 = __uint_as_float(rv[0]), v1 = __uint_as_float(rv[1]); const int i0 = (int)ri[0], i1 = (int)ri[1];
-        const bool first = v0 > v1 || (v0 == v1 && i0 < i1);
-        v = first ? v0 : v1; i = first ? i0 : i1;
-    }
-    {
-        const auto rv = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        const auto ri = __builtin_amdgcn_permlane32_swap((unsigned)i, (unsigned)i, false, false);
-        const float v0 = __uint_as_float(rv[0]), v1 = __uint_as_float(rv[1]); const int i0 = (int)ri[0], i1 = (int)ri[1];
-        const bool first = v0 > v1 || (v0 == v1 && i0 < i1);
-        v = first ? v0 : v1; i = first ? i0 : i1;
-    }
-}
-#endif
-template <bool PF, bool AL>
-__global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __restrict__ logits, int Vp, int V, int k, int id_end, int time,
-                                                            float* __restrict__ logp, int* __restrict__ finished,
-                                                            int* __restrict__ ids_step, int* __restrict__ parents_step,
-                                                            int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
-                                                            int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf, DecAllow al) {
-    __shared__ float lse[16];
-    __shared__ float sel_v[16]; __shared__ int sel_i[16];
-    __shared__ int fin_old[16];
-    __shared__ float lp_old[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float FMIN = -3.40282347e38f;
-    __shared__ float wc_v[BS_NW * 16]; __shared__ int wc_i[BS_NW * 16];      // the waves' k best each
-    int t0 = 0;                                                // PF: the image's prefix length (beam_step_kernel)
-    if constexpr (PF) t0 = pfx_len(pf, b);
-    const unsigned* ar = nullptr;                              // AL: the image's allowed-token bits
-    if constexpr (AL) ar = alw_row(al, b);
-    const int nb = time > t0 ? k : 1;
-    const int total = nb * V;
-    float raw[BS_NPT];                                         // raw logits of this thread's candidates (unconditional, clamped: requested before anything is waited for)
-    {
-        int jq = tid / V, cq = tid - jq * V;
-#pragma unroll
-        for (int u = 0; u < BS_NPT; ++u) {
-            const int j = min(jq, k - 1), c = cq;
-            cq += BS_TH;
-            while (cq >= V) { cq -= V; ++jq; }
-            raw[u] = logits[((long long)b * k + j) * Vp + c];
-        }
-    }
-    if (V <= 64 * 8 && k <= 8) {
-        // log-sum-exp per hypothesis: a wave takes hypothesis `wave` (+ BS_NW q: every row requested before any is reduced), the row in registers
-        // for its two passes
-        constexpr int RQ = 8 / BS_NW > 0 ? 8 / BS_NW : 1;
-        float x[RQ][8];
-        bool ok8[8];                                           // AL: column lane + 64 u is allowed (the same for every hypothesis of the image)
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { ok8[u] = true; if constexpr (AL) { const int c = lane + 64 * u; ok8[u] = alw_ok(ar, c < V ? c : V - 1); } }
-#pragma unroll
-        for (int q = 0; q < RQ; ++q) {
-            const int j = min(wave + BS_NW * q, k - 1);
-            const float* lg = logits + ((long long)b * k + j) * Vp;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const int c = lane + 64 * u; x[q][u] = lg[c < V ? c : V - 1]; }
-        }
-#pragma unroll
-        for (int q = 0; q < RQ; ++q) {
-            const int j = wave + BS_NW * q;
-            float m = -3.0e38f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) if (lane + 64 * u < V && ok8[u]) m = fmaxf(m, x[q][u]);
-            m = wave_max(m);
-            float l = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) if (lane + 64 * u < V && ok8[u]) l += expf(x[q][u] - m);
-            l = wave_sum(l);
-            if (lane == 0 && j < k) lse[j] = m + logf(l);
-        }
-    } else
-    for (int j = wave; j < k; j += BS_NW) {                   // the general form: one wave per hypothesis, round-robin
-        const float* lg = logits + ((long long)b * k + j) * Vp;
-        float m = -3.0e38f;
-        if (V <= 64 * 16) {
-            float x[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) { const int c = lane + 64 * u; x[u] = lg[c < V ? c : V - 1]; }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) if (lane + 64 * u < V && (!AL || alw_ok(ar, lane + 64 * u))) m = fmaxf(m, x[u]);
-            m = wave_max(m);
-            float l = 0.f;
-#pragma unroll
-            for (int u = 0; u < 16; ++u) if (lane + 64 * u < V && (!AL || alw_ok(ar, lane + 64 * u))) l += expf(x[u] - m);
-            l = wave_sum(l);
-            if (lane == 0) lse[j] = m + logf(l);
-        } else {
-            for (int c = lane; c < V; c += 64) if (!AL || alw_ok(ar, c)) m = fmaxf(m, lg[c]);
-            m = wave_max(m);
-            float l = 0.f;
-            for (int c = lane; c < V; c += 64) if (!AL || alw_ok(ar, c)) l += expf(lg[c] - m);
-            l = wave_sum(l);
-            if (lane == 0) lse[j] = m + logf(l);
-        }
-    }
-    if (tid < k) { fin_old[tid] = finished[b * k + tid]; lp_old[tid] = logp[b * k + tid]; }
-    __syncthreads();
-    if constexpr (PF) {
-        if (time < t0) {
-            if (tid < k) {
-                const int id = pfx_id(pf, b, time, V);
-                beam_forced_out(b, k, tid, time, id, lp_old[tid] + (logits[((long long)b * k + tid) * Vp + id] - lse[tid]), fin_old[tid],
-                                ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
-            }
-            return;
-        }
-    }
-    // candidates of this thread: i = tid + BS_TH u -> (hypothesis, id) walked instead of divided; their raw logits were requested in front of the
-    // log-sum-exp pass (raw[]: the second read of the rows no longer waits behind the first)
-    float val[BS_NPT];
-    {
-        int jq = tid / V, cq = tid - jq * V;
-#pragma unroll
-        for (int u = 0; u < BS_NPT; ++u) {
-            const int i = tid + BS_TH * u;
-            val[u] = -INFINITY;
-            const int j = jq, c = cq;
-            cq += BS_TH;
-            while (cq >= V) { cq -= V; ++jq; }
-            if (i < total) {
-                float sl = raw[u] - lse[j];
-                const float f = fin_old[j] ? 1.f : 0.f;
-                sl = (1.f - f) * sl + f * (c == id_end ? 0.f : FMIN);
-                val[u] = lp_old[j] + sl;
-                if constexpr (AL) { if (!alw_ok(ar, c)) val[u] = -INFINITY; }
-            }
-        }
-    }
-    // top-k in two stages, ONE workgroup barrier between them (it was two per selection): every wave selects the k best of ITS candidates by itself
-    // -- the k best of the block are among them -- then wave 0 selects the k best of the BS_NW k survivors, one per lane.  Order everywhere:
-    // value descending, flat index ascending (tf.nn.top_k over the flattened [k * V] scores: the lower index of equal values first).
-    {
-        unsigned taken = 0u;                                   // bit u: this thread's candidate u has been selected
-        for (int sel = 0; sel < k; ++sel) {
-            float best = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-            for (int u = 0; u < BS_NPT; ++u) {
-                const int i = tid + BS_TH * u;
-                if (i < total && !((taken >> u) & 1u) && (val[u] > best || (val[u] == best && i < bi))) { best = val[u]; bi = i; }
-            }
-            wave_argmax(best, bi);
-            if (lane == 0) { wc_v[wave * 16 + sel] = best; wc_i[wave * 16 + sel] = bi; }
-#pragma unroll
-            for (int u = 0; u < BS_NPT; ++u) if (tid + BS_TH * u == bi) taken |= 1u << u;
-        }
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const int w = lane / k, e = lane - w * k;              // survivor e of wave w (BS_NW k <= 64 lanes: the launcher's condition)
-        float cv = -INFINITY; int ci = 0x7fffffff;
-        if (w < BS_NW) { cv = wc_v[w * 16 + e]; ci = wc_i[w * 16 + e]; }
-        for (int sel = 0; sel < k; ++sel) {
-            float bv = cv; int bx = ci;
-            wave_argmax(bv, bx);
-            if (lane == 0) { sel_v[sel] = bv; sel_i[sel] = bx; }
-            if (ci == bx) { cv = -INFINITY; ci = 0x7fffffff; }
-        }
-    }
-    __syncthreads();
-    if (tid < k) {
-        const int idx = sel_i[tid];
-        const int id = idx % V, par = idx / V;
-        const int f = fin_old[par] | (id == id_end ? 1 : 0);
-        ids_step[b * k + tid] = id;
-        parents_step[b * k + tid] = par;
-        ids_out[((long long)b * max_steps + time) * k + tid] = id;
-        if (par_out) par_out[((long long)b * max_steps + time) * k + tid] = par;
-        if (scores_out) scores_out[((long long)b * max_steps + time) * k + tid] = sel_v[tid];      // the running log-prob after the step (state.log_probs)
-        logp[b * k + tid] = sel_v[tid];
-        finished[b * k + tid] = f;
-        if (!f) atomicAdd(n_unfinished, 1);
-    }
-}
-
-// ---- teacher-forced scoring (lxo_score_tokens) ----
-// Forward-only read-out of the training logits: logp_out[b][t] = logits[row][formula[b][t]] - lse(row) and top1_out[b][t] (nullable) =
-// the row's first maximum (argmax_kernel's rule: the lower index on ties), row = t * B + b.  No d(logits), no loss statistics, no atomics.
-// One wave per row with the row in registers, as ce_loss_rows_kernel, and with its expressions (bf16 mode: v_exp_f32, f32 mode: expf):
-// -sum logp over the live tokens is that kernel's sum CE up to summation order.  Rows t >= lengths[b]: logp 0, top1 -1.  A failed forward
-// chain (chain_err set): every logp NaN, every top1 -1, as the CE kernel turns its loss into NaN.
-template <bool BF, int KV>
-__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
-                                                        const int* __restrict__ lengths, float* __restrict__ logp_out, int* __restrict__ top1_out,
-                                                        const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool bad = chain_err && chain_err[0] != 0u;
-    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
-        const int t = row / B, b = row - t * B;
-        const long long o = (long long)b * T + t;
-        if (bad || t >= lengths[b]) {
-            if (lane == 0) { logp_out[o] = bad ? __uint_as_float(0x7fc00000u) : 0.f; if (top1_out) top1_out[o] = -1; }
-            continue;
-        }
-        const float* lg = logits + (long long)row * Vp;
-        int tgt = formula[o];
-        tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
-        const float xt = lg[tgt];
-        float x[KV];
-#pragma unroll
-        for (int q = 0; q < KV / 4; ++q) {
-            const int j0 = 4 * (lane + 64 * q);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(lg + (j0 < Vp ? j0 : 0));          // unconditional (clamped) load
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[4 * q + e] = (j0 + e < V) ? v[e] : -3.0e38f;
-        }
-        float m = x[0];
-#pragma unroll
-        for (int e = 1; e < KV; ++e) m = fmaxf(m, x[e]);
-        m = wave_max(m);
-        float l = 0.f;
-#pragma unroll
-        for (int e = 0; e < KV; ++e) l += BF ? __expf(x[e] - m) : expf(x[e] - m);
-        l = wave_sum(l);
-        const float lse = m + logf(l);
-        float best = -3.0e38f; int bi = 0x7fffffff;
-        if (top1_out) {
-            // a lane's columns in ascending order (strict >: its first maximum), then the wave's (value desc, index asc)
-#pragma unroll
-            for (int q = 0; q < KV / 4; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int j = 4 * (lane + 64 * q) + e;
-                    if (j < V && x[4 * q + e] > best) { best = x[4 * q + e]; bi = j; }
-                }
-            wave_argmax(best, bi);
-        }
-        if (lane == 0) { logp_out[o] = xt - lse; if (top1_out) top1_out[o] = bi < V ? bi : 0; }
-    }
-}
-
-// The same for any Vp (the row does not fit in registers): three strided passes per row, with ce_loss_kernel's expressions (expf in both
-// modes), so that its sum CE is again -sum logp up to summation order.
-__global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
-                                                   const int* __restrict__ lengths, float* __restrict__ logp_out, int* __restrict__ top1_out,
-                                                   const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool bad = chain_err && chain_err[0] != 0u;
-    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
-        const int t = row / B, b = row - t * B;
-        const long long o = (long long)b * T + t;
-        if (bad || t >= lengths[b]) {
-            if (lane == 0) { logp_out[o] = bad ? __uint_as_float(0x7fc00000u) : 0.f; if (top1_out) top1_out[o] = -1; }
-            continue;
-        }
-        const float* lg = logits + (long long)row * Vp;
-        int tgt = formula[o];
-        tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
-        float m = -3.0e38f;
-        for (int j = lane; j < V; j += 64) m = fmaxf(m, lg[j]);
-        m = wave_max(m);
-        float l = 0.f;
-        for (int j = lane; j < V; j += 64) l += expf(lg[j] - m);
-        l = wave_sum(l);
-        const float lse = m + logf(l);
-        float best = -3.0e38f; int bi = 0x7fffffff;
-        if (top1_out) {
-            for (int j = lane; j < V; j += 64) { const float x = lg[j]; if (x > best) { best = x; bi = j; } }
-            wave_argmax(best, bi);
-        }
-        if (lane == 0) { logp_out[o] = lg[tgt] - lse; if (top1_out) top1_out[o] = bi < V ? bi : 0; }
-    }
-}
-
-// seq_out[b] = logp_out[b][0] + ... + logp_out[b][len - 1], one thread per sequence adding in ascending t: the f32 sum in np.float32's
-// left-to-right order, whatever the grid of the pass before; a failed forward chain: NaN.  The loads go out 16 at a time ahead of their
-// additions (one load after another, T = 101 took 21 us of dependent latency)
-__global__ __launch_bounds__(256) void score_seq_kernel(const float* __restrict__ logp, const int* __restrict__ lengths, float* __restrict__ seq_out,
-                                                       const unsigned* __restrict__ chain_err, int B, int T) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    int n = lengths[b];
-    n = n < 0 ? 0 : (n > T ? T : n);
-    const float* p = logp + (long long)b * T;
-    float s = 0.f;
-    for (int t0 = 0; t0 < n; t0 += 16) {
-        float v[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = t0 + e < n ? p[t0 + e] : 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) if (t0 + e < n) s += v[e];
-    }
-    seq_out[b] = (chain_err && chain_err[0] != 0u) ? __uint_as_float(0x7fc00000u) : s;
 }
 
 // new[v] = old[b*k + parents[v]] for the carried state (o | h of rec, and c)   (beam_search_decoder_cell.py:176-178)
@@ -2329,41 +1707,6 @@ int lxo_k_add_mean_grad(float* dimg, const float* dmean, int B, int R, int C, hi
     LAUNCH(add_mean_grad_kernel, grid1((long long)B * R * C), dimg, dmean, B, R, C);
     DONE;
 }
-int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
-                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st) {
-    int g = cdiv(T * B, 4);
-    float* part = (det.p && det.floats >= 1024) ? det.p : nullptr;      // loss_acc is zero on entry (lxo_impl_ce_loss)
-    if (Vp % 4 == 0 && Vp <= 1024 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0) {
-        // a wave per row, the row in registers (one pass); the f32 parity mode keeps at most 512 workgroups (its ordered partial sums)
-        if (g > (part ? 512 : 2048)) g = part ? 512 : 2048;
-#define CE_ROWS(CT_, KV_) LAUNCH((ce_loss_rows_kernel<CT_, KV_>), g, logits, formula, lengths, (CT_*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp)
-        if (dt == LXO_BF16) { if (Vp <= 256) CE_ROWS(bf16_t, 4); else if (Vp <= 512) CE_ROWS(bf16_t, 8); else CE_ROWS(bf16_t, 16); }
-        else { if (Vp <= 256) CE_ROWS(float, 4); else if (Vp <= 512) CE_ROWS(float, 8); else CE_ROWS(float, 16); }
-#undef CE_ROWS
-        if (part) return lxo_k_det_reduce(part, g, 2, 2, loss_acc, st);
-        DONE;
-    }
-    if (g > 512) g = 512;
-    if (dt == LXO_BF16) LAUNCH((ce_loss_kernel<bf16_t>), g, logits, formula, lengths, (bf16_t*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp);
-    else LAUNCH((ce_loss_kernel<float>), g, logits, formula, lengths, (float*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp);
-    if (part) return lxo_k_det_reduce(part, g, 2, 2, loss_acc, st);
-    DONE;
-}
-int lxo_k_score(int dt, const float* logits, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out,
-                const unsigned* chain_err, int B, int T, int V, int Vp, hipStream_t st) {
-    int g = cdiv(T * B, 4);
-    if (Vp % 4 == 0 && Vp <= 1024 && ((uintptr_t)logits & 15) == 0) {
-        if (g > 2048) g = 2048;
-#define SC_ROWS(BF_, KV_) LAUNCH((score_rows_kernel<BF_, KV_>), g, logits, formula, lengths, logp_out, top1_out, chain_err, B, T, V, Vp)
-        if (dt == LXO_BF16) { if (Vp <= 256) SC_ROWS(true, 4); else if (Vp <= 512) SC_ROWS(true, 8); else SC_ROWS(true, 16); }
-        else { if (Vp <= 256) SC_ROWS(false, 4); else if (Vp <= 512) SC_ROWS(false, 8); else SC_ROWS(false, 16); }
-#undef SC_ROWS
-    } else {
-        LAUNCH(score_kernel, g > 512 ? 512 : g, logits, formula, lengths, logp_out, top1_out, chain_err, B, T, V, Vp);
-    }
-    if (seq_out) LAUNCH(score_seq_kernel, cdiv(B, 256), logp_out, lengths, seq_out, chain_err, B, T);
-    DONE;
-}
 // ordered column sums (no atomics): per-row-block partial sums into the scratch, then the blocks in order; a = f32 or (bf16 != 0) bf16
 int lxo_k_colsum_det(const void* a, int bf16, long long lda, float* out, long long M, int N, DetScratch det, hipStream_t st) {
     if (!det.p) return -6;
@@ -2396,41 +1739,6 @@ int lxo_k_embed_scatter(const float* demb, const int* formula, float* dtable, fl
 }
 int lxo_k_init_bwd(const float* dcc, Slabs dxh, const float* c0, const float* rec0, int ldr, float* dpre, int B, int U, int O, hipStream_t st) {
     LAUNCH(init_bwd_kernel, grid1((long long)B * (2 * U + O)), dcc, dxh, c0, rec0, ldr, dpre, B, U, O);
-    DONE;
-}
-// The decode kernels' compile-time flags from the call's nullable arguments: KERNEL<PF, AL> with PF = a forced prefix, AL = allowed-token sets
-#define DEC_VARIANT(KERNEL, grid, block, ...)                                                                         \
-    do {                                                                                                               \
-        if (prefix && allow) hipLaunchKernelGGL((KERNEL<true, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);    \
-        else if (prefix) hipLaunchKernelGGL((KERNEL<true, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);       \
-        else if (allow) hipLaunchKernelGGL((KERNEL<false, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);        \
-        else hipLaunchKernelGGL((KERNEL<false, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);                  \
-    } while (0)
-int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
-                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out, const DecPrefix* prefix, const DecAllow* allow) {
-    const DecPrefix pf = prefix ? *prefix : DecPrefix{};
-    const DecAllow al = allow ? *allow : DecAllow{};
-    DEC_VARIANT(argmax_kernel, cdiv(n, 4), 256, logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, pf, al);
-    DONE;
-}
-int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
-                    float* scratch, float* logp, int* finished,
-                    int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
-                    float* scores_out, const DecPrefix* prefix, const DecAllow* allow) {
-    if (k > 16 || k > V) return -2;                            // k > V: at time 0 only V candidates exist -- a k-th selection would have no index
-    DivPen dp = {0.f, 0u, (unsigned)div_seed, scratch};
-    if (div_gamma > 0.f && div_gamma != 1.f && div_prob > 0.f) {      // the reference returns early for gamma == 1 or prob == 0
-        dp.log_gamma = logf(div_gamma);
-        dp.thr = div_prob >= 1.f ? 16777216u : (unsigned)(div_prob * 16777216.0f);
-    }
-    static int fast = -1;                                      // LXO_BEAM_FAST=0: the general kernel always (A/B)
-    if (fast < 0) { const char* e = getenv("LXO_BEAM_FAST"); fast = (e && e[0] == '0') ? 0 : 1; }
-    const DecPrefix pf = prefix ? *prefix : DecPrefix{};
-    const DecAllow al = allow ? *allow : DecAllow{};
-    if (fast && dp.log_gamma == 0.f && (long long)k * V <= BS_TH * BS_NPT && k * BS_NW <= 64) {
-        DEC_VARIANT(beam_step_fast_kernel, nimg, BS_TH, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf, al);
-    } else
-        DEC_VARIANT(beam_step_kernel, nimg, 256, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf, al);
     DONE;
 }
 int lxo_k_beam_gather(float* rec, int ldr, int XH, float* cs, int U, const int* parents, int k, float* tmp_rec, float* tmp_cs, int n, void* recb, int ldrb, hipStream_t st) {

@@ -1,0 +1,658 @@
+// The output head: every kernel that reads a row of logits and turns it into a loss (ce_loss*), a log-prob (score*) or a token
+// (argmax_kernel, beam_step*), their launchers, and -- first -- the row steps they are made of.
+#include "head_kernels.h"
+#include "drop.h"
+#include <stdlib.h>
+
+namespace {
+
+// ---- row steps ----
+// Every step of the head exists once, here; a kernel below only says which steps it takes and where the result goes.  A new head feature
+// (a tie rule, a temperature, a length penalty, another mask) goes into these helpers, never into a kernel.
+
+// Forced prefix (PF instantiations of the decode kernels, DecPrefix in head_kernels.h): row r emits ids[r][t] at steps t < len[r].  What
+// the device holds is read defensively -- a length is clamped into [0, lim], lim = min(ld, max_iter), and an id outside [0, V) is read as
+// 0 -- so that no caller error faults.
+LXO_DEV int pfx_len(const DecPrefix& q, int r) { return min(max(q.len[r], 0), q.lim); }
+LXO_DEV int pfx_id(const DecPrefix& q, int r, int t, int V) { const int f = q.ids[(long long)r * q.ld + t]; return (f >= 0 && f < V) ? f : 0; }
+// Allowed-token sets (AL instantiations, DecAllow in head_kernels.h): a banned column is a column outside the vocabulary -- its logit is
+// -inf before anything else happens in the select step.  The words of a row are read inside [0, (V + 31) / 32): nothing faults on any content.
+LXO_DEV const unsigned* alw_row(const DecAllow& q, int r) { return q.bits + (long long)r * q.ld; }
+LXO_DEV bool alw_ok(const unsigned* row, int v) { return (row[v >> 5] >> (v & 31)) & 1u; }
+
+// Register row (Vp <= 64 * KV): 16-byte loads, a lane owns 4 consecutive columns per quarter of KV; the load is unconditional (clamped) and a
+// column >= V reads as -3.0e38f
+template <int KV>
+LXO_DEV void row_load(const float* lg, int lane, int V, int Vp, float (&x)[KV]) {
+#pragma unroll
+    for (int q = 0; q < KV / 4; ++q) {
+        const int j0 = 4 * (lane + 64 * q);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(lg + (j0 < Vp ? j0 : 0));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[4 * q + e] = (j0 + e < V) ? v[e] : -3.0e38f;
+    }
+}
+// e^x of the register-row kernels: v_exp_f32 (1 ulp) in bf16 mode, expf in f32 parity mode
+template <bool FAST> LXO_DEV float row_exp(float x) { return FAST ? __expf(x) : expf(x); }
+// its log-sum-exp, every lane's
+template <bool FAST, int KV>
+LXO_DEV float row_lse(const float (&x)[KV]) {
+    float m = x[0];
+#pragma unroll
+    for (int e = 1; e < KV; ++e) m = fmaxf(m, x[e]);
+    m = wave_max(m);
+    float l = 0.f;
+#pragma unroll
+    for (int e = 0; e < KV; ++e) l += row_exp<FAST>(x[e] - m);
+    l = wave_sum(l);
+    return m + logf(l);
+}
+
+// Strided row (any V): a lane takes columns lane, lane + 64, ...; AL: the banned ones are skipped.  The wave's exp-sum around a given max ...
+template <bool AL>
+LXO_DEV float strided_expsum(const float* lg, int lane, int V, const unsigned* ar, float m) {
+    float l = 0.f;
+    for (int j = lane; j < V; j += 64) if (!AL || alw_ok(ar, j)) l += expf(lg[j] - m);
+    return wave_sum(l);
+}
+// ... and its log-sum-exp, around its own
+template <bool AL>
+LXO_DEV float strided_lse(const float* lg, int lane, int V, const unsigned* ar) {
+    float m = -3.0e38f;
+    for (int j = lane; j < V; j += 64) if (!AL || alw_ok(ar, j)) m = fmaxf(m, lg[j]);
+    m = wave_max(m);
+    return m + logf(strided_expsum<AL>(lg, lane, V, ar, m));
+}
+// a lane's first maximum of such a row (strict >, ascending columns); a wave arg-max follows
+template <bool AL>
+LXO_DEV void strided_argmax(const float* lg, int lane, int V, const unsigned* ar, float& best, int& bi) {
+    best = -3.0e38f; bi = 0x7fffffff;
+    for (int j = lane; j < V; j += 64) { const float x = lg[j]; if ((!AL || alw_ok(ar, j)) && x > best) { best = x; bi = j; } }
+}
+
+// Lane-register row (V <= 64 * N): columns lane + 64 u, every load requested (clamped index) before anything is reduced, masked by V and AL
+template <int N, bool AL>
+LXO_DEV float lane_row_lse(const float* lg, int lane, int V, const unsigned* ar) {
+    float x[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) { const int c = lane + 64 * u; x[u] = lg[c < V ? c : V - 1]; }
+    float m = -3.0e38f;
+#pragma unroll
+    for (int u = 0; u < N; ++u) if (lane + 64 * u < V && (!AL || alw_ok(ar, lane + 64 * u))) m = fmaxf(m, x[u]);
+    m = wave_max(m);
+    float l = 0.f;
+#pragma unroll
+    for (int u = 0; u < N; ++u) if (lane + 64 * u < V && (!AL || alw_ok(ar, lane + 64 * u))) l += expf(x[u] - m);
+    l = wave_sum(l);
+    return m + logf(l);
+}
+
+// (value, index) arg-max over the 64 lanes of a wave -- value descending, index ascending -- every lane ends with the winner: the shuffle butterfly ...
+LXO_DEV void shfl_argmax(float& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(i, o);
+        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    }
+}
+// ... and the one without LDS crossbar round trips: the four steps inside a row of 16 lanes are DPP moves, the two across rows permlane swaps
+// (as bm_wave_sum_dpp of decoder_kernels.hip)
+#ifdef LXO_HIPSIM
+LXO_DEV void wave_argmax(float& v, int& i) { shfl_argmax(v, i); }
+#else
+template <int CTRL> LXO_DEV void amax_dpp(float& v, int& i) {
+    const float ov = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+    const int oi = __builtin_amdgcn_update_dpp(0, i, CTRL, 0xf, 0xf, true);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+LXO_DEV void wave_argmax(float& v, int& i) {
+    amax_dpp<0xB1>(v, i); amax_dpp<0x4E>(v, i); amax_dpp<0x141>(v, i); amax_dpp<0x140>(v, i);
+    {
+        const auto rv = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        const auto ri = __builtin_amdgcn_permlane16_swap((unsigned)i, (unsigned)i, false, false);
+        const float v0 = __uint_as_float(rv[0]), v1 = __uint_as_float(rv[1]); const int i0 = (int)ri[0], i1 = (int)ri[1];
+        const bool first = v0 > v1 || (v0 == v1 && i0 < i1);
+        v = first ? v0 : v1; i = first ? i0 : i1;
+    }
+    {
+        const auto rv = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        const auto ri = __builtin_amdgcn_permlane32_swap((unsigned)i, (unsigned)i, false, false);
+        const float v0 = __uint_as_float(rv[0]), v1 = __uint_as_float(rv[1]); const int i0 = (int)ri[0], i1 = (int)ri[1];
+        const bool first = v0 > v1 || (v0 == v1 && i0 < i1);
+        v = first ? v0 : v1; i = first ? i0 : i1;
+    }
+}
+#endif
+
+// Row of the loss and scoring kernels: row = t * B + b reads formula[b][t] (o = its flat index), live while t < lengths[b]; the target clamped into [0, V)
+struct RowTok { int t, b; long long o; bool live; };
+LXO_DEV RowTok row_tok(int row, int B, int T, const int* lengths) {
+    const int t = row / B, b = row - t * B;
+    return {t, b, (long long)b * T + t, t < lengths[b]};
+}
+LXO_DEV int row_target(const int* formula, long long o, int V) {
+    const int tgt = formula[o];
+    return tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
+}
+
+// The CE kernels' way in: the persistent decoder chain (xdec.hip) flags a barrier that timed out: its logits are then garbage -- make the loss say
+// so (NaN) instead of training on them silently.  Returns 1 / the token count (data parallel: the global count arrives by all-reduce in ntok_dev,
+// never through the host)
+LXO_DEV float ce_begin(const unsigned* chain_err, float* loss_acc, const float* ntok_dev, float inv_ntok) {
+    if (chain_err && blockIdx.x == 0 && threadIdx.x == 0 && chain_err[0] != 0u) atomicAdd(&loss_acc[0], __uint_as_float(0x7fc00000u));
+    return ntok_dev ? 1.0f / ntok_dev[0] : inv_ntok;
+}
+// ... and out: the two loss statistics (wave-uniform) are summed per workgroup first -- one atomic pair per workgroup instead of one per token (the
+// tokens all hit the same two addresses); f32 parity mode (loss_part): stored, and summed in workgroup order by lxo_k_det_reduce
+LXO_DEV void ce_end(float* red, float ce_sum, float n_sum, float* loss_acc, float* loss_part) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[wave] = ce_sum; red[4 + wave] = n_sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float c = red[0] + red[1] + red[2] + red[3], n = red[4] + red[5] + red[6] + red[7];
+        if (loss_part) { loss_part[2 * blockIdx.x] = c; loss_part[2 * blockIdx.x + 1] = n; }
+        else if (n > 0.f) { atomicAdd(&loss_acc[0], c); atomicAdd(&loss_acc[1], n); }
+    }
+}
+
+// Score of the beam candidate (slot, token c) from the token's raw logit x: log_softmax, a finished slot masked (0 at END, f32 lowest elsewhere),
+// plus the slot's running log-prob; AL: a banned token scores -inf, also for a finished slot
+template <bool AL>
+LXO_DEV float cand_score(float x, float lse, int fin, float lp, int c, int id_end, const unsigned* ar) {
+    float sl = x - lse;
+    const float f = fin ? 1.f : 0.f;
+    sl = (1.f - f) * sl + f * (c == id_end ? 0.f : -3.40282347e38f);
+    float v = lp + sl;
+    if constexpr (AL) { if (!alw_ok(ar, c)) v = -INFINITY; }
+    return v;
+}
+// What slot tid of image b leaves behind at a beam step: its id and parent, v = its running log-prob after the step (state.log_probs), its finished flag
+LXO_DEV void beam_emit(int b, int k, int tid, int time, int id, int par, float v, int fin, int* ids_step, int* parents_step, int* ids_out, int* par_out,
+                       int max_steps, float* scores_out, float* logp, int* finished, int* n_unfinished) {
+    ids_step[b * k + tid] = id;
+    parents_step[b * k + tid] = par;
+    ids_out[((long long)b * max_steps + time) * k + tid] = id;
+    if (par_out) par_out[((long long)b * max_steps + time) * k + tid] = par;
+    if (scores_out) scores_out[((long long)b * max_steps + time) * k + tid] = v;
+    logp[b * k + tid] = v;
+    finished[b * k + tid] = fin;
+    if (!fin) atomicAdd(n_unfinished, 1);
+}
+
+// ---- loss ----
+// loss of img2seq.py:68-75 + gradient; one wave per (t, b) row, rows strided over the grid, three strided passes per row
+template <typename CT>
+__global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                     const int* __restrict__ lengths, CT* __restrict__ dlogits,
+                                                     float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
+                                                     const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    __shared__ float red[8];
+    inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float ce_sum = 0.f, n_sum = 0.f;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const RowTok r = row_tok(row, B, T, lengths);
+        const float* lg = logits + (long long)row * Vp;
+        CT* dl = dlogits + (long long)row * Vp;
+        const int tgt = row_target(formula, r.o, V);
+        const float lse = strided_lse<false>(lg, lane, V, nullptr);
+        const float scale = r.live ? inv_ntok : 0.f;
+        for (int j = lane; j < Vp; j += 64) {
+            float g = 0.f;
+            if (j < V) g = (expf(lg[j] - lse) - (j == tgt ? 1.f : 0.f)) * scale;
+            dl[j] = from_f32<CT>(g);
+        }
+        if (r.live) { ce_sum += lse - lg[tgt]; n_sum += 1.0f; }
+    }
+    ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
+}
+
+// The same with the row held in registers (Vp <= 64 * KV): ONE pass over the logits instead of three passes of 4-byte loads, and every row
+// has its own wave from the start (the three-pass kernel: 31 us for 13 MB at the benchmark shape, a chain of dependent passes per row; this one 8).
+template <typename CT, int KV>
+__global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                          const int* __restrict__ lengths, CT* __restrict__ dlogits,
+                                                          float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
+                                                          const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    constexpr bool BF = is_bf16<CT>::value;
+    __shared__ float red[8];
+    inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float ce_sum = 0.f, n_sum = 0.f;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const RowTok r = row_tok(row, B, T, lengths);
+        const float* lg = logits + (long long)row * Vp;
+        CT* dl = dlogits + (long long)row * Vp;
+        const int tgt = row_target(formula, r.o, V);
+        const float xt = lg[tgt];
+        float x[KV];
+        row_load<KV>(lg, lane, V, Vp, x);
+        const float lse = row_lse<BF, KV>(x);
+        const float scale = r.live ? inv_ntok : 0.f;
+#pragma unroll
+        for (int q = 0; q < KV / 4; ++q) {
+            const int j0 = 4 * (lane + 64 * q);
+            if (j0 >= Vp) continue;
+            float g[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = j0 + e;
+                const float pr = row_exp<BF>(x[4 * q + e] - lse);
+                g[e] = j < V ? (pr - (j == tgt ? 1.f : 0.f)) * scale : 0.f;
+            }
+            if constexpr (BF) { const u32x2 pk = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])}; *reinterpret_cast<u32x2*>(dl + j0) = pk; }
+            else { const f32x4 gv = {g[0], g[1], g[2], g[3]}; *reinterpret_cast<f32x4*>(dl + j0) = gv; }
+        }
+        if (r.live) { ce_sum += lse - xt; n_sum += 1.0f; }
+    }
+    ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
+}
+
+// ---- teacher-forced scoring (lxo_score_tokens) ----
+// Forward-only read-out of the training logits: logp_out[b][t] = logits[row][formula[b][t]] - lse(row) and top1_out[b][t] (nullable) =
+// the row's first maximum (argmax_kernel's rule: the lower index on ties), row = t * B + b.  No d(logits), no loss statistics, no atomics.
+// One wave per row with the row in registers, ce_loss_rows_kernel's row steps: -sum logp over the live tokens is that kernel's sum CE up to
+// summation order.  Rows t >= lengths[b]: logp 0, top1 -1.  A failed forward chain (chain_err set): every logp NaN, every top1 -1, as the
+// CE kernel turns its loss into NaN.
+LXO_DEV void score_dead(bool bad, int lane, long long o, float* logp_out, int* top1_out) {
+    if (lane == 0) { logp_out[o] = bad ? __uint_as_float(0x7fc00000u) : 0.f; if (top1_out) top1_out[o] = -1; }
+}
+template <bool BF, int KV>
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                        const int* __restrict__ lengths, float* __restrict__ logp_out, int* __restrict__ top1_out,
+                                                        const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool bad = chain_err && chain_err[0] != 0u;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const RowTok r = row_tok(row, B, T, lengths);
+        if (bad || !r.live) { score_dead(bad, lane, r.o, logp_out, top1_out); continue; }
+        const float* lg = logits + (long long)row * Vp;
+        const int tgt = row_target(formula, r.o, V);
+        const float xt = lg[tgt];
+        float x[KV];
+        row_load<KV>(lg, lane, V, Vp, x);
+        const float lse = row_lse<BF, KV>(x);
+        float best = -3.0e38f; int bi = 0x7fffffff;
+        if (top1_out) {
+            // a lane's columns in ascending order (strict >: its first maximum), then the wave's (value desc, index asc)
+#pragma unroll
+            for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int j = 4 * (lane + 64 * q) + e;
+                    if (j < V && x[4 * q + e] > best) { best = x[4 * q + e]; bi = j; }
+                }
+            wave_argmax(best, bi);
+        }
+        if (lane == 0) { logp_out[r.o] = xt - lse; if (top1_out) top1_out[r.o] = bi < V ? bi : 0; }
+    }
+}
+
+// The same for any Vp (the row does not fit in registers): ce_loss_kernel's strided row steps (expf in both modes), so that its sum CE is
+// again -sum logp up to summation order.
+__global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                   const int* __restrict__ lengths, float* __restrict__ logp_out, int* __restrict__ top1_out,
+                                                   const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool bad = chain_err && chain_err[0] != 0u;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const RowTok r = row_tok(row, B, T, lengths);
+        if (bad || !r.live) { score_dead(bad, lane, r.o, logp_out, top1_out); continue; }
+        const float* lg = logits + (long long)row * Vp;
+        const int tgt = row_target(formula, r.o, V);
+        const float lse = strided_lse<false>(lg, lane, V, nullptr);
+        float best = -3.0e38f; int bi = 0x7fffffff;
+        if (top1_out) {
+            strided_argmax<false>(lg, lane, V, nullptr, best, bi);
+            wave_argmax(best, bi);
+        }
+        if (lane == 0) { logp_out[r.o] = lg[tgt] - lse; if (top1_out) top1_out[r.o] = bi < V ? bi : 0; }
+    }
+}
+
+// seq_out[b] = logp_out[b][0] + ... + logp_out[b][len - 1], one thread per sequence adding in ascending t: the f32 sum in np.float32's
+// left-to-right order, whatever the grid of the pass before; a failed forward chain: NaN.  The loads go out 16 at a time ahead of their
+// additions (one load after another, T = 101 took 21 us of dependent latency)
+__global__ __launch_bounds__(256) void score_seq_kernel(const float* __restrict__ logp, const int* __restrict__ lengths, float* __restrict__ seq_out,
+                                                       const unsigned* __restrict__ chain_err, int B, int T) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int n = lengths[b];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    const float* p = logp + (long long)b * T;
+    float s = 0.f;
+    for (int t0 = 0; t0 < n; t0 += 16) {
+        float v[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[e] = t0 + e < n ? p[t0 + e] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) if (t0 + e < n) s += v[e];
+    }
+    seq_out[b] = (chain_err && chain_err[0] != 0u) ? __uint_as_float(0x7fc00000u) : s;
+}
+
+// ---- decode ----
+// greedy_decoder_cell.py:58-64: id = argmax (first max), finished |= id == END; one wave per row.
+// logp_out (nullable) [n][max_steps]: log_softmax(logits)[id] = logits[id] - lse, the log-sum-exp from one more pass over the row the wave has read
+// PF: at a step inside its prefix a row emits the forced id f (logp: logits[f] - lse) and stays unfinished
+// AL: banned columns are skipped in the max pass and in the exp-sum pass (a forced id's log-prob is taken under the same renormalised distribution)
+template <bool PF, bool AL>
+__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int Vp, int V, int n, int id_end,
+                                                    int* __restrict__ ids_step, int* __restrict__ ids_out, int max_steps, int step,
+                                                    int* __restrict__ finished, int* __restrict__ n_unfinished, float* __restrict__ logp_out,
+                                                    DecPrefix pf, DecAllow al) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float* lg = logits + (long long)row * Vp;
+    const unsigned* ar = nullptr;
+    if constexpr (AL) ar = alw_row(al, row);
+    float best; int bi;
+    strided_argmax<AL>(lg, lane, V, ar, best, bi);
+    shfl_argmax(best, bi);
+    int fi = -1;                                               // PF: the forced id of this step (-1: a free step)
+    if constexpr (PF) { if (step < pfx_len(pf, row)) fi = pfx_id(pf, row, step, V); }
+    float lp = 0.f;
+    if (logp_out) {
+        lp = -logf(strided_expsum<AL>(lg, lane, V, ar, best));      // logits[id] - (best + log l), logits[id] = best
+        if constexpr (PF) { if (fi >= 0) lp += lg[fi] - best; }
+    }
+    if (lane == 0) {
+        if (bi >= V) bi = 0;
+        if constexpr (PF) { if (fi >= 0) bi = fi; }
+        if (logp_out) logp_out[(long long)row * max_steps + step] = lp;
+        ids_step[row] = bi;
+        ids_out[(long long)row * max_steps + step] = bi;
+        const int f = finished[row] | (bi == id_end && fi < 0 ? 1 : 0);
+        finished[row] = f;
+        if (!f) atomicAdd(n_unfinished, 1);
+    }
+}
+
+// One block per image: beam_search_decoder_cell.py:146-187.
+//  log_softmax, mask finished beams (0 at END, f32 lowest elsewhere), add running log-probs,
+//  top-k over k*V (beam 0 only at time 0), ids = idx % V, parents = idx / V, gather finished.
+// add_div_penalty (beam_search_decoder_cell.py:258-287, Li et al. 2016): score += log(div_gamma) * rank * bernoulli(div_prob),
+// rank = position of the entry in the descending sort of its hypothesis' V scores (ties: lower id first, as
+// tf.nn.top_k orders them).  Bernoulli draws: the counter hash of drop_scale on (time, image, beam, id).
+struct DivPen { float log_gamma; unsigned thr; unsigned seed; float* scratch; };   // log_gamma == 0 or thr == 0: off
+// PF (both beam kernels): at a step t < P inside image b's prefix every slot j takes the forced id with parent j, its running log-prob grows by
+// that id's log-prob, its finished flag stays, no diversity penalty -- the k slots stay identical, as in the initial state.  Step P selects
+// over slot 0 alone (what time 0 does without a prefix), later steps over all k V candidates.
+// AL (both beam kernels): the log-sum-exp runs over image b's allowed columns; a banned candidate (slot, token) scores -inf, also for a finished
+// hypothesis, and is never selected while an allowed one is left; the diversity rank of an allowed column counts the allowed columns ahead of it.
+template <bool PF, bool AL>
+__global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logits, int Vp, int V, int k, int id_end, int time, DivPen dp,
+                                                       float* __restrict__ logp, int* __restrict__ finished,
+                                                       int* __restrict__ ids_step, int* __restrict__ parents_step,
+                                                       int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
+                                                       int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf, DecAllow al) {
+    __shared__ float lse[16];
+    __shared__ float cand_v[16 * 4]; __shared__ int cand_i[16 * 4];
+    __shared__ float sel_v[16]; __shared__ int sel_i[16];
+    __shared__ int fin_old[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned* ar = nullptr;
+    if constexpr (AL) ar = alw_row(al, b);
+    // log-sum-exp per beam (one wave per beam, round-robin)
+    for (int j = wave; j < k; j += 4) {
+        const float s = strided_lse<AL>(logits + ((long long)b * k + j) * Vp, lane, V, ar);
+        if (lane == 0) lse[j] = s;
+    }
+    if (tid < k) fin_old[tid] = finished[b * k + tid];
+    __syncthreads();
+    int t0 = 0;                                                // PF: the image's prefix length -- its beam search starts there
+    if constexpr (PF) {
+        t0 = pfx_len(pf, b);
+        if (time < t0) {
+            if (tid < k) {
+                const int id = pfx_id(pf, b, time, V);
+                beam_emit(b, k, tid, time, id, tid, logp[b * k + tid] + (logits[((long long)b * k + tid) * Vp + id] - lse[tid]), fin_old[tid],
+                          ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
+            }
+            return;
+        }
+    }
+    const int nb = time > t0 ? k : 1;
+    const int total = nb * V;
+    const bool div = dp.log_gamma != 0.f && dp.thr != 0u;
+    float* pen = dp.scratch + (long long)b * k * Vp;
+    if (div) {
+        float* row0 = logits + (long long)b * k * Vp;
+        for (int i = tid; i < k * V; i += 256) {            // scores of every hypothesis, in place of its logits
+            const int j = i / V, c = i - j * V;
+            row0[j * Vp + c] = cand_score<AL>(row0[j * Vp + c], lse[j], fin_old[j], logp[b * k + j], c, id_end, ar);
+        }
+        __syncthreads();
+        for (int i = tid; i < k * V; i += 256) {
+            const int j = i / V, c = i - j * V;
+            const float* row = row0 + j * Vp;
+            const float v = row[c];
+            int rank = 0;
+            for (int q = 0; q < V; ++q) { const float w = row[q]; rank += (w > v || (w == v && q < c)) ? 1 : 0; }
+            const Drop dd = {dp.thr, 1.f, dp.seed, time, b * k + j, (int)gridDim.x * k};
+            pen[j * Vp + c] = v + dp.log_gamma * (float)rank * drop_scale(dd, 3u, 0, c, V);
+            if constexpr (AL) { if (!alw_ok(ar, c)) pen[j * Vp + c] = -INFINITY; }
+        }
+        __syncthreads();
+    }
+    for (int sel = 0; sel < k; ++sel) {
+        float best = -INFINITY; int bi = 0x7fffffff;
+        for (int i = tid; i < total; i += 256) {
+            const int j = i / V, c = i - j * V;
+            bool taken = false;
+            for (int q = 0; q < sel; ++q) taken |= (sel_i[q] == i);
+            if (taken) continue;
+            const float val = div ? pen[j * Vp + c]
+                                  : cand_score<AL>(logits[((long long)b * k + j) * Vp + c], lse[j], fin_old[j], logp[b * k + j], c, id_end, ar);
+            if (val > best || (val == best && i < bi)) { best = val; bi = i; }
+        }
+        shfl_argmax(best, bi);
+        if (lane == 0) { cand_v[wave] = best; cand_i[wave] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            float bv = cand_v[0]; int bx = cand_i[0];
+            for (int w = 1; w < 4; ++w)
+                if (cand_v[w] > bv || (cand_v[w] == bv && cand_i[w] < bx)) { bv = cand_v[w]; bx = cand_i[w]; }
+            sel_v[sel] = bv; sel_i[sel] = bx;
+        }
+        __syncthreads();
+    }
+    if (tid < k) {
+        const int idx = sel_i[tid];
+        const int id = idx % V, par = idx / V;
+        beam_emit(b, k, tid, time, id, par, sel_v[tid], fin_old[par] | (id == id_end ? 1 : 0),
+                  ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
+    }
+}
+
+// The same step with every candidate score held in REGISTERS (k * V <= BS_TH * BS_NPT = 4096, k <= 64 / BS_NW, no diversity penalty): beam_step_kernel re-reads and
+// re-forms all k * V scores (an integer division each) for every one of its k selections and makes two passes over a row for its
+// log-sum-exp -- 31 us of a 161 us beam-5 step at B = 64, on 64 workgroups.  Here a lane loads its share of a row ONCE (max, then the
+// exponentials, from registers), a thread forms its <= BS_NPT scores ONCE, and a selection is a register scan + the block-wide arg-max.
+// Same row steps, same summation order inside a wave, same tie rule (lower flat index first): the ids and parents are the slow kernel's.
+constexpr int BS_TH = 512, BS_NW = BS_TH / 64, BS_NPT = 4096 / BS_TH;      // 8 waves x 8 candidates per thread (it was 4 x 16: a selection round scans a thread's candidates, k rounds per step)
+template <bool PF, bool AL>
+__global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __restrict__ logits, int Vp, int V, int k, int id_end, int time,
+                                                            float* __restrict__ logp, int* __restrict__ finished,
+                                                            int* __restrict__ ids_step, int* __restrict__ parents_step,
+                                                            int* __restrict__ ids_out, int* __restrict__ par_out, int max_steps,
+                                                            int* __restrict__ n_unfinished, float* __restrict__ scores_out, DecPrefix pf, DecAllow al) {
+    __shared__ float lse[16];
+    __shared__ float sel_v[16]; __shared__ int sel_i[16];
+    __shared__ int fin_old[16];
+    __shared__ float lp_old[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float wc_v[BS_NW * 16]; __shared__ int wc_i[BS_NW * 16];      // the waves' k best each
+    int t0 = 0;                                                // PF: the image's prefix length (beam_step_kernel)
+    if constexpr (PF) t0 = pfx_len(pf, b);
+    const unsigned* ar = nullptr;                              // AL: the image's allowed-token bits
+    if constexpr (AL) ar = alw_row(al, b);
+    const int nb = time > t0 ? k : 1;
+    const int total = nb * V;
+    float raw[BS_NPT];                                         // raw logits of this thread's candidates (unconditional, clamped: requested before anything is waited for)
+    {
+        int jq = tid / V, cq = tid - jq * V;
+#pragma unroll
+        for (int u = 0; u < BS_NPT; ++u) {
+            const int j = min(jq, k - 1), c = cq;
+            cq += BS_TH;
+            while (cq >= V) { cq -= V; ++jq; }
+            raw[u] = logits[((long long)b * k + j) * Vp + c];
+        }
+    }
+    // log-sum-exp per hypothesis
+    if (V <= 64 * 8 && k <= BS_NW) {
+        // a wave takes hypothesis `wave` (a spare wave repeats the last one), the row in registers for its two passes
+        const float s = lane_row_lse<8, AL>(logits + ((long long)b * k + min(wave, k - 1)) * Vp, lane, V, ar);
+        if (lane == 0 && wave < k) lse[wave] = s;
+    } else
+    for (int j = wave; j < k; j += BS_NW) {                   // the general form: one wave per hypothesis, round-robin
+        const float* lg = logits + ((long long)b * k + j) * Vp;
+        const float s = V <= 64 * 16 ? lane_row_lse<16, AL>(lg, lane, V, ar) : strided_lse<AL>(lg, lane, V, ar);
+        if (lane == 0) lse[j] = s;
+    }
+    if (tid < k) { fin_old[tid] = finished[b * k + tid]; lp_old[tid] = logp[b * k + tid]; }
+    __syncthreads();
+    if constexpr (PF) {
+        if (time < t0) {
+            if (tid < k) {
+                const int id = pfx_id(pf, b, time, V);
+                beam_emit(b, k, tid, time, id, tid, lp_old[tid] + (logits[((long long)b * k + tid) * Vp + id] - lse[tid]), fin_old[tid],
+                          ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
+            }
+            return;
+        }
+    }
+    // candidates of this thread: i = tid + BS_TH u -> (hypothesis, id) walked instead of divided; their raw logits were requested in front of the
+    // log-sum-exp pass (raw[]: the second read of the rows no longer waits behind the first)
+    float val[BS_NPT];
+    {
+        int jq = tid / V, cq = tid - jq * V;
+#pragma unroll
+        for (int u = 0; u < BS_NPT; ++u) {
+            const int i = tid + BS_TH * u;
+            val[u] = -INFINITY;
+            const int j = jq, c = cq;
+            cq += BS_TH;
+            while (cq >= V) { cq -= V; ++jq; }
+            if (i < total) val[u] = cand_score<AL>(raw[u], lse[j], fin_old[j], lp_old[j], c, id_end, ar);
+        }
+    }
+    // top-k in two stages, ONE workgroup barrier between them (it was two per selection): every wave selects the k best of ITS candidates by itself
+    // -- the k best of the block are among them -- then wave 0 selects the k best of the BS_NW k survivors, one per lane.  Order everywhere:
+    // value descending, flat index ascending (tf.nn.top_k over the flattened [k * V] scores: the lower index of equal values first).
+    {
+        unsigned taken = 0u;                                   // bit u: this thread's candidate u has been selected
+        for (int sel = 0; sel < k; ++sel) {
+            float best = -INFINITY; int bi = 0x7fffffff;
+#pragma unroll
+            for (int u = 0; u < BS_NPT; ++u) {
+                const int i = tid + BS_TH * u;
+                if (i < total && !((taken >> u) & 1u) && (val[u] > best || (val[u] == best && i < bi))) { best = val[u]; bi = i; }
+            }
+            wave_argmax(best, bi);
+            if (lane == 0) { wc_v[wave * 16 + sel] = best; wc_i[wave * 16 + sel] = bi; }
+#pragma unroll
+            for (int u = 0; u < BS_NPT; ++u) if (tid + BS_TH * u == bi) taken |= 1u << u;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int w = lane / k, e = lane - w * k;              // survivor e of wave w (BS_NW k <= 64 lanes: the launcher's condition)
+        float cv = -INFINITY; int ci = 0x7fffffff;
+        if (w < BS_NW) { cv = wc_v[w * 16 + e]; ci = wc_i[w * 16 + e]; }
+        for (int sel = 0; sel < k; ++sel) {
+            float bv = cv; int bx = ci;
+            wave_argmax(bv, bx);
+            if (lane == 0) { sel_v[sel] = bv; sel_i[sel] = bx; }
+            if (ci == bx) { cv = -INFINITY; ci = 0x7fffffff; }
+        }
+    }
+    __syncthreads();
+    if (tid < k) {
+        const int idx = sel_i[tid];
+        const int id = idx % V, par = idx / V;
+        beam_emit(b, k, tid, time, id, par, sel_v[tid], fin_old[par] | (id == id_end ? 1 : 0),
+                  ids_step, parents_step, ids_out, par_out, max_steps, scores_out, logp, finished, n_unfinished);
+    }
+}
+
+}  // namespace
+
+#define LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, __VA_ARGS__)
+#define DONE return (int)hipGetLastError()
+// the register-row kernels' KV from the padded vocabulary: ROWS(KV) with 64 * KV >= Vp
+#define BY_KV(Vp, ROWS) do { if ((Vp) <= 256) ROWS(4); else if ((Vp) <= 512) ROWS(8); else ROWS(16); } while (0)
+
+int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
+                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st) {
+    int g = cdiv(T * B, 4);
+    float* part = (det.p && det.floats >= 1024) ? det.p : nullptr;      // loss_acc is zero on entry (lxo_impl_ce_loss)
+#define CE_ARGS(CT_) logits, formula, lengths, (CT_*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp
+    if (Vp % 4 == 0 && Vp <= 1024 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0) {
+        // a wave per row, the row in registers (one pass); the f32 parity mode keeps at most 512 workgroups (its ordered partial sums)
+        if (g > (part ? 512 : 2048)) g = part ? 512 : 2048;
+#define CE_ROWS(KV_) do { if (dt == LXO_BF16) LAUNCH((ce_loss_rows_kernel<bf16_t, KV_>), g, CE_ARGS(bf16_t)); else LAUNCH((ce_loss_rows_kernel<float, KV_>), g, CE_ARGS(float)); } while (0)
+        BY_KV(Vp, CE_ROWS);
+#undef CE_ROWS
+    } else {
+        if (g > 512) g = 512;
+        if (dt == LXO_BF16) LAUNCH((ce_loss_kernel<bf16_t>), g, CE_ARGS(bf16_t));
+        else LAUNCH((ce_loss_kernel<float>), g, CE_ARGS(float));
+    }
+#undef CE_ARGS
+    if (part) return lxo_k_det_reduce(part, g, 2, 2, loss_acc, st);
+    DONE;
+}
+int lxo_k_score(int dt, const float* logits, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out,
+                const unsigned* chain_err, int B, int T, int V, int Vp, hipStream_t st) {
+    int g = cdiv(T * B, 4);
+#define SC_ARGS logits, formula, lengths, logp_out, top1_out, chain_err, B, T, V, Vp
+    if (Vp % 4 == 0 && Vp <= 1024 && ((uintptr_t)logits & 15) == 0) {
+        if (g > 2048) g = 2048;
+#define SC_ROWS(KV_) do { if (dt == LXO_BF16) LAUNCH((score_rows_kernel<true, KV_>), g, SC_ARGS); else LAUNCH((score_rows_kernel<false, KV_>), g, SC_ARGS); } while (0)
+        BY_KV(Vp, SC_ROWS);
+#undef SC_ROWS
+    } else {
+        LAUNCH(score_kernel, g > 512 ? 512 : g, SC_ARGS);
+    }
+#undef SC_ARGS
+    if (seq_out) LAUNCH(score_seq_kernel, cdiv(B, 256), logp_out, lengths, seq_out, chain_err, B, T);
+    DONE;
+}
+// The decode kernels' compile-time flags from the call's nullable arguments: KERNEL<PF, AL> with PF = a forced prefix, AL = allowed-token sets
+#define DEC_VARIANT(KERNEL, grid, block, ...)                                                                         \
+    do {                                                                                                               \
+        if (prefix && allow) hipLaunchKernelGGL((KERNEL<true, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);    \
+        else if (prefix) hipLaunchKernelGGL((KERNEL<true, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);       \
+        else if (allow) hipLaunchKernelGGL((KERNEL<false, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);        \
+        else hipLaunchKernelGGL((KERNEL<false, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);                  \
+    } while (0)
+int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
+                 int* finished, int* n_unfinished, hipStream_t st, float* logp_out, const DecPrefix* prefix, const DecAllow* allow) {
+    const DecPrefix pf = prefix ? *prefix : DecPrefix{};
+    const DecAllow al = allow ? *allow : DecAllow{};
+    DEC_VARIANT(argmax_kernel, cdiv(n, 4), 256, logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, pf, al);
+    DONE;
+}
+int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
+                    float* scratch, float* logp, int* finished,
+                    int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,
+                    float* scores_out, const DecPrefix* prefix, const DecAllow* allow) {
+    if (k > 16 || k > V) return -2;                            // k > V: at time 0 only V candidates exist -- a k-th selection would have no index
+    DivPen dp = {0.f, 0u, (unsigned)div_seed, scratch};
+    if (div_gamma > 0.f && div_gamma != 1.f && div_prob > 0.f) {      // the reference returns early for gamma == 1 or prob == 0
+        dp.log_gamma = logf(div_gamma);
+        dp.thr = div_prob >= 1.f ? 16777216u : (unsigned)(div_prob * 16777216.0f);
+    }
+    static int fast = -1;                                      // LXO_BEAM_FAST=0: the general kernel always (A/B)
+    if (fast < 0) { const char* e = getenv("LXO_BEAM_FAST"); fast = (e && e[0] == '0') ? 0 : 1; }
+    const DecPrefix pf = prefix ? *prefix : DecPrefix{};
+    const DecAllow al = allow ? *allow : DecAllow{};
+    if (fast && dp.log_gamma == 0.f && (long long)k * V <= BS_TH * BS_NPT && k * BS_NW <= 64) {
+        DEC_VARIANT(beam_step_fast_kernel, nimg, BS_TH, logits, Vp, V, k, id_end, time, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf, al);
+    } else
+        DEC_VARIANT(beam_step_kernel, nimg, 256, logits, Vp, V, k, id_end, time, dp, logp, finished, ids_step, parents_step, ids_out, par_out, max_steps, n_unfinished, scores_out, pf, al);
+    DONE;
+}

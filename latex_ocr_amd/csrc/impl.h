@@ -1,7 +1,7 @@
 // Internal entry points behind the C ABI (one per extern "C" function of lxo.h).
 #pragma once
 #include "plan.h"
-struct DecPrefix;                     // decoder_kernels.h
+struct DecPrefix;                     // head_kernels.h
 struct DecAllow;
 const char* lxo_ws_name(int id);
 int lxo_impl_pack_weights(const Plan& P, const float* prm, void* wp, hipStream_t st);
@@ -15,7 +15,7 @@ int lxo_impl_score_tokens(const Plan& P, void* ws, const int* formula, const int
 int lxo_impl_decoder_train_bwd(const Plan& P, const float* prm, const void* wp, void* ws, const int* formula, float* grads, int parts, hipStream_t st,
                                bool defer_join = false, void* ready = nullptr);
 // Where a whole-loop decode writes and what it is forced to emit (device arrays; all but ids nullable): scores = the token log-probs
-// (greedy) / the running log-probs (beam), alpha = the attention maps, prefix = forced ids, allow = the images' allowed-token sets (decoder_kernels.h).  Greedy has no parents.
+// (greedy) / the running log-probs (beam), alpha = the attention maps, prefix = forced ids, allow = the images' allowed-token sets (head_kernels.h).  Greedy has no parents.
 struct DecodeOuts { int* ids; int* parents; float* scores; float* alpha; const DecPrefix* prefix; const DecAllow* allow; };
 int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out, int* steps_out, hipStream_t st);
 int lxo_impl_decode_begin(const Plan& P, const float* prm, const void* wp, void* ws, hipStream_t st);

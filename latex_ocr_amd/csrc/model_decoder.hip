@@ -5,7 +5,7 @@
 #include "plan.h"
 #include "impl.h"
 #include "gemm.h"
-#include "decoder_kernels.h"
+#include "head_kernels.h"
 #include "rstep.h"
 #include "xdec.h"
 #include "dimg.h"
