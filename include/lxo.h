@@ -237,6 +237,24 @@ int lxo_ce_loss_fwd_bwd_dev(const lxo_shape* s, void* ws, const int32_t* formula
  * (the caller should refuse them).  When the forward chain's error word is set every logp / seq is NaN and every top1 -1. */
 int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
                      float* logp_out, int32_t* top1_out, float* seq_out, void* stream);
+/* Alternatives per position, after lxo_decoder_train_fwd with the same shape and formula: the model's k best tokens at every step of the
+ * teacher-forced pass, the rank of the given token and the entropy of the step; reads ws region "logits" and the forward chain's error
+ * word, writes only the caller's outputs (device), uses no workspace region of its own.  1 <= k <= min(16, V).
+ * ORDER: value descending on the raw f32 logits, then token id ascending -- exact ties go to the lower id, as greedy decode picks.
+ * ids_out int32 [B, T, k] (NOT NULL): slot j = the j-th token of step t in that order.  logp_out f32 [B, T, k] (NOT NULL): its
+ * log_softmax.  rank_out int32 [B, T] (nullable): the number of tokens in front of formula[b][t] in that order (0 = it is the model's
+ * top-1).  entropy_out f32 [B, T] (nullable): sum_v p_v (lse - x_v), in nats.
+ * Bit identities with lxo_score_tokens on the same workspace: ids_out[b][t][0] is its top1_out[b][t]; a slot whose id is the (clamped)
+ * formula token carries its logp_out[b][t], and that slot's index is rank_out[b][t].
+ * allow / allow_ld: allowed-token sets as in lxo_greedy_decode_constrained (one row per sample b), or NULL / 0 for none.  A banned token
+ * is a column outside the vocabulary: the log-sum-exp, the selection, the rank and the entropy run over the allowed tokens; a banned
+ * formula token has rank -1; where fewer than k tokens are allowed the remaining slots are id -1, logp -inf.  Words of a set are read
+ * inside [0, (V + 31) / 32) only.
+ * t >= lengths[b]: ids -1, logp 0, rank -1, entropy 0.  Forward chain's error word set: ids -1, logp NaN, rank -1, entropy NaN, everywhere.
+ * -1: a NULL ids_out or logp_out, k out of range, a non-NULL allow with 0 < allow_ld < (V + 31) / 32, a NULL allow with allow_ld != 0. */
+int lxo_score_alternatives(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths, int k,
+                           const uint32_t* allow, int allow_ld, int32_t* ids_out, float* logp_out,
+                           int32_t* rank_out, float* entropy_out, void* stream);
 /* BPTT through the decoder (what TF autodiff does for img2seq.py:119-123);
  * accumulates decoder gradients into grads and leaves d(enc) in ws region "d_img" (bf16 mode: already masked by conv6's
  * ReLU and converted, with conv6's bias gradient added to grads; f32 mode: the plain f32 gradient). */

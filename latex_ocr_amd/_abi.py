@@ -76,6 +76,7 @@ def bind(lib):
         "lxo_greedy_decode_scores": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_void, c_void, P(c_int), c_void]),
         "lxo_beam_decode_scores": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_void, P(c_int), c_void]),
         "lxo_score_tokens": (c_int, [S, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+        "lxo_score_alternatives": (c_int, [S, c_void, c_void, c_void, c_int, c_void, c_int, c_void, c_void, c_void, c_void, c_void]),
         "lxo_greedy_decode_prefix": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_void, c_void, c_void, P(c_int), c_void]),
         "lxo_beam_decode_prefix": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_void, c_void, c_void, c_void, P(c_int), c_void]),
         "lxo_greedy_decode_constrained": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_int, c_void, c_void, c_void, c_void, P(c_int), c_void]),
@@ -112,7 +113,7 @@ ENTRY_POINTS = ["lxo_last_error", "lxo_version", "lxo_shape_size", "lxo_ws_regio
                 "lxo_param_total", "lxo_param_info", "lxo_wpack_bytes", "lxo_workspace_bytes", "lxo_ws_region",
                 "lxo_pack_weights", "lxo_encoder_fwd", "lxo_encoder_bwd", "lxo_encoder_bwd_ready", "lxo_train_bwd", "lxo_set_side_stream", "lxo_set_encoder_side_stream", "lxo_decoder_train_fwd",
                 "lxo_ce_loss_fwd_bwd", "lxo_ce_loss_fwd_bwd_dev", "lxo_decoder_train_bwd", "lxo_decoder_train_bwd_part", "lxo_global_norm_scale", "lxo_adam_step", "lxo_optimizer_step",
-                "lxo_greedy_decode", "lxo_greedy_decode_attn", "lxo_beam_decode", "lxo_beam_decode_attn", "lxo_greedy_decode_scores", "lxo_beam_decode_scores", "lxo_score_tokens", "lxo_greedy_decode_prefix", "lxo_beam_decode_prefix", "lxo_greedy_decode_constrained", "lxo_beam_decode_constrained", "lxo_decode_begin", "lxo_decode_step",
+                "lxo_greedy_decode", "lxo_greedy_decode_attn", "lxo_beam_decode", "lxo_beam_decode_attn", "lxo_greedy_decode_scores", "lxo_beam_decode_scores", "lxo_score_tokens", "lxo_score_alternatives", "lxo_greedy_decode_prefix", "lxo_beam_decode_prefix", "lxo_greedy_decode_constrained", "lxo_beam_decode_constrained", "lxo_decode_begin", "lxo_decode_step",
                 "lxo_chain_guard", "lxo_decode_state_get", "lxo_decode_state_set", "lxo_decode_cell_step",
                 "lxo_comm_unique_id", "lxo_comm_init", "lxo_comm_info", "lxo_allreduce_bucket", "lxo_comm_destroy", "lxo_comm_last_error"]
 

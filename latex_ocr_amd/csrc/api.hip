@@ -139,6 +139,22 @@ extern "C" int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* for
     CHECK_LAUNCH(lxo_impl_score_tokens(P, ws, formula, lengths, logp_out, top1_out, seq_out, (hipStream_t)stream), "lxo_score_tokens");
     return 0;
 }
+extern "C" int lxo_score_alternatives(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths, int k,
+                                      const uint32_t* allow, int allow_ld, int32_t* ids_out, float* logp_out,
+                                      int32_t* rank_out, float* entropy_out, void* stream) {
+    MAKE_PLAN(P, s);
+    if (s->T <= 0) return fail(-1, "T must be positive");
+    if (!ws || !formula || !lengths) return fail(-1, "lxo_score_alternatives: null workspace, formula or lengths");
+    if (!ids_out) return fail(-1, "lxo_score_alternatives: null ids_out");
+    if (!logp_out) return fail(-1, "lxo_score_alternatives: null logp_out");
+    if (k < 1 || k > 16 || k > P.s.V) return fail(-1, "lxo_score_alternatives: k outside 1 .. min(16, V)");
+    if (allow && (allow_ld < 0 || (allow_ld != 0 && allow_ld < (P.s.V + 31) / 32))) return fail(-1, "lxo_score_alternatives: allow_ld must be 0 or >= (V + 31) / 32");
+    if (!allow && allow_ld != 0) return fail(-1, "lxo_score_alternatives: null allow with allow_ld != 0");
+    const DecAllow al = {allow, allow_ld};
+    CHECK_LAUNCH(lxo_impl_score_alternatives(P, ws, formula, lengths, k, allow ? &al : nullptr, ids_out, logp_out, rank_out, entropy_out, (hipStream_t)stream),
+                 "lxo_score_alternatives");
+    return 0;
+}
 extern "C" int lxo_decoder_train_bwd(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                                      const int32_t* formula, float* grads, void* stream) {
     MAKE_PLAN(P, s);

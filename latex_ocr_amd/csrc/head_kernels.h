@@ -14,6 +14,12 @@ struct DecPrefix { const int* ids; const int* len; int ld; int lim; };
 // Allowed-token sets (lxo_greedy_decode_constrained / lxo_beam_decode_constrained), device bit sets: bit v & 31 of word v >> 5 of row b set = image b
 // may emit token v; ld words per row, 0 = one row shared by every image.  A banned column is read as a column outside the vocabulary
 struct DecAllow { const unsigned* bits; int ld; };
+// alternatives per position of the same logits: ids_out / logp_out [B][T][k] = the k first columns of row t * B + b (value descending, then column
+// ascending) and logits[id] - lse, rank_out [B][T] (nullable) = the columns in front of the clamped target, ent_out [B][T] (nullable) = sum p (lse - x);
+// allow (nullable): one row per sample b, everything then runs over its allowed columns (banned target: rank -1; no column left: -1 / -inf);
+// rows t >= lengths[b]: -1 / 0 / -1 / 0; chain_err set: -1 / NaN / -1 / NaN.  1 <= k <= min(16, V), else -2.  Reads the logits only.
+int lxo_k_score_alt(int dt, const float* logits, const int* formula, const int* lengths, int k, const DecAllow* allow, int* ids_out, float* logp_out,
+                    int* rank_out, float* ent_out, const unsigned* chain_err, int B, int T, int V, int Vp, hipStream_t st);
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
                  int* finished, int* n_unfinished, hipStream_t st, float* logp_out = nullptr,      // logp_out (nullable): [n][max_steps] log-prob of the id
                  const DecPrefix* prefix = nullptr, const DecAllow* allow = nullptr);

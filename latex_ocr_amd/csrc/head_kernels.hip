@@ -1,4 +1,4 @@
-// The output head: every kernel that reads a row of logits and turns it into a loss (ce_loss*), a log-prob (score*) or a token
+// The output head: every kernel that reads a row of logits and turns it into a loss (ce_loss*), a log-prob (score*), a choice list (score_alt*) or a token
 // (argmax_kernel, beam_step*), their launchers, and -- first -- the row steps they are made of.
 #include "head_kernels.h"
 #include "drop.h"
@@ -123,6 +123,86 @@ LXO_DEV void wave_argmax(float& v, int& i) {
     }
 }
 #endif
+
+// Alternatives (the score_alt kernels): the k first columns of a row, the target's rank and the step's entropy.  ONE total order on the raw
+// f32 logits -- value descending, then column ascending -- and `alt_before` is the only place that states it.
+LXO_DEV bool alt_before(float x, int c, float y, int d) { return x > y || (x == y && c < d); }      // (x, c) comes strictly before (y, d)
+LXO_DEV int wave_sum_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// Register row: bit 4 q + e of the result = the lane's column 4 (lane + 64 q) + e counts (inside [0, V), AL: and allowed); AL: a banned column is
+// masked here, right after the load, to the value a column >= V carries
+template <int KV, bool AL>
+LXO_DEV unsigned row_counts(int lane, int V, const unsigned* ar, float (&x)[KV]) {
+    unsigned ok = 0u;
+#pragma unroll
+    for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * (lane + 64 * q) + e;
+            bool on = c < V;
+            if constexpr (AL) { on = on && alw_ok(ar, c < V ? c : 0); if (!on) x[4 * q + e] = -3.0e38f; }
+            ok |= (on ? 1u : 0u) << (4 * q + e);
+        }
+    return ok;
+}
+// a lane's first maximum among its columns that come strictly after (pv, pi) -- slot j of the selection is the maximum of what comes after slot
+// j - 1, so nothing is overwritten and no taken-list is kept; (+inf, -1) in front of slot 0.  None left: (-inf, 0x7fffffff).  A wave arg-max follows
+template <int KV>
+LXO_DEV void row_next(const float (&x)[KV], unsigned ok, int lane, float pv, int pi, float& best, int& bi) {
+    best = -INFINITY; bi = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * (lane + 64 * q) + e;
+            const float v = x[4 * q + e];
+            if (((ok >> (4 * q + e)) & 1u) && alt_before(pv, pi, v, c) && v > best) { best = v; bi = c; }
+        }
+}
+// the wave's number of counting columns in front of (xt, tgt): the target's rank
+template <int KV>
+LXO_DEV int row_rank(const float (&x)[KV], unsigned ok, int lane, float xt, int tgt) {
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            n += (((ok >> (4 * q + e)) & 1u) && alt_before(x[4 * q + e], 4 * (lane + 64 * q) + e, xt, tgt)) ? 1 : 0;
+    return wave_sum_i(n);
+}
+// the wave's entropy sum p (lse - x), p = e^(x - lse), over the counting columns: every term >= 0 (lse - sum p x cancels at |x| ~ 100), a lane's
+// columns first, then the wave, as row_lse adds; a column that does not count is skipped, never multiplied in
+template <bool FAST, int KV>
+LXO_DEV float row_entropy(const float (&x)[KV], unsigned ok, float lse) {
+    float h = 0.f;
+#pragma unroll
+    for (int e = 0; e < KV; ++e) if ((ok >> e) & 1u) h += row_exp<FAST>(x[e] - lse) * (lse - x[e]);
+    return wave_sum(h);
+}
+// The same three steps on a strided row: a pass over the row (it sits in L2) each
+template <bool AL>
+LXO_DEV void strided_next(const float* lg, int lane, int V, const unsigned* ar, float pv, int pi, float& best, int& bi) {
+    best = -INFINITY; bi = 0x7fffffff;
+    for (int j = lane; j < V; j += 64) {
+        const float v = lg[j];
+        if ((!AL || alw_ok(ar, j)) && alt_before(pv, pi, v, j) && v > best) { best = v; bi = j; }
+    }
+}
+template <bool AL>
+LXO_DEV int strided_rank(const float* lg, int lane, int V, const unsigned* ar, float xt, int tgt) {
+    int n = 0;
+    for (int j = lane; j < V; j += 64) n += ((!AL || alw_ok(ar, j)) && alt_before(lg[j], j, xt, tgt)) ? 1 : 0;
+    return wave_sum_i(n);
+}
+template <bool AL>
+LXO_DEV float strided_entropy(const float* lg, int lane, int V, const unsigned* ar, float lse) {
+    float h = 0.f;
+    for (int j = lane; j < V; j += 64) if (!AL || alw_ok(ar, j)) { const float v = lg[j]; h += expf(v - lse) * (lse - v); }
+    return wave_sum(h);
+}
 
 // Row of the loss and scoring kernels: row = t * B + b reads formula[b][t] (o = its flat index), live while t < lengths[b]; the target clamped into [0, V)
 struct RowTok { int t, b; long long o; bool live; };
@@ -329,6 +409,99 @@ __global__ __launch_bounds__(256) void score_seq_kernel(const float* __restrict_
         for (int e = 0; e < 16; ++e) if (t0 + e < n) s += v[e];
     }
     seq_out[b] = (chain_err && chain_err[0] != 0u) ? __uint_as_float(0x7fc00000u) : s;
+}
+
+// ---- alternatives per position (lxo_score_alternatives) ----
+// Read-out of the same logits: ids_out / logp_out [B][T][k] = the k first columns of row t * B + b in alt_before's order and their log-probs
+// x[id] - lse, rank_out [B][T] (nullable) = how many columns come before the target (0: it is the top-1), ent_out [B][T] (nullable) = the
+// entropy of the step.  Slot 0 is score_rows_kernel's arg-max and a slot that holds the target carries its logp_out, bit for bit (same lse
+// helper, same operands).  AL: everything runs over row b's allowed columns; a banned target has rank -1, slots beyond the allowed columns
+// are -1 / -inf.  Rows t >= lengths[b]: -1 / 0 / -1 / 0.  A failed forward chain: -1 / NaN / -1 / NaN.
+LXO_DEV void alt_dead(bool bad, int lane, int k, long long o, int* ids_out, float* logp_out, int* rank_out, float* ent_out) {
+    const float z = bad ? __uint_as_float(0x7fc00000u) : 0.f;
+    if (lane < k) { ids_out[o * k + lane] = -1; logp_out[o * k + lane] = z; }
+    if (lane == 0) { if (rank_out) rank_out[o] = -1; if (ent_out) ent_out[o] = z; }
+}
+// lane j holds slot j: (sv, si) = its logit and column, 0x7fffffff where the row had no column left
+LXO_DEV void alt_emit(int lane, int k, long long o, float sv, int si, float lse, int* ids_out, float* logp_out) {
+    if (lane < k) {
+        const bool none = si == 0x7fffffff;
+        ids_out[o * k + lane] = none ? -1 : si;
+        logp_out[o * k + lane] = none ? -INFINITY : sv - lse;
+    }
+}
+template <bool BF, int KV, bool AL>
+__global__ __launch_bounds__(256) void score_alt_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                            const int* __restrict__ lengths, int k, DecAllow al, int* __restrict__ ids_out,
+                                                            float* __restrict__ logp_out, int* __restrict__ rank_out, float* __restrict__ ent_out,
+                                                            const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool bad = chain_err && chain_err[0] != 0u;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const RowTok r = row_tok(row, B, T, lengths);
+        if (bad || !r.live) { alt_dead(bad, lane, k, r.o, ids_out, logp_out, rank_out, ent_out); continue; }
+        const float* lg = logits + (long long)row * Vp;
+        const unsigned* ar = nullptr;
+        if constexpr (AL) ar = alw_row(al, r.b);
+        const int tgt = row_target(formula, r.o, V);
+        const float xt = lg[tgt];
+        float x[KV];
+        row_load<KV>(lg, lane, V, Vp, x);
+        const unsigned ok = row_counts<KV, AL>(lane, V, ar, x);
+        const float lse = row_lse<BF, KV>(x);
+        float pv = INFINITY, sv = 0.f; int pi = -1, si = 0x7fffffff;
+        for (int j = 0; j < k; ++j) {
+            float best; int bi;
+            row_next<KV>(x, ok, lane, pv, pi, best, bi);
+            wave_argmax(best, bi);
+            if (lane == j) { sv = best; si = bi; }
+            pv = best; pi = bi;
+        }
+        alt_emit(lane, k, r.o, sv, si, lse, ids_out, logp_out);
+        if (rank_out) {
+            const int n = row_rank<KV>(x, ok, lane, xt, tgt);
+            if (lane == 0) rank_out[r.o] = (AL && !alw_ok(ar, tgt)) ? -1 : n;
+        }
+        if (ent_out) {
+            const float h = row_entropy<BF, KV>(x, ok, lse);
+            if (lane == 0) ent_out[r.o] = h;
+        }
+    }
+}
+// The same for any Vp: the strided row steps, k + 4 passes over a row
+template <bool AL>
+__global__ __launch_bounds__(256) void score_alt_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
+                                                       const int* __restrict__ lengths, int k, DecAllow al, int* __restrict__ ids_out,
+                                                       float* __restrict__ logp_out, int* __restrict__ rank_out, float* __restrict__ ent_out,
+                                                       const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool bad = chain_err && chain_err[0] != 0u;
+    for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
+        const RowTok r = row_tok(row, B, T, lengths);
+        if (bad || !r.live) { alt_dead(bad, lane, k, r.o, ids_out, logp_out, rank_out, ent_out); continue; }
+        const float* lg = logits + (long long)row * Vp;
+        const unsigned* ar = nullptr;
+        if constexpr (AL) ar = alw_row(al, r.b);
+        const int tgt = row_target(formula, r.o, V);
+        const float lse = strided_lse<AL>(lg, lane, V, ar);
+        float pv = INFINITY, sv = 0.f; int pi = -1, si = 0x7fffffff;
+        for (int j = 0; j < k; ++j) {
+            float best; int bi;
+            strided_next<AL>(lg, lane, V, ar, pv, pi, best, bi);
+            wave_argmax(best, bi);
+            if (lane == j) { sv = best; si = bi; }
+            pv = best; pi = bi;
+        }
+        alt_emit(lane, k, r.o, sv, si, lse, ids_out, logp_out);
+        if (rank_out) {
+            const int n = strided_rank<AL>(lg, lane, V, ar, lg[tgt], tgt);
+            if (lane == 0) rank_out[r.o] = (AL && !alw_ok(ar, tgt)) ? -1 : n;
+        }
+        if (ent_out) {
+            const float h = strided_entropy<AL>(lg, lane, V, ar, lse);
+            if (lane == 0) ent_out[r.o] = h;
+        }
+    }
 }
 
 // ---- decode ----
@@ -619,6 +792,26 @@ int lxo_k_score(int dt, const float* logits, const int* formula, const int* leng
     }
 #undef SC_ARGS
     if (seq_out) LAUNCH(score_seq_kernel, cdiv(B, 256), logp_out, lengths, seq_out, chain_err, B, T);
+    DONE;
+}
+int lxo_k_score_alt(int dt, const float* logits, const int* formula, const int* lengths, int k, const DecAllow* allow, int* ids_out, float* logp_out,
+                    int* rank_out, float* ent_out, const unsigned* chain_err, int B, int T, int V, int Vp, hipStream_t st) {
+    if (k < 1 || k > 16 || k > V) return -2;
+    int g = cdiv(T * B, 4);
+    const DecAllow al = allow ? *allow : DecAllow{};
+#define SA_ARGS logits, formula, lengths, k, al, ids_out, logp_out, rank_out, ent_out, chain_err, B, T, V, Vp
+    if (Vp % 4 == 0 && Vp <= 1024 && ((uintptr_t)logits & 15) == 0) {
+        if (g > 2048) g = 2048;
+#define SA_ROWS_AL(KV_, AL_) do { if (dt == LXO_BF16) LAUNCH((score_alt_rows_kernel<true, KV_, AL_>), g, SA_ARGS); else LAUNCH((score_alt_rows_kernel<false, KV_, AL_>), g, SA_ARGS); } while (0)
+#define SA_ROWS(KV_) do { if (allow) SA_ROWS_AL(KV_, true); else SA_ROWS_AL(KV_, false); } while (0)
+        BY_KV(Vp, SA_ROWS);
+#undef SA_ROWS
+#undef SA_ROWS_AL
+    } else {
+        if (g > 512) g = 512;
+        if (allow) LAUNCH(score_alt_kernel<true>, g, SA_ARGS); else LAUNCH(score_alt_kernel<false>, g, SA_ARGS);
+    }
+#undef SA_ARGS
     DONE;
 }
 // The decode kernels' compile-time flags from the call's nullable arguments: KERNEL<PF, AL> with PF = a forced prefix, AL = allowed-token sets

@@ -308,6 +308,13 @@ int lxo_impl_score_tokens(const Plan& P, void* ws, const int* formula, const int
                        P.bf ? P.ws<unsigned>(ws, W_XSYNC) + 8 * 64 : nullptr, P.s.B, P.s.T, P.s.V, P.Vp, st);
 }
 
+// ... and the alternatives at every position of the same logits (no workspace region of its own)
+int lxo_impl_score_alternatives(const Plan& P, void* ws, const int* formula, const int* lengths, int k, const DecAllow* allow, int* ids_out, float* logp_out,
+                                int* rank_out, float* ent_out, hipStream_t st) {
+    return lxo_k_score_alt(P.s.dtype, P.ws<float>(ws, W_LOGITS), formula, lengths, k, allow, ids_out, logp_out, rank_out, ent_out,
+                           P.bf ? P.ws<unsigned>(ws, W_XSYNC) + 8 * 64 : nullptr, P.s.B, P.s.T, P.s.V, P.Vp, st);
+}
+
 // The weight-gradient side stream of the encoder backward (model_encoder.hip: lxo_set_encoder_side_stream) also takes the decoder's
 // deferred all-step weight gradients (round 5): behind the backward chain the critical path is init states -> d_att_img (bound by the
 // transcendental rate) -> d_img -> conv6; the four dense dW GEMMs, d_z's column sum, the embedding gradient and dW_att_img feed nothing

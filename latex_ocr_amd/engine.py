@@ -8,13 +8,17 @@ there is no eager/PyTorch compute path and no CPU fallback here.
 import ctypes
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
 
 from . import _abi
 from .model import params as PP
+
+
+# Engine.score(alternatives=k): per position the k best token ids and their log-probs, the given token's rank and the step's entropy
+Alternatives = namedtuple("Alternatives", ["ids", "logp", "rank", "entropy"])
 
 
 def _p(t):
@@ -585,13 +589,19 @@ class Engine(object):
         s = self.loss(lengths, 1.0 / max(n, 1)).cpu().numpy()
         return float(s[0]), n
 
-    def score(self, img, formula, lengths, return_top1=False):
+    def score(self, img, formula, lengths, return_top1=False, alternatives=0, allowed=None):
         """Teacher-forced scoring of given formulas (lxo_score_tokens): -> (logp f32 [B, T], seq f32 [B]) or (logp, top1 int32 [B, T], seq),
         host arrays.  logp[b, t] = log_softmax(logits of step t)[formula[b, t]] for t < lengths[b], 0 after; top1[b, t] = the model's
         arg-max at step t (lower id on ties, the greedy rule), -1 after; seq[b] = the f32 sum of logp[b, :lengths[b]] in ascending t
         (-sum(seq) = evaluate_batch's CE sum up to summation order).  The forward is forward(img, formula) without dropout -- the chain
         batch padding comes with it -- and a batch above 64 is scored in consecutive pieces of at most 64 rows, so each piece can take
-        the persistent chain.  Touches no gradient, loss statistic or optimizer state."""
+        the persistent chain.  Touches no gradient, loss statistic or optimizer state.
+        alternatives = k > 0 (lxo_score_alternatives, 1 <= k <= min(16, V)): the tuple gains a last element Alternatives(ids int32 [B, T, k],
+        logp f32 [B, T, k], rank int32 [B, T], entropy f32 [B, T]) -- the model's k best tokens at every position (value descending, the lower
+        id on ties) with their log-probs, the rank of the given token (0 = the model's top-1) and the entropy of the step in nats; positions
+        t >= lengths[b]: -1 / 0 / -1 / 0.  allowed (with alternatives only): a boolean / 0-1 array [V] or [B, V] as the decode calls take it;
+        the alternatives then run over each row's allowed tokens (renormalised log-probs, rank -1 for a banned given token, id -1 / logp -inf
+        where fewer than k are allowed) while logp / top1 / seq stay the unconstrained values."""
         f = formula.detach().cpu().numpy() if isinstance(formula, torch.Tensor) else np.asarray(formula)
         ln = lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
         f = np.ascontiguousarray(f, dtype=np.int64)
@@ -604,11 +614,21 @@ class Engine(object):
         if ln.size and (ln.min() < 0 or ln.max() > f.shape[1]):
             raise ValueError("score: lengths must lie in [0, T = %d], got %d .. %d" % (f.shape[1], int(ln.min()), int(ln.max())))
         f, ln = f.astype(np.int32), ln.astype(np.int32)
-        parts = [self._score_piece(img[i:i + 64], f[i:i + 64], ln[i:i + 64], return_top1) for i in range(0, B, 64)]
+        k = int(alternatives)
+        if k == 0 and allowed is not None:
+            raise ValueError("score: allowed= constrains the alternatives only and needs alternatives > 0")
+        if k != 0 and not 1 <= k <= min(16, self.n_tok):
+            raise ValueError("score: alternatives must lie in 1 .. min(16, V = %d), got %d" % (self.n_tok, k))
+        al = self._allow_host(allowed, B, None, 1) if allowed is not None else None
+        parts = [self._score_piece(img[i:i + 64], f[i:i + 64], ln[i:i + 64], return_top1, k,
+                                   al if al is None or al.shape[0] == 1 else al[i:i + 64]) for i in range(0, B, 64)]
         logp, seq = np.concatenate([p[0] for p in parts]), np.concatenate([p[2] for p in parts])
-        return (logp, np.concatenate([p[1] for p in parts]), seq) if return_top1 else (logp, seq)
+        out = (logp, np.concatenate([p[1] for p in parts]), seq) if return_top1 else (logp, seq)
+        if k:
+            out += (Alternatives(*[np.concatenate([p[3][j] for p in parts]) for j in range(4)]),)
+        return out
 
-    def _score_piece(self, img, formula, lengths, top1_on):
+    def _score_piece(self, img, formula, lengths, top1_on, k=0, al=None):
         while True:
             self.forward(img, formula)
             B, T = int(self.shape.B), int(self.shape.T)
@@ -618,19 +638,32 @@ class Engine(object):
             ln_dev = self._lengths_dev(ln)
             chain = self._chains_possible()
             # ONE device buffer and one copy to the host: logp | top1 | seq | the forward chain's sync words (chain_status's slice)
-            buf = torch.empty(2 * n + B + (8 * 64 + 1 if chain else 0), dtype=torch.int32, device=self.device)
+            # (with alternatives: + ids [n, k] | their logp [n, k] | rank | entropy in front of the sync words)
+            na = 2 * n + B                                          # where the alternatives start
+            ns = na + (2 * n * k + 2 * n if k else 0)               # ... and the sync words
+            buf = torch.empty(ns + (8 * 64 + 1 if chain else 0), dtype=torch.int32, device=self.device)
             logp, top1, seq = buf[:n].view(torch.float32), buf[n:2 * n] if top1_on else None, buf[2 * n:2 * n + B].view(torch.float32)
             self._ck(self.lib.lxo_score_tokens(self.sref(), _p(self.ws), _p(self._formula), _p(ln_dev), _p(logp), _p(top1), _p(seq),
                                                self._stream()), "score_tokens")
+            if k:
+                alw = self._allow_args(al, live, B) if al is not None else (None, 0)
+                self._ck(self.lib.lxo_score_alternatives(self.sref(), _p(self.ws), _p(self._formula), _p(ln_dev), k, _p(alw[0]), alw[1],
+                                                         _p(buf[na:na + n * k]), _p(buf[na + n * k:na + 2 * n * k].view(torch.float32)),
+                                                         _p(buf[na + 2 * n * k:na + 2 * n * k + n]), _p(buf[na + 2 * n * k + n:ns].view(torch.float32)),
+                                                         self._stream()), "score_alternatives")
             if chain:
-                buf[2 * n + B:].copy_(self.region("xdec_sync", "i32")[:8 * 64 + 1])
+                buf[ns:].copy_(self.region("xdec_sync", "i32")[:8 * 64 + 1])
             h = buf.cpu().numpy()
             out = (h[:n].view(np.float32).reshape(B, T)[:live].copy(), h[n:2 * n].reshape(B, T)[:live].copy() if top1_on else None,
                    h[2 * n:2 * n + B].view(np.float32)[:live].copy())
+            if k:
+                a = h[na:ns]
+                out += ((a[:n * k].reshape(B, T, k)[:live].copy(), a[n * k:2 * n * k].view(np.float32).reshape(B, T, k)[:live].copy(),
+                         a[2 * n * k:2 * n * k + n].reshape(B, T)[:live].copy(), a[2 * n * k + n:].view(np.float32).reshape(B, T)[:live].copy()),)
             if chain:
                 # a chain that did not assemble (forward() checks the first one itself): the launch-per-step kernels from now on, and
                 # this piece again
-                w = h[2 * n + B:]
+                w = h[ns:]
                 used, err = bool(w[32:512:64].any()), int(w[512])
                 self.chain_used = used and not err
                 if err:
@@ -691,10 +724,11 @@ class Engine(object):
         if al.ndim != 2 or al.shape[1] != self.n_tok or al.shape[0] not in (1, B0):
             raise ValueError("allowed must be [V] or [B, V] for B = %d images and V = %d tokens, got shape %s" % (B0, self.n_tok, np.shape(allowed)))
         al = al.astype(bool)
-        if not 0 <= int(id_end) < self.n_tok:
-            raise ValueError("id_end = %d outside [0, %d)" % (int(id_end), self.n_tok))
-        if not al[:, int(id_end)].all():
-            raise ValueError("allowed rows %s ban id_end = %d" % (np.nonzero(~al[:, int(id_end)])[0].tolist(), int(id_end)))
+        if id_end is not None:                                     # (Engine.score: no decode, nothing has to end)
+            if not 0 <= int(id_end) < self.n_tok:
+                raise ValueError("id_end = %d outside [0, %d)" % (int(id_end), self.n_tok))
+            if not al[:, int(id_end)].all():
+                raise ValueError("allowed rows %s ban id_end = %d" % (np.nonzero(~al[:, int(id_end)])[0].tolist(), int(id_end)))
         need = max(1, int(beam_size))
         if (al.sum(1) < need).any():
             raise ValueError("allowed rows %s allow fewer than max(1, beam_size) = %d tokens" % (np.nonzero(al.sum(1) < need)[0].tolist(), need))

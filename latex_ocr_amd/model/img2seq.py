@@ -206,7 +206,7 @@ class Img2SeqModel(BaseModel):
         perp = -np.exp(ce_words / float(n_words))
         return files, perp
 
-    def predict_batch(self, images, return_scores=False, banned=None, allowed=None):
+    def predict_batch(self, images, return_scores=False, banned=None, allowed=None, alternatives=0):
         """Reference: model/img2seq.py:256-276.
         return_scores: -> (hyps, scores), scores[i][b] = (sequence log-prob, [log-prob of each token up to and including the first END]) of
         hypothesis hyps[i][b]; the sequence log-prob is the sum of the token log-probs.  Greedy: the hypotheses are the default call's.
@@ -216,8 +216,16 @@ class Img2SeqModel(BaseModel):
         penalised scores).
         banned / allowed: a token constraint (Engine greedy_decode / beam_decode with allowed=): token strings or ids, one list for all
         images or one list per image; a token outside an image's set is never emitted and the scores are renormalised over the set.
-        END must stay allowed.  E.g. banned=["_UNK", "_PAD"].  Nothing is banned by default."""
+        END must stay allowed.  E.g. banned=["_UNK", "_PAD"].  Nothing is banned by default.
+        alternatives = k > 0: -> (hyps, scores, alts), hyps and scores as with return_scores, alts[i][b] = one entry per emitted token of
+        hyps[i][b] (the first END included), as score_batch(alternatives=k) lists them: the model's k best tokens there, the emitted
+        token's rank and the step's entropy, under the same token sets.  They come from a SECOND, teacher-forced pass over the emitted
+        tokens (Engine.score, one per hypothesis slot), not from the decode itself: at a near-tie the slot-0 token of that pass may
+        differ from the emitted one, and in beam search the log-probs are the model's, not the (penalised) running scores the search
+        ranked by.  A path that ran into the length bound without END has no entry for an END it never emitted."""
         sets = self._token_sets(len(images), banned, allowed)
+        if alternatives:
+            return self._predict_scored(images, allowed=sets, alternatives=alternatives)
         if return_scores:
             return self._predict_scored(images, allowed=sets)
         fd = self._get_feed_dict(images, dropout=1)
@@ -229,32 +237,48 @@ class Img2SeqModel(BaseModel):
                 hyps[i].append(" ".join(self._vocab.id_to_tok[int(idx)] for idx in p))
         return hyps
 
-    def score_batch(self, images, formulas):
+    def _alt_entries(self, alt, b, n):
+        """positions [0, n) of row b of an Engine.score Alternatives as [{"rank", "entropy", "alternatives": [(token string, logp), ...]}]
+        (a slot beyond a row's allowed tokens, id -1, is left out)"""
+        tok = self._vocab.id_to_tok
+        return [{"rank": int(alt.rank[b, t]), "entropy": float(alt.entropy[b, t]),
+                 "alternatives": [(tok[int(i)], float(lp)) for i, lp in zip(alt.ids[b, t], alt.logp[b, t]) if i >= 0]} for t in range(n)]
+
+    def score_batch(self, images, formulas, alternatives=0, banned=None, allowed=None):
         """Teacher-forced scores of given transcriptions (Engine.score): formulas are token-id lists or space-separated token strings
         (Vocab.form_prepro: unknown tokens -> id_unk), padded as _get_feed_dict pads a training batch, so the END the reference appends is
         scored too.  -> one (sequence log-prob, [token log-probs incl. END], first position where the model's top-1 differs from the
-        formula or -1) per (image, formula) pair."""
+        formula or -1) per (image, formula) pair.
+        alternatives = k > 0 (Engine.score(alternatives=k)): each tuple gains a 4th element, one entry per scored position, the appended END
+        included: {"rank": the given token's rank among the model's choices (0 = its top-1), "entropy": of the step, in nats,
+        "alternatives": [(token string, log-prob), ... k], best first}.  banned / allowed (with alternatives only): token sets as in
+        predict_batch; the alternatives, ranks and entropies then run over each image's allowed tokens (a banned given token: rank -1, fewer
+        than k allowed: a shorter list), the first three elements stay the unconstrained scores."""
         if len(images) != len(formulas):
             raise ValueError("score_batch: %d images but %d formulas" % (len(images), len(formulas)))
         prepro = self._vocab.form_prepro
         forms = [prepro(f) if isinstance(f, str) else [int(x) for x in f] for f in formulas]
         fd = self._get_feed_dict(images, formula=forms, dropout=1)
         f, ln = fd["formula"], fd["formula_length"]
-        logp, top1, seq = self.engine.score(fd["img"], f, ln, return_top1=True)
+        res = self.engine.score(fd["img"], f, ln, return_top1=True, alternatives=int(alternatives),
+                                allowed=self._token_sets(len(images), banned, allowed))
+        logp, top1, seq = res[:3]
         out = []
         for b in range(len(forms)):
             n = int(ln[b])
             diff = np.flatnonzero(top1[b, :n] != f[b, :n])
-            out.append((float(seq[b]), [float(x) for x in logp[b, :n]], int(diff[0]) if diff.size else -1))
+            out.append((float(seq[b]), [float(x) for x in logp[b, :n]], int(diff[0]) if diff.size else -1)
+                       + ((self._alt_entries(res[3], b, n),) if alternatives else ()))
         return out
 
-    def complete_batch(self, images, prefixes, return_scores=False, banned=None, allowed=None):
+    def complete_batch(self, images, prefixes, return_scores=False, banned=None, allowed=None, alternatives=0):
         """Decode each image from a given prefix (Engine greedy_decode / beam_decode with prefix=): the prefixes are token-id lists or
         space-separated token strings (Vocab.form_prepro, as score_batch takes them, but no END is appended), one per image; "" or []
         decodes from the start.  config.decoding chooses greedy or beam search; beam hypotheses are the back-traced ones, as
         predict_batch(return_scores=True) returns them.  -> hyps (hyps[i][b]: hypothesis i of image b, its prefix included), or
         (hyps, scores) with return_scores, scores as in predict_batch (the forced tokens' log-probs included).
-        banned / allowed: as in predict_batch ("and not that token again"); a prefix token must be allowed for its image."""
+        banned / allowed: as in predict_batch ("and not that token again"); a prefix token must be allowed for its image.
+        alternatives = k > 0: -> (hyps, scores, alts) as in predict_batch (a second, teacher-forced pass; the forced tokens' positions included)."""
         if len(images) != len(prefixes):
             raise ValueError("complete_batch: %d images but %d prefixes" % (len(images), len(prefixes)))
         prepro = self._vocab.form_prepro
@@ -263,10 +287,10 @@ class Img2SeqModel(BaseModel):
         pf = np.zeros((len(forms), max(1, int(ln.max()) if ln.size else 1)), np.int32)
         for b, f in enumerate(forms):
             pf[b, :len(f)] = f
-        hyps, scores = self._predict_scored(images, pf, ln, self._token_sets(len(images), banned, allowed))
-        return (hyps, scores) if return_scores else hyps
+        out = self._predict_scored(images, pf, ln, self._token_sets(len(images), banned, allowed), alternatives=alternatives)
+        return out if return_scores or alternatives else out[0]
 
-    def _predict_scored(self, images, prefix=None, prefix_lengths=None, allowed=None):
+    def _predict_scored(self, images, prefix=None, prefix_lengths=None, allowed=None, alternatives=0):
         fd = self._get_feed_dict(images, dropout=1)
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1
@@ -283,15 +307,24 @@ class Img2SeqModel(BaseModel):
             ids, tok = ids[:, :, None], tok[:, :, None]
         k = ids.shape[2]
         hyps, scores = [[] for _ in range(k)], [[] for _ in range(k)]
+        emitted = np.zeros((ids.shape[0], k), np.int32)             # tokens of each path up to and including its first END
         for b in range(ids.shape[0]):
             for i in range(k):
                 path = ids[b, :, i]
                 end = np.flatnonzero(path == id_end)
-                n = int(end[0]) + 1 if end.size else len(path)
+                n = emitted[b, i] = int(end[0]) + 1 if end.size else len(path)
                 lp = [float(x) for x in tok[b, :n, i]]
                 hyps[i].append(" ".join(self._vocab.id_to_tok[int(idx)] for idx in truncate_end(path, id_end)))
                 scores[i].append((float(np.sum(np.asarray(lp, dtype=np.float64))), lp))
-        return hyps, scores
+        if not alternatives:
+            return hyps, scores
+        alts = []
+        for i in range(k):                                           # one teacher-forced pass per hypothesis slot, over what it emitted
+            T = max(1, int(emitted[:, i].max()))
+            f = np.where(np.arange(T)[None, :] < emitted[:, i, None], ids[:, :T, i], id_end).astype(np.int32)
+            alt = self.engine.score(fd["img"], f, emitted[:, i], alternatives=int(alternatives), allowed=allowed)[-1]
+            alts.append([self._alt_entries(alt, b, int(emitted[b, i])) for b in range(ids.shape[0])])
+        return hyps, scores, alts
 
     def predict(self, img):
         """Reference: model/img2seq.py:278-285."""

@@ -7,7 +7,11 @@ that transcription instead of decoding: its log-prob (END included), geometric-m
 the model's top-1 token differs from it (Img2SeqModel.score_batch).  --prefix "<tokens>" (one image) decodes from that prefix: the
 hypothesis keeps it and the model writes the rest (Img2SeqModel.complete_batch); it combines with --scores.  --ban "<tokens>" keeps those
 tokens out of every hypothesis (e.g. --ban "_UNK _PAD"), --allow-file FILE (one token per line; END is added) lets only those in; both
-combine with --scores and --prefix (predict_batch / complete_batch with banned= / allowed=)."""
+combine with --scores and --prefix (predict_batch / complete_batch with banned= / allowed=).  --alternatives K adds one line per position
+of the hypothesis (or, with --formula, of the given transcription): the token, its log-prob, its rank among the model's choices, the
+entropy of the step and the model's K best tokens there with their log-probs (predict_batch / complete_batch / score_batch with
+alternatives=K: for a decode they come from a second, teacher-forced pass over the emitted tokens); with --formula it combines with
+--ban / --allow-file, which then constrain the alternatives."""
 import argparse
 
 import numpy as np
@@ -26,6 +30,7 @@ def main(argv=None):
     ap.add_argument("--prefix", default=None, help="decode the (single) image from this space-separated token prefix")
     ap.add_argument("--ban", default=None, help="space-separated tokens that must not be emitted")
     ap.add_argument("--allow-file", default=None, help="file with one token per line: only these (and END) may be emitted")
+    ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="per position: the token's log-prob and rank, the entropy and the K best tokens")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     if a.formula is not None and len(a.images) != 1:
@@ -43,32 +48,55 @@ def main(argv=None):
     if a.allow_file is not None:
         with open(a.allow_file) as f:
             sets["allowed"] = [t for t in (line.strip() for line in f) if t] + [vocab.id_end]
-    if sets and a.formula is not None:
-        ap.error("--ban / --allow-file constrain a decode and do not combine with --formula")
+    if sets and a.formula is not None and not a.alternatives:
+        ap.error("--ban / --allow-file constrain a decode and do not combine with --formula (without --alternatives)")
+    if a.alternatives and not 1 <= a.alternatives <= min(16, vocab.n_tok):
+        ap.error("--alternatives takes 1 .. min(16, vocabulary size)")
+    alt = {"alternatives": a.alternatives} if a.alternatives else {}
+
+    def print_alternatives(tokens, logps, entries):
+        for t, (tok, lp, e) in enumerate(zip(tokens, logps, entries)):
+            print("  %3d %-12s logp %8.4f  rank %3d  entropy %.4f  | %s" % (t, tok, lp, e["rank"], e["entropy"],
+                                                                          "  ".join("%s %.4f" % c for c in e["alternatives"])))
+
+    def emitted(hyp, n):
+        toks = hyp.split()
+        return toks + [vocab.id_to_tok[vocab.id_end]] * (n - len(toks))
     from PIL import Image
     out = []
     for path in a.images:
         img = np.asarray(Image.open(path).convert("RGB"))
         if a.formula is not None:
-            lp, toks, first = model.score_batch([greyscale(img)], [a.formula])[0]
+            res = model.score_batch([greyscale(img)], [a.formula], **dict(alt, **sets))[0]
+            lp, toks, first = res[:3]
             print(path, "<=", a.formula, "\tlogp %.4f\tgeo-mean p %.4f\tfirst disagreement %d" % (lp, np.exp(lp / max(1, len(toks))), first))
-            out.append((lp, toks, first))
+            if alt:
+                print_alternatives(emitted(" ".join(vocab.id_to_tok[i] for i in vocab.form_prepro(a.formula)), len(toks)), toks, res[3])
+            out.append(res)
             continue
         if a.prefix is not None:
-            hyps, scores = model.complete_batch([greyscale(img)], [a.prefix], return_scores=True, **sets)
+            res = model.complete_batch([greyscale(img)], [a.prefix], return_scores=True, **dict(alt, **sets))
+            hyps, scores = res[:2]
             lp, toks = scores[0][0]
             if a.scores:
                 print(path, "=>", hyps[0][0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
             else:
                 print(path, "=>", hyps[0][0])
-            out.append(([h[0] for h in hyps], [s[0] for s in scores]) if a.scores else [h[0] for h in hyps])
+            if alt:
+                print_alternatives(emitted(hyps[0][0], len(toks)), toks, res[2][0][0])
+            out.append(([h[0] for h in hyps], [s[0] for s in scores]) + (([x[0] for x in res[2]],) if alt else ()) if a.scores or alt else [h[0] for h in hyps])
             continue
-        if a.scores:
-            hyps, scores = model.predict_batch([greyscale(img)], return_scores=True, **sets)
-            hyps = [h[0] for h in hyps]
+        if a.scores or alt:
+            res = model.predict_batch([greyscale(img)], return_scores=True, **dict(alt, **sets))
+            hyps, scores = [h[0] for h in res[0]], res[1]
             lp, toks = scores[0][0]
-            print(path, "=>", hyps[0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
-            out.append((hyps, [s[0] for s in scores]))
+            if a.scores:
+                print(path, "=>", hyps[0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
+            else:
+                print(path, "=>", hyps[0])
+            if alt:
+                print_alternatives(emitted(hyps[0], len(toks)), toks, res[2][0][0])
+            out.append((hyps, [s[0] for s in scores]) + (([x[0] for x in res[2]],) if alt else ()))
             continue
         hyps = [h[0] for h in model.predict_batch([greyscale(img)], **sets)] if sets else model.predict(greyscale(img))
         print(path, "=>", hyps[0])
