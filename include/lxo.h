@@ -351,6 +351,34 @@ int lxo_greedy_decode_constrained(const lxo_shape* s, const float* params, const
                                   const uint32_t* allow, int allow_ld,
                                   const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
                                   int32_t* ids_out, float* logp_out, float* alpha_out, int* steps_out, void* stream);
+/* Sampled decode: DRAWS from the model's distribution instead of its arg-max.  For a decoder row with f32 logits x[0..V) and its image's allowed
+ * set A (a banned column is a column outside the vocabulary): y = x * (1 / temperature); the row's order is value descending, then column
+ * ascending; C_K = its first top_k allowed columns (top_k = 0 or >= |A|: all of A); C = the shortest prefix of the order inside C_K whose
+ * softmax(y over C_K) mass is >= top_p (1: all of C_K) -- temperature, then top-k, then top-p on the renormalised mass; the token is
+ * argmax over C of y_v + g_v (ties: the lower column), g_v = -log(-log u_v), the Gumbel-max form of a draw from softmax(y over C).  The uniforms
+ * are counter-based: mix(z) = splitmix64's step (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ * 0x94D049BB133111EB; z ^= z >> 31), key = mix(seed << 32 | b << 4 | j) for draw j of image b, u_v = ((mix(key + t * V + v) >> 41) + 0.5) * 2^-23 at
+ * step t.  So draw (b, j) depends on neither n nor B nor any other row, the same seed repeats bit for bit, and top_k = 1 is the arg-max. */
+typedef struct lxo_sample_opts { float temperature; int top_k; float top_p; unsigned seed; } lxo_sample_opts;
+/* n = s->beam rows per image (1..16), each an independent draw of the whole sequence.
+ * ids_out int32 [B, max_steps, n]; logp_out, logq_out f32, same shape, nullable: logp = x_id - logsumexp_A(x), the model's own log-prob as in
+ * lxo_greedy_decode_scores / _constrained; logq = y_id - logsumexp_C(y), the log-prob under the distribution sampled from.
+ * allow / prefix: ONE ROW PER IMAGE, as in the beam calls, all NULL / 0 for none.  alpha_out (nullable): f32 [max_steps][B * n][Rp].
+ * The loop is lxo_greedy_decode's at n rows per image: a row is finished once it draws END at a free step (it goes on being decoded; its later
+ * columns are deterministic, no more); the loop ends after the first step with no unfinished row, or at max_iter.  At a forced step the forced id is
+ * emitted with its logp, logq is 0 and nothing is drawn; step t's uniforms keep the global t.  Launch per step in both dtypes.
+ * -1: NULL opts / ids_out, temperature or 1 / temperature not positive and finite in f32, top_k < 0, top_p outside (0, 1], a half-given set or prefix; -5: the shape limits of the
+ * other decodes (max_steps <= max_iter, beam outside 1 .. min(16, V)); all before any launch.  The device reads defensively, as the constrained
+ * calls do: an empty allowed row emits 0 and nothing faults. */
+int lxo_sample_decode(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                      const lxo_sample_opts* opts, const uint32_t* allow, int allow_ld,
+                      const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                      int32_t* ids_out, float* logp_out, float* logq_out, float* alpha_out, int* steps_out, void* stream);
+/* The select step alone, on logits the caller holds (e.g. ws region "dec_logits" after lxo_decode_cell_step): logits f32 [rows][ld] (device),
+ * row r = image r / n, sample r % n, step `time`.  Writes ids / logp / logq [rows] (the last two nullable).  No finished flags.
+ * -5: V < 1, ld < V, rows < 1, n outside 1 .. 16, time < 0; -1: the option and set refusals of lxo_sample_decode. */
+int lxo_sample_tokens(const float* logits, int ld, int rows, int n, int V, int time, const lxo_sample_opts* opts,
+                      const uint32_t* allow, int allow_ld, int32_t* ids_out, float* logp_out, float* logq_out, void* stream);
 /* The same loops ONE STEP AT A TIME: the calls behind the reference's decoder-cell protocol (dynamic_decode.py:35-36,43-44:
  * decoder_cell.initialize() / .step(time, state, inputs, finished); greedy_decoder_cell.py:46-66,
  * beam_search_decoder_cell.py:113-187).  latex_ocr_amd/model/components/ wraps them in cell objects with the reference's

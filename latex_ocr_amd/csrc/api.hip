@@ -244,6 +244,48 @@ extern "C" int lxo_greedy_decode_constrained(const lxo_shape* s, const float* pa
     CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_constrained");
     return 0;
 }
+// lxo_sample_opts as the kernels take it (head_kernels.h: DecSample); what is refused, or null
+static const char* make_sample(DecSample* so, const lxo_sample_opts* opts) {
+    if (!opts) return "lxo_sample_*: null opts";
+    if (!(opts->temperature > 0.f) || opts->temperature > 3.0e38f || !(1.0f / opts->temperature <= 3.0e38f))      // a subnormal tau: 1 / tau overflows
+        return "lxo_sample_*: temperature and 1 / temperature must be positive and finite";
+    if (opts->top_k < 0) return "lxo_sample_*: top_k < 0";
+    if (!(opts->top_p > 0.f && opts->top_p <= 1.f)) return "lxo_sample_*: top_p outside (0, 1]";
+    *so = DecSample{1.0f / opts->temperature, opts->top_k, opts->top_p, opts->seed, 1, 0};
+    return nullptr;
+}
+extern "C" int lxo_sample_decode(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                 const lxo_sample_opts* opts, const uint32_t* allow, int allow_ld,
+                                 const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                 int32_t* ids_out, float* logp_out, float* logq_out, float* alpha_out, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    DecSample so; DecAllow al; DecPrefix pf; bool has_prefix = false;
+    if (const char* why = make_sample(&so, opts)) return fail(-1, why);
+    if (!ids_out) return fail(-1, "lxo_sample_decode: null ids_out");
+    if (!allow && allow_ld != 0) return fail(-1, "lxo_sample_decode: null allow with allow_ld != 0");
+    if (allow) {
+        if (const char* why = make_constraint(&al, &pf, &has_prefix, P.s.V, allow, allow_ld, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, why);
+    } else {
+        has_prefix = prefix || prefix_len || prefix_ld != 0;
+        if (has_prefix && !make_prefix(&pf, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, "lxo_sample_decode: a prefix needs prefix, prefix_len and prefix_ld >= 1 (none: all NULL / 0)");
+    }
+    const DecodeOuts o = {ids_out, nullptr, logp_out, alpha_out, has_prefix ? &pf : nullptr, allow ? &al : nullptr};
+    CHECK_LAUNCH(lxo_impl_sample_decode(P, params, wpack, ws, id_end, max_iter, so, o, logq_out, steps_out, (hipStream_t)stream), "lxo_sample_decode");
+    return 0;
+}
+extern "C" int lxo_sample_tokens(const float* logits, int ld, int rows, int n, int V, int time, const lxo_sample_opts* opts,
+                                 const uint32_t* allow, int allow_ld, int32_t* ids_out, float* logp_out, float* logq_out, void* stream) {
+    DecSample so;
+    if (const char* why = make_sample(&so, opts)) return fail(-1, why);
+    if (!logits || !ids_out) return fail(-1, "lxo_sample_tokens: null logits or ids_out");
+    if (V < 1 || ld < V || rows < 1 || n < 1 || n > 16 || time < 0) return fail(-5, "lxo_sample_tokens: V < 1, ld < V, rows < 1, n outside 1 .. 16 or time < 0");
+    if (!allow && allow_ld != 0) return fail(-1, "lxo_sample_tokens: null allow with allow_ld != 0");
+    if (allow && (allow_ld < 0 || (allow_ld != 0 && allow_ld < (V + 31) / 32))) return fail(-1, "lxo_sample_tokens: allow_ld must be 0 or >= (V + 31) / 32");
+    const DecAllow al = {allow, allow_ld};
+    CHECK_LAUNCH(lxo_k_sample(logits, ld, V, rows, n, -1, time, so, nullptr, ids_out, logp_out, logq_out, 1, 0, nullptr, nullptr, (hipStream_t)stream,
+                              nullptr, allow ? &al : nullptr), "lxo_sample_tokens");
+    return 0;
+}
 extern "C" int lxo_decode_begin(const lxo_shape* s, const float* params, const void* wpack, void* ws, void* stream) {
     MAKE_PLAN(P, s);
     CHECK_LAUNCH(lxo_impl_decode_begin(P, params, wpack, ws, (hipStream_t)stream), "lxo_decode_begin");

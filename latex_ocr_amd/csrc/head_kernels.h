@@ -23,6 +23,30 @@ int lxo_k_score_alt(int dt, const float* logits, const int* formula, const int* 
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
                  int* finished, int* n_unfinished, hipStream_t st, float* logp_out = nullptr,      // logp_out (nullable): [n][max_steps] log-prob of the id
                  const DecPrefix* prefix = nullptr, const DecAllow* allow = nullptr);
+// The sampled select step (lxo_sample_decode / lxo_sample_tokens).  THE DISTRIBUTION AND THE DRAW, stated here once: for a decoder row with f32
+// logits x[0..V) whose image allows the set A (a banned column is a column outside the vocabulary), temperature tau > 0, top_k K >= 0 (0: off) and
+// top_p p in (0, 1] (1: off):
+//   1. y_v = x_v * (1 / tau) in f32;
+//   2. the row's total order is alt_before's on x: value descending, then column ascending;
+//   3. C_K = the first K allowed columns of that order (all of A when K = 0 or K >= |A|);
+//   4. q = softmax of y over C_K; C = the shortest prefix of the order inside C_K whose q-mass is >= p (temperature, then top-k, then top-p on
+//      the renormalised mass);
+//   5. the token is argmax over v in C of y_v + g_v, ties to the lower column, g_v = -log(-log u_v): the Gumbel-max trick -- arg-max row steps, no
+//      prefix sum over the row;
+//   6. logp = x_id - logsumexp_A(x), the model's own log-prob (lxo_k_argmax's arithmetic), logq = y_id - logsumexp_C(y), the log-prob under the
+//      distribution sampled from.
+// The uniforms are counter-based: mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+// z ^= z >> 31 in 64 bits; key = mix(seed << 32 | b << 4 | j) for draw j (< 16) of image b; bits = mix(key + (t V + v)) >> 41 (23 bits);
+// u = (bits + 0.5) 2^-23.  23 bits, not 24: bits + 0.5 is then exact in f32, u never rounds to 1 and g is always finite.  logf and expf in both
+// dtype modes.  So draw (b, j) at step t depends on neither n nor B nor another row, a seed repeats bit for bit, and K = 1 is the arg-max.
+// n, cb: filled in by the launcher (draws per image; the bits of a column index)
+struct DecSample { float inv_tau; int top_k; float top_p; unsigned seed; int n; int cb; };
+// row r of logits [rows][Vp] = draw r % n of image r / n at step `time` (the hash's and the prefix's step); ids_out / logp_out / logq_out (the last
+// two nullable) [image][max_steps][n] at column ostep; ids_step (nullable) [rows]: the ids fed back; finished / n_unfinished (nullable together):
+// as lxo_k_argmax keeps them.  prefix / allow: one row per IMAGE.  A forced step emits the forced id, its logp, logq 0, and draws nothing.
+int lxo_k_sample(const float* logits, int Vp, int V, int rows, int n, int id_end, int time, const DecSample& opts, int* ids_step, int* ids_out,
+                 float* logp_out, float* logq_out, int max_steps, int ostep, int* finished, int* n_unfinished, hipStream_t st,
+                 const DecPrefix* prefix = nullptr, const DecAllow* allow = nullptr);
 int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,
                     float* scratch, float* logp, int* finished,
                     int* ids_step, int* parents_step, int* ids_out, int* par_out, int max_steps, int* n_unfinished, hipStream_t st,

@@ -204,6 +204,182 @@ LXO_DEV float strided_entropy(const float* lg, int lane, int V, const unsigned* 
     return wave_sum(h);
 }
 
+// Sampling (the sample kernels; head_kernels.h states the distribution and the draw).  The uniforms are counter-based as drop.h's mask is: smp_mix is
+// splitmix64's step, a sample (image b, draw j) has ONE key and column v of step t the counter t V + v behind it -- nothing depends on n, B or a neighbour.
+LXO_DEV unsigned long long smp_mix(unsigned long long z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+LXO_DEV unsigned long long smp_key(unsigned seed, int b, int j) {
+    return smp_mix(((unsigned long long)seed << 32) | ((unsigned long long)(unsigned)b << 4) | (unsigned long long)(unsigned)j);
+}
+// g = -log(-log u), u = (bits + 0.5) 2^-23 from 23 hash bits: bits + 0.5 is exact in f32, u < 1 always, g finite (24 bits round u to 1)
+LXO_DEV float smp_gumbel(unsigned long long key, int t, int V, int v) {
+    const unsigned bits = (unsigned)(smp_mix(key + ((unsigned long long)(unsigned)t * (unsigned)V + (unsigned)v)) >> 41);
+    const float u = ((float)bits + 0.5f) * 1.1920928955078125e-7f;
+    return -logf(-logf(u));
+}
+// y = x / tau as the definition states it: the f32 product, ROUNDED -- never contracted into the subtraction or addition that follows, so that every
+// step sees the same y (top_k = 1: logq = y - (y + log 1) = 0 exactly)
+LXO_DEV float smp_y(float x, float inv_tau) {
+#pragma clang fp contract(off)
+    return x * inv_tau;
+}
+// alt_before's order as ONE integer: (x, c) comes before (y, d) <=> alt_key(x, c) > alt_key(y, d) -- high word: the value's bits made monotone (-0 = +0,
+// never 0), low word: the column complemented.  A cut-off of the order is then a key T: the columns with alt_key >= T are a prefix of the order,
+// CUT_NONE the cut that keeps every column.  alt_val: the value back from a high word
+constexpr unsigned long long CUT_NONE = 1ull << 32;
+LXO_DEV unsigned alt_key_hi(float x) {
+    unsigned u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0u;
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return u ? u : 1u;
+}
+LXO_DEV float alt_val(unsigned kh) { return __uint_as_float((kh & 0x80000000u) ? (kh & 0x7fffffffu) : ~kh); }
+LXO_DEV unsigned long long alt_key(float x, int c) { return ((unsigned long long)alt_key_hi(x) << 32) | (unsigned long long)(~(unsigned)c); }
+LXO_DEV bool key_ge(unsigned kh, int c, unsigned long long T) {
+    const unsigned th = (unsigned)(T >> 32), tl = (unsigned)T;
+    return kh > th || (kh == th && ~(unsigned)c >= tl);
+}
+// The cut-offs are found by bisection on the key, most significant bit first: the largest T whose prefix still holds `need` columns (top-k) or
+// `need` exp-mass (top-p).  cb = the bits a column < V takes: above them the low word of every key is ones, so those bits are set from the start
+// and 32 + cb probes decide the rest -- a trip count fixed by V.  cut_bit(i): the bit probe i decides
+LXO_DEV unsigned long long cut_start(int cb) { return 0xFFFFFFFFull & ~((1ull << cb) - 1ull); }
+LXO_DEV unsigned long long cut_bit(int i, int cb) { return 1ull << (i < 32 ? 63 - i : cb - 1 - (i - 32)); }
+// Register row, what the sample kernel keeps of it: kh = the key's high word of a counting column, 0 (behind every cut) elsewhere, and
+// ex = exp(y - max y), y = x / tau, 0 elsewhere; returns max y
+template <int KV>
+LXO_DEV float row_tempered(const float (&x)[KV], unsigned ok, float inv_tau, unsigned (&kh)[KV], float (&ex)[KV]) {
+    float m = -3.0e38f;
+#pragma unroll
+    for (int i = 0; i < KV; ++i) if ((ok >> i) & 1u) m = fmaxf(m, smp_y(x[i], inv_tau));
+    m = wave_max(m);
+#pragma unroll
+    for (int i = 0; i < KV; ++i) {
+        const bool on = (ok >> i) & 1u;
+        kh[i] = on ? alt_key_hi(x[i]) : 0u;
+        ex[i] = on ? expf(smp_y(x[i], inv_tau) - m) : 0.f;
+    }
+    return m;
+}
+// the wave's number of counting columns / their exp-mass at or in front of the cut T (a lane's columns first, then the wave: both monotone in T)
+template <int KV>
+LXO_DEV int row_count_ge(const unsigned (&kh)[KV], int lane, unsigned long long T) {
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) n += key_ge(kh[4 * q + e], 4 * (lane + 64 * q) + e, T) ? 1 : 0;
+    return wave_sum_i(n);
+}
+template <int KV>
+LXO_DEV float row_mass_ge(const unsigned (&kh)[KV], const float (&ex)[KV], int lane, unsigned long long T) {
+    float l = 0.f;
+#pragma unroll
+    for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (key_ge(kh[4 * q + e], 4 * (lane + 64 * q) + e, T)) l += ex[4 * q + e];
+    return wave_sum(l);
+}
+template <int KV>
+LXO_DEV unsigned long long row_cut_count(const unsigned (&kh)[KV], int lane, int cb, int need) {
+    unsigned long long T = cut_start(cb);
+    for (int i = 0; i < 32 + cb; ++i) { const unsigned long long c = T | cut_bit(i, cb); if (row_count_ge<KV>(kh, lane, c) >= need) T = c; }
+    return T;
+}
+template <int KV>
+LXO_DEV unsigned long long row_cut_mass(const unsigned (&kh)[KV], const float (&ex)[KV], int lane, int cb, float need) {
+    unsigned long long T = cut_start(cb);
+    for (int i = 0; i < 32 + cb; ++i) { const unsigned long long c = T | cut_bit(i, cb); if (row_mass_ge<KV>(kh, ex, lane, c) >= need) T = c; }
+    return T;
+}
+// a lane's first maximum of y + g over its columns inside the cut (strict >, ascending columns): the Gumbel-max draw; a wave arg-max follows
+template <int KV>
+LXO_DEV void row_gumbel(const unsigned (&kh)[KV], int lane, unsigned long long T, float inv_tau, unsigned long long key, int t, int V, float& best, int& bi) {
+    best = -INFINITY; bi = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * (lane + 64 * q) + e;
+            if (key_ge(kh[4 * q + e], c, T)) {
+                const float s = smp_y(alt_val(kh[4 * q + e]), inv_tau) + smp_gumbel(key, t, V, c);
+                if (s > best) { best = s; bi = c; }
+            }
+        }
+}
+// The same steps on a strided row: a pass over the row each (a probe of a cut-off is one)
+template <bool AL>
+LXO_DEV float strided_tempered_max(const float* lg, int lane, int V, const unsigned* ar, float inv_tau) {
+    float m = -3.0e38f;
+    for (int j = lane; j < V; j += 64) if (!AL || alw_ok(ar, j)) m = fmaxf(m, smp_y(lg[j], inv_tau));
+    return wave_max(m);
+}
+template <bool AL>
+LXO_DEV int strided_count_ge(const float* lg, int lane, int V, const unsigned* ar, unsigned long long T) {
+    int n = 0;
+    for (int j = lane; j < V; j += 64) n += ((!AL || alw_ok(ar, j)) && alt_key(lg[j], j) >= T) ? 1 : 0;
+    return wave_sum_i(n);
+}
+template <bool AL>
+LXO_DEV float strided_mass_ge(const float* lg, int lane, int V, const unsigned* ar, float inv_tau, float m, unsigned long long T) {
+    float l = 0.f;
+    for (int j = lane; j < V; j += 64) { const float x = lg[j]; if ((!AL || alw_ok(ar, j)) && alt_key(x, j) >= T) l += expf(smp_y(x, inv_tau) - m); }
+    return wave_sum(l);
+}
+template <bool AL>
+LXO_DEV unsigned long long strided_cut_count(const float* lg, int lane, int V, const unsigned* ar, int cb, int need) {
+    unsigned long long T = cut_start(cb);
+    for (int i = 0; i < 32 + cb; ++i) { const unsigned long long c = T | cut_bit(i, cb); if (strided_count_ge<AL>(lg, lane, V, ar, c) >= need) T = c; }
+    return T;
+}
+template <bool AL>
+LXO_DEV unsigned long long strided_cut_mass(const float* lg, int lane, int V, const unsigned* ar, float inv_tau, float m, int cb, float need) {
+    unsigned long long T = cut_start(cb);
+    for (int i = 0; i < 32 + cb; ++i) { const unsigned long long c = T | cut_bit(i, cb); if (strided_mass_ge<AL>(lg, lane, V, ar, inv_tau, m, c) >= need) T = c; }
+    return T;
+}
+template <bool AL>
+LXO_DEV void strided_gumbel(const float* lg, int lane, int V, const unsigned* ar, unsigned long long T, float inv_tau, unsigned long long key, int t,
+                            float& best, int& bi) {
+    best = -INFINITY; bi = 0x7fffffff;
+    for (int j = lane; j < V; j += 64) {
+        const float x = lg[j];
+        if ((!AL || alw_ok(ar, j)) && alt_key(x, j) >= T) {
+            const float s = smp_y(x, inv_tau) + smp_gumbel(key, t, V, j);
+            if (s > best) { best = s; bi = j; }
+        }
+    }
+}
+// What a sampled row leaves behind: id, logp = the model's own log-prob of it with argmax_kernel's arithmetic (-log of the exp-sum around the
+// allowed maximum, plus x[id] - max where the id is not that maximum or is forced), logq = its log-prob under the distribution it was drawn from
+// (0 at a forced step); outputs [image][step][draw].  finished (nullable): as argmax_kernel keeps it
+struct SmpOut { int* ids_step; int* ids; float* logp; float* logq; int* finished; int* n_unfinished; int max_steps, ostep; };
+template <bool AL>
+LXO_DEV void smp_emit(const SmpOut& o, const float* lg, int lane, int V, const unsigned* ar, int row, int b, int j, int n, int id, bool forced, float xmax,
+                      float lq, int id_end) {
+    float lp = 0.f;
+    if (o.logp) {
+        lp = -logf(strided_expsum<AL>(lg, lane, V, ar, xmax));
+        const float xi = lg[id];
+        if (forced || xi != xmax) lp += xi - xmax;
+    }
+    if (lane == 0) {
+        const long long at = ((long long)b * o.max_steps + o.ostep) * n + j;
+        o.ids[at] = id;
+        if (o.logp) o.logp[at] = lp;
+        if (o.logq) o.logq[at] = lq;
+        if (o.ids_step) o.ids_step[row] = id;
+        if (o.finished) {
+            const int f = o.finished[row] | (id == id_end && !forced ? 1 : 0);
+            o.finished[row] = f;
+            if (!f) atomicAdd(o.n_unfinished, 1);
+        }
+    }
+}
+
 // Row of the loss and scoring kernels: row = t * B + b reads formula[b][t] (o = its flat index), live while t < lengths[b]; the target clamped into [0, V)
 struct RowTok { int t, b; long long o; bool live; };
 LXO_DEV RowTok row_tok(int row, int B, int T, const int* lengths) {
@@ -542,6 +718,74 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
     }
 }
 
+// Sampled select step (head_kernels.h: the distribution and the draw): row r is draw r % n of image r / n, one wave per row as argmax_kernel; the row
+// in registers (Vp <= 64 * KV).  PF / AL: one prefix and one allowed set per IMAGE.  The cut-off searches run only where top_k / top_p ask for them
+// (wave-uniform branches, fixed trip counts); an empty allowed row emits 0.
+template <int KV, bool PF, bool AL>
+__global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ logits, int Vp, int V, int rows, int id_end, int time, DecSample so,
+                                                         SmpOut o, DecPrefix pf, DecAllow al) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int b = row / so.n, j = row - b * so.n;
+    const float* lg = logits + (long long)row * Vp;
+    const unsigned* ar = nullptr;
+    if constexpr (AL) ar = alw_row(al, b);
+    int fi = -1;
+    if constexpr (PF) { if (time < pfx_len(pf, b)) fi = pfx_id(pf, b, time, V); }
+    float x[KV];
+    row_load<KV>(lg, lane, V, Vp, x);
+    const unsigned ok = row_counts<KV, AL>(lane, V, ar, x);
+    float xmax = x[0];
+#pragma unroll
+    for (int e = 1; e < KV; ++e) xmax = fmaxf(xmax, x[e]);
+    xmax = wave_max(xmax);
+    int id = fi; float lq = 0.f;
+    if (fi < 0) {
+        unsigned kh[KV]; float ex[KV];
+        const float m = row_tempered<KV>(x, ok, so.inv_tau, kh, ex);
+        unsigned long long T = CUT_NONE;
+        if (so.top_k > 0) T = row_cut_count<KV>(kh, lane, so.cb, min(so.top_k, wave_sum_i(__builtin_popcount(ok))));
+        if (so.top_p < 1.f) T = row_cut_mass<KV>(kh, ex, lane, so.cb, so.top_p * row_mass_ge<KV>(kh, ex, lane, T));
+        float best; int bi;
+        row_gumbel<KV>(kh, lane, T, so.inv_tau, smp_key(so.seed, b, j), time, V, best, bi);
+        wave_argmax(best, bi);
+        id = bi < V ? bi : 0;
+        lq = smp_y(lg[id], so.inv_tau) - (m + logf(row_mass_ge<KV>(kh, ex, lane, T)));
+    }
+    smp_emit<AL>(o, lg, lane, V, ar, row, b, j, so.n, id, fi >= 0, xmax, lq, id_end);
+}
+// The same for any Vp: the strided row steps
+template <bool PF, bool AL>
+__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, int Vp, int V, int rows, int id_end, int time, DecSample so,
+                                                    SmpOut o, DecPrefix pf, DecAllow al) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int b = row / so.n, j = row - b * so.n;
+    const float* lg = logits + (long long)row * Vp;
+    const unsigned* ar = nullptr;
+    if constexpr (AL) ar = alw_row(al, b);
+    int fi = -1;
+    if constexpr (PF) { if (time < pfx_len(pf, b)) fi = pfx_id(pf, b, time, V); }
+    float xmax; int xi;
+    strided_argmax<AL>(lg, lane, V, ar, xmax, xi);
+    xmax = wave_max(xmax);
+    int id = fi; float lq = 0.f;
+    if (fi < 0) {
+        const float m = strided_tempered_max<AL>(lg, lane, V, ar, so.inv_tau);
+        unsigned long long T = CUT_NONE;
+        if (so.top_k > 0) T = strided_cut_count<AL>(lg, lane, V, ar, so.cb, min(so.top_k, strided_count_ge<AL>(lg, lane, V, ar, CUT_NONE)));
+        if (so.top_p < 1.f) T = strided_cut_mass<AL>(lg, lane, V, ar, so.inv_tau, m, so.cb, so.top_p * strided_mass_ge<AL>(lg, lane, V, ar, so.inv_tau, m, T));
+        float best; int bi;
+        strided_gumbel<AL>(lg, lane, V, ar, T, so.inv_tau, smp_key(so.seed, b, j), time, best, bi);
+        wave_argmax(best, bi);
+        id = bi < V ? bi : 0;
+        lq = smp_y(lg[id], so.inv_tau) - (m + logf(strided_mass_ge<AL>(lg, lane, V, ar, so.inv_tau, m, T)));
+    }
+    smp_emit<AL>(o, lg, lane, V, ar, row, b, j, so.n, id, fi >= 0, xmax, lq, id_end);
+}
+
 // One block per image: beam_search_decoder_cell.py:146-187.
 //  log_softmax, mask finished beams (0 at END, f32 lowest elsewhere), add running log-probs,
 //  top-k over k*V (beam 0 only at time 0), ids = idx % V, parents = idx / V, gather finished.
@@ -822,11 +1066,38 @@ int lxo_k_score_alt(int dt, const float* logits, const int* formula, const int* 
         else if (allow) hipLaunchKernelGGL((KERNEL<false, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);        \
         else hipLaunchKernelGGL((KERNEL<false, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);                  \
     } while (0)
+// ... and of a register-row decode kernel KERNEL<KV, PF, AL>
+#define DEC_VARIANT_KV(KERNEL, KV_, grid, block, ...)                                                                      \
+    do {                                                                                                                    \
+        if (prefix && allow) hipLaunchKernelGGL((KERNEL<KV_, true, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);    \
+        else if (prefix) hipLaunchKernelGGL((KERNEL<KV_, true, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);       \
+        else if (allow) hipLaunchKernelGGL((KERNEL<KV_, false, true>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);        \
+        else hipLaunchKernelGGL((KERNEL<KV_, false, false>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);                  \
+    } while (0)
 int lxo_k_argmax(const float* logits, int Vp, int V, int n, int id_end, int* ids_step, int* ids_out, int max_steps, int step,
                  int* finished, int* n_unfinished, hipStream_t st, float* logp_out, const DecPrefix* prefix, const DecAllow* allow) {
     const DecPrefix pf = prefix ? *prefix : DecPrefix{};
     const DecAllow al = allow ? *allow : DecAllow{};
     DEC_VARIANT(argmax_kernel, cdiv(n, 4), 256, logits, Vp, V, n, id_end, ids_step, ids_out, max_steps, step, finished, n_unfinished, logp_out, pf, al);
+    DONE;
+}
+int lxo_k_sample(const float* logits, int Vp, int V, int rows, int n, int id_end, int time, const DecSample& opts, int* ids_step, int* ids_out,
+                 float* logp_out, float* logq_out, int max_steps, int ostep, int* finished, int* n_unfinished, hipStream_t st,
+                 const DecPrefix* prefix, const DecAllow* allow) {
+    if (rows < 1 || n < 1 || n > 16 || V < 1) return -2;
+    DecSample so = opts;
+    so.n = n;
+    so.cb = 0;
+    while (so.cb < 31 && (1ll << so.cb) < V) ++so.cb;
+    const SmpOut o = {ids_step, ids_out, logp_out, logq_out, finished, n_unfinished, max_steps, ostep};
+    const DecPrefix pf = prefix ? *prefix : DecPrefix{};
+    const DecAllow al = allow ? *allow : DecAllow{};
+    if (Vp % 4 == 0 && Vp <= 1024 && ((uintptr_t)logits & 15) == 0) {
+#define SM_ROWS(KV_) DEC_VARIANT_KV(sample_rows_kernel, KV_, cdiv(rows, 4), 256, logits, Vp, V, rows, id_end, time, so, o, pf, al)
+        BY_KV(Vp, SM_ROWS);
+#undef SM_ROWS
+    } else
+        DEC_VARIANT(sample_kernel, cdiv(rows, 4), 256, logits, Vp, V, rows, id_end, time, so, o, pf, al);
     DONE;
 }
 int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, int time, float div_gamma, float div_prob, int div_seed,

@@ -3,6 +3,7 @@
 #include "plan.h"
 struct DecPrefix;                     // head_kernels.h
 struct DecAllow;
+struct DecSample;
 const char* lxo_ws_name(int id);
 int lxo_impl_pack_weights(const Plan& P, const float* prm, void* wp, hipStream_t st);
 int lxo_impl_encoder_fwd(const Plan& P, const float* prm, const void* wp, void* ws, const uint8_t* img, hipStream_t st);
@@ -27,6 +28,9 @@ int lxo_impl_decode_state_get(const Plan& P, void* ws, int time, float* c, float
 int lxo_impl_decode_state_set(const Plan& P, void* ws, int time, const float* c, const float* h, const float* o, const int* ids_prev, hipStream_t st);
 int lxo_impl_decode_cell_step(const Plan& P, const float* prm, const void* wp, void* ws, int time, int start_token, hipStream_t st);
 int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out, int* steps_out, hipStream_t st);
+// n = s.beam independent draws per image; out.scores = the tokens' log-probs under the model, logq_out (nullable) under the sampled distribution
+int lxo_impl_sample_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecSample& opts, const DecodeOuts& out,
+                           float* logq_out, int* steps_out, hipStream_t st);
 int lxo_impl_set_side_stream(hipStream_t s);
 int lxo_impl_set_encoder_side_stream(hipStream_t s);
 // optional row-BiLSTM encoder (model_rowenc.hip): features in ws region "img" in place; backward: "d_img" (f32) in place + parameter gradients

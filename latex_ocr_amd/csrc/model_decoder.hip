@@ -841,6 +841,22 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
     });
 }
 
+// Sampled decode: lxo_impl_greedy_decode's loop over n = s.beam rows per image, every row an independent draw of the whole sequence -- the beam's
+// tiled set-up and decoder step, no parents, and lxo_k_sample as the select step.  Launch per step in both dtypes (the chain holds no sampler)
+int lxo_impl_sample_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecSample& opts,
+                           const DecodeOuts& out, float* logq_out, int* steps_out, hipStream_t st) {
+    const int n = P.s.beam;
+    RC(decode_check(P, n, max_iter + 1, out.prefix, out.allow));
+    const Dec d = dec_of(P, ws, n, false);
+    RC(decode_setup(P, prm, wp, ws, d, false, st));
+    return decode_loop_steps(max_iter, d.flags, st, steps_out, [&](int time, int* unfinished) -> int {
+        RC(decode_common_step(P, prm, wp, ws, d.nv, d.k, (time + 1) & 1, time == 0 ? nullptr : d.ids_step, st));
+        if (out.alpha) HIPRC(hipMemcpyAsync(out.alpha + (size_t)time * d.nv * P.Rp, d.alpha, (size_t)d.nv * P.Rp * 4, hipMemcpyDeviceToDevice, st));
+        return lxo_k_sample(d.logits, P.Vp, P.s.V, d.nv, n, id_end, time, opts, d.ids_step, out.ids, out.scores, logq_out, P.s.max_steps, time,
+                            d.finished, unfinished, st, out.prefix, out.allow);
+    });
+}
+
 // lxo_chain_guard: scale[0] = NaN when a chain of this step left an error word, else the clip scale / 1 (decoder_kernels.hip)
 int lxo_impl_chain_guard(const Plan& P, void* ws, const float* grads, float* scale, int have_scale, unsigned* status, hipStream_t st) {
     const unsigned* ef = P.bf ? P.ws<unsigned>(ws, W_XSYNC) + 8 * 64 : nullptr;

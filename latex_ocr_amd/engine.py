@@ -981,3 +981,81 @@ class Engine(object):
             out.append(sc[:, :n])
         out = tuple(a.cpu().numpy() for a in out)
         return out if len(out) > 1 else out[0]
+
+    def _sample_opts(self, n, temperature, top_k, top_p, seed):
+        """Checks the sampling options before any launch: -> lxo_sample_opts.  temperature = 0 means top_k = 1 (the arg-max)."""
+        n, top_k = int(n), int(top_k)
+        temperature, top_p = float(temperature), float(top_p)
+        if not 1 <= n <= 16:
+            raise ValueError("n = %d draws per image outside 1 .. 16" % n)
+        if not (temperature >= 0.0 and np.isfinite(temperature)):
+            raise ValueError("temperature must be finite and >= 0, got %r" % temperature)
+        if top_k < 0:
+            raise ValueError("top_k must be >= 0 (0: off), got %d" % top_k)
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError("top_p must lie in (0, 1] (1: off), got %r" % top_p)
+        if temperature == 0.0:
+            temperature, top_k = 1.0, 1
+        with np.errstate(over="ignore", divide="ignore"):
+            t32 = np.float32(temperature)
+            if not (t32 > 0 and np.isfinite(t32) and np.isfinite(np.float32(1.0) / t32)):      # what the C call refuses, before the encoder runs
+                raise ValueError("temperature %r and its reciprocal must be finite and positive in float32 (0 itself means top_k = 1)" % temperature)
+        return _abi.LxoSampleOpts(temperature, top_k, top_p, int(seed) & 0xFFFFFFFF)
+
+    def sample_decode(self, img, id_end, n=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, max_iter=151, return_scores=False, return_attention=False,
+                      prefix=None, prefix_lengths=None, allowed=None):
+        """n independent DRAWS of the whole sequence per image (lxo_sample_decode): ids int32 [B, T', n].  Every step draws from the model's
+        distribution at `temperature`, cut to the top_k most likely tokens (0: off) and then to the smallest set of renormalised mass >= top_p
+        (1: off); temperature = 0 means top_k = 1, the arg-max.  Draw (b, j) depends only on seed, b, j and the step: the same seed repeats bit for
+        bit, and neither n nor the batch changes a draw.  Launch per step in both dtypes (no chain, so no fill-up of the batch).
+        return_scores: -> (ids, logp, logq) or (ids, alpha, logp, logq), f32 [B, T', n]: logp = the model's own log-prob of the token (as
+        greedy_decode's, renormalised over `allowed`), logq = its log-prob under the distribution it was drawn from (0 at a forced step); the
+        sequence log-prob of a draw is the sum through its first END.  return_attention: alpha f32 [B, T', n, H', W'].
+        prefix / prefix_lengths / allowed: per image, as in greedy_decode.  A ValueError before any launch for what greedy_decode refuses, n outside
+        1 .. min(16, V), temperature < 0 or not finite, top_k < 0, top_p outside (0, 1]."""
+        so = self._sample_opts(n, temperature, top_k, top_p, seed)
+        n = int(n)
+        if n > self.n_tok:                                             # the decode calls' shape limit (rows per image <= V); the select step alone has none
+            raise ValueError("n = %d draws per image exceed the vocabulary size %d" % (n, self.n_tok))
+        if self.max_steps < max_iter + 1:
+            self.max_steps, self.ws = max_iter + 1, None
+        B0 = int(img.shape[0])
+        al = self._allow_host(allowed, B0, id_end, 1) if allowed is not None else None
+        pfx = self._prefix_args(prefix, prefix_lengths, B0, B0, id_end, max_iter, al) if prefix is not None else None
+        alw = self._allow_args(al, B0, B0) if al is not None else (None, 0)
+        B = self._encode_only(img, n)
+        ids = torch.zeros(B, self.max_steps, n, dtype=torch.int32, device=self.device)
+        logp = torch.zeros(B, self.max_steps, n, dtype=torch.float32, device=self.device) if return_scores else None
+        logq = torch.zeros(B, self.max_steps, n, dtype=torch.float32, device=self.device) if return_scores else None
+        alpha, R, Hp, Wp = self._alpha_buf(B * n, img) if return_attention else (None, 0, 0, 0)
+        pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
+        steps = self._run_decode((self.lib.lxo_sample_decode, "sample_decode",
+                                  (ctypes.byref(so), _p(alw[0]), alw[1]) + pa + (_p(ids), _p(logp), _p(logq), _p(alpha))), id_end, max_iter)
+        out = [ids[:, :steps]]
+        if return_attention:
+            out.append(alpha[:steps, :, :R].reshape(steps, B, n, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
+        if return_scores:
+            out += [logp[:, :steps], logq[:, :steps]]
+        out = tuple(a.cpu().numpy() for a in out)
+        return out if len(out) > 1 else out[0]
+
+    def sample_tokens(self, logits, n=1, time=0, temperature=1.0, top_k=0, top_p=1.0, seed=0, allowed=None):
+        """The sampled select step alone (lxo_sample_tokens) on logits [rows, V] the caller holds (host array or tensor): row r is draw r % n of
+        image r // n at step `time`.  -> (ids int32 [rows], logp f32 [rows], logq f32 [rows]).  allowed: [V] or [images, V], images = ceil(rows / n).
+        A float32 device tensor with unit column stride is read in place, whatever its row stride (a view of padded rows)."""
+        so = self._sample_opts(n, temperature, top_k, top_p, seed)
+        in_place = isinstance(logits, torch.Tensor) and logits.device == self.device and logits.dtype == torch.float32 and logits.dim() == 2 and \
+            logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]
+        lg = logits if in_place else self._to_dev(logits, torch.float32)
+        if lg.dim() != 2 or lg.shape[1] != self.n_tok or lg.shape[0] < 1:
+            raise ValueError("logits must be [rows >= 1, V = %d], got shape %s" % (self.n_tok, tuple(lg.shape)))
+        if int(time) < 0:
+            raise ValueError("time must be >= 0, got %d" % int(time))
+        rows, images = int(lg.shape[0]), (int(lg.shape[0]) + int(n) - 1) // int(n)
+        alw = self._allow_args(self._allow_host(allowed, images, None, 0), images, images) if allowed is not None else (None, 0)
+        ids = torch.zeros(rows, dtype=torch.int32, device=self.device)
+        logp = torch.zeros(rows, dtype=torch.float32, device=self.device)
+        logq = torch.zeros(rows, dtype=torch.float32, device=self.device)
+        self._ck(self.lib.lxo_sample_tokens(_p(lg), int(lg.stride(0)), rows, int(n), self.n_tok, int(time), ctypes.byref(so), _p(alw[0]), alw[1],
+                                            _p(ids), _p(logp), _p(logq), self._stream()), "sample_tokens")
+        return ids.cpu().numpy(), logp.cpu().numpy(), logq.cpu().numpy()

@@ -11,7 +11,9 @@ combine with --scores and --prefix (predict_batch / complete_batch with banned= 
 of the hypothesis (or, with --formula, of the given transcription): the token, its log-prob, its rank among the model's choices, the
 entropy of the step and the model's K best tokens there with their log-probs (predict_batch / complete_batch / score_batch with
 alternatives=K: for a decode they come from a second, teacher-forced pass over the emitted tokens); with --formula it combines with
---ban / --allow-file, which then constrain the alternatives."""
+--ban / --allow-file, which then constrain the alternatives.  --sample N draws N transcriptions per image instead of decoding the best one
+(Img2SeqModel.sample_batch; --temperature T, --top-k K, --top-p P and --seed S shape and repeat the draws; combines with --ban /
+--allow-file): one line with the agreement (top count / N), then one line per distinct hypothesis with its count and log-prob."""
 import argparse
 
 import numpy as np
@@ -31,12 +33,19 @@ def main(argv=None):
     ap.add_argument("--ban", default=None, help="space-separated tokens that must not be emitted")
     ap.add_argument("--allow-file", default=None, help="file with one token per line: only these (and END) may be emitted")
     ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="per position: the token's log-prob and rank, the entropy and the K best tokens")
+    ap.add_argument("--sample", type=int, default=0, metavar="N", help="draw N transcriptions per image: distinct hypotheses with counts, and their agreement")
+    ap.add_argument("--temperature", type=float, default=1.0, help="--sample: softmax temperature (0: the arg-max)")
+    ap.add_argument("--top-k", type=int, default=0, help="--sample: draw among the K most likely tokens (0: off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="--sample: draw among the smallest token set of mass >= P (1: off)")
+    ap.add_argument("--seed", type=int, default=0, help="--sample: the same seed repeats the draws")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     if a.formula is not None and len(a.images) != 1:
         ap.error("--formula scores one image")
     if a.prefix is not None and (len(a.images) != 1 or a.formula is not None):
         ap.error("--prefix completes one image and does not combine with --formula")
+    if a.sample and (a.formula is not None or a.prefix is not None or a.alternatives or not 1 <= a.sample <= 16):
+        ap.error("--sample takes 1 .. 16 and does not combine with --formula, --prefix or --alternatives")
     d = a.results
     config_vocab, config_model = Config(d + "vocab.json"), Config(d + "model.json")
     vocab = Vocab(config_vocab)
@@ -72,6 +81,13 @@ def main(argv=None):
             print(path, "<=", a.formula, "\tlogp %.4f\tgeo-mean p %.4f\tfirst disagreement %d" % (lp, np.exp(lp / max(1, len(toks))), first))
             if alt:
                 print_alternatives(emitted(" ".join(vocab.id_to_tok[i] for i in vocab.form_prepro(a.formula)), len(toks)), toks, res[3])
+            out.append(res)
+            continue
+        if a.sample:
+            res = model.sample_batch([greyscale(img)], a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, **sets)[0]
+            print(path, "~>", "%d draws\tagreement %.3f" % (a.sample, res["agreement"]))
+            for h in res["hypotheses"]:
+                print("  %3d x  logp %9.4f  %s" % (h["count"], h["logp"], h["text"]))
             out.append(res)
             continue
         if a.prefix is not None:

@@ -2,7 +2,9 @@
 the full max_iter + 1 steps).  --scores: each decode once without and once with return_scores (token log-probs / hypothesis
 scores), interleaved over --reps rounds, for the A/B of the scored calls.  --prefix N: the same A/B of the calls without a prefix and
 with an N-token forced prefix on every row (prefix=, the decode still runs max_iter + 1 steps).  --ban N: the A/B of the calls without a
-constraint and with N random tokens banned in every row (allowed= as [B, V]: a set per image)."""
+constraint and with N random tokens banned in every row (allowed= as [B, V]: a set per image).  --sample N: sampled decode with N draws per image
+(Engine.sample_decode at temperature 1, then with top_k = 50 and top_p = 0.9) against beam N of the same tree, in alternating rounds; nothing else
+runs then."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,6 +34,23 @@ def timed(fn, n=3):
     out = out[0] if isinstance(out, tuple) else out
     return (time.perf_counter() - t0) / n, out.shape[1]
 
+
+if "--sample" in sys.argv:
+    n = int(sys.argv[sys.argv.index("--sample") + 1])
+    eng = Engine(V, dtype="bf16", beam=n, max_steps=152)
+    arms = [("beam %d" % n, lambda: eng.beam_decode(img, V - 1, n, max_iter=100)),
+            ("sample %d" % n, lambda: eng.sample_decode(img, V - 1, n=n, seed=1, max_iter=100)),
+            ("sample %d top_k 50 top_p 0.9" % n, lambda: eng.sample_decode(img, V - 1, n=n, top_k=50, top_p=0.9, seed=1, max_iter=100))]
+    for _, fn in arms: fn()
+    per = [[] for _ in arms]
+    for r in range(reps):
+        for i in (range(len(arms)) if r % 2 == 0 else reversed(range(len(arms)))):
+            dt, steps = timed(arms[i][1])
+            per[i].append(dt * 1e6 / steps)
+    for (name, _), v in zip(arms, per):
+        v = sorted(v)
+        print("%s: %d steps, us per step median of %d %.2f (%.2f..%.2f), ratio to beam %.4f" % (name, steps, reps, v[reps // 2], v[0], v[-1], v[reps // 2] / sorted(per[0])[reps // 2]))
+    sys.exit(0)
 
 for beam in (1, 5):
     eng = Engine(V, dtype="bf16", beam=beam, max_steps=152)
