@@ -2,6 +2,7 @@
 // launch -- 8 independent chains (one per XCD, B/8 samples each), workgroups of a chain hand over through their XCD's L2 and
 // meet at a flag-line barrier that costs 0.44 us (tools/xcd_barrier_probe.hip) where a dependent kernel boundary costs 1.5 us.
 #pragma once
+#include "lxo.h"
 #include "lxo_common.h"
 #include "decoder_kernels.h"
 #include "lxo_debug.h"
@@ -102,5 +103,9 @@ int lxo_launch_xdec_bwd(const XDecBwd& p, int U, int O, int C, int E, hipStream_
 // [hand-over words, 384 KB: 8-byte {value, tag} pairs for up to 64 samples]; the launcher zeroes the whole block (tags of an earlier
 // launch must not pass for this one's).  Forward chain: block 0, backward chain: block 1.
 constexpr size_t kXDecSyncBytes = 4096, kXDecLLBytes = 384u << 10, kXDecBlockBytes = kXDecSyncBytes + kXDecLLBytes;
+constexpr size_t kXDecBlockWords = kXDecBlockBytes / 4;      // a block in 32-bit words: what the host's pointers into the region count in
+constexpr size_t kXDecErrWord = 8 * 64;                      // the error word's index in a block: behind the 8 XCDs' flag and ticket words ...
+constexpr size_t kXDecTicketBytes = kXDecErrWord * 4;        // ... which are what a call without a chain clears when it leaves the error word alone
+static_assert(kXDecErrWord == LXO_XDEC_ERR_WORD, "include/lxo.h names the error word for the callers");
 constexpr size_t kLLFwdHt = 0, kLLFwdAh = 128u << 10, kLLFwdO = 256u << 10;      // h~ [B][256 pairs], att_h [B][256], o [B][256 pairs]
 constexpr size_t kLLBwdGb = 0, kLLBwdDctx = 128u << 10;                          // g [B][256 pairs], d_ctx [B][512]

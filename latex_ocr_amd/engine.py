@@ -29,6 +29,13 @@ def _p(t):
 # backward): 4 KB of flag lines, tickets and the error word (word LXO_XDEC_ERR_WORD) + 384 KB of hand-over words (tests/test_abi.py keeps
 # the definitions together)
 XDEC_BLOCK_BYTES = _abi.LXO_XDEC_BLOCK_BYTES
+XDEC_STATUS_WORDS = _abi.LXO_XDEC_ERR_WORD + 1      # the head of a block that tells how its chain went
+
+
+def _chain_words(w):
+    """(used, error) from the first XDEC_STATUS_WORDS int32 words of a chain's block: used = a ticket word of one of the 8 XCDs' lines is
+    set (its workgroups took their tickets), error = the error word"""
+    return bool(w[32:_abi.LXO_XDEC_ERR_WORD:64].any()), int(w[_abi.LXO_XDEC_ERR_WORD])
 
 
 class Engine(object):
@@ -272,7 +279,9 @@ class Engine(object):
                  "decoder_train_fwd")
         if (not self._xdec_checked and self.dtype == _abi.LXO_BF16 and self.step_kernels == 0 and self.device.type == "cuda"
                 and (B, H, W) not in self._nochain_shapes):
-            self._check_chain(st)
+            if self._check_chain():
+                self._ck(self.lib.lxo_decoder_train_fwd(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), _p(self._formula), st),
+                         "decoder_train_fwd")
 
     def chain_status(self, backward=False):
         """(used, error) of the persistent XCD-local decoder chain (csrc/xdec.hip) in the last lxo_decoder_train_fwd (backward=True: the
@@ -280,24 +289,24 @@ class Engine(object):
         assemble (a barrier timed out / an XCD got the wrong number of workgroups) and the step's decoder outputs are invalid.
         Synchronises the device."""
         o = XDEC_BLOCK_BYTES // 4 if backward else 0             # the backward chain's block
-        w = self.region("xdec_sync", "i32")[o:o + 8 * 64 + 1].cpu().numpy()
-        return bool(w[32:512:64].any()), int(w[512])
+        return _chain_words(self.region("xdec_sync", "i32")[o:o + XDEC_STATUS_WORDS].cpu().numpy())
 
-    def _check_chain(self, st):
-        """After the first forward that RAN the persistent chain (a shape that does not qualify leaves no tickets: checked again on the
-        next one): the chain relies on how the hardware places a 256-workgroup grid (32 per XCD, one per CU).  If it reports an error,
-        switch this engine to the launch-per-step chain for good and redo the decoder forward.  Later steps are watched without a host
-        synchronisation (_chain_health_post / _chain_health_poll)."""
-        used, err = self.chain_status()
-        self.chain_used = used and not err
+    def _check_chain(self, backward=False):
+        """After the first forward (backward) that RAN the persistent chain (a shape that does not qualify leaves no tickets: noted, and
+        not looked at again): the chain relies on how the hardware places a 256-workgroup grid (32 per XCD, one per CU).  If it reports an
+        error, this engine switches to the launch-per-step kernels for good, and the caller redoes the pass (-> the error word).  The words
+        are cleared by every call, chain or not, so the error is this call's.  Later steps are watched without a host synchronisation
+        (_chain_health_post / _chain_health_poll)."""
+        sfx = "_bwd" if backward else ""
+        used, err = self.chain_status(backward)
+        setattr(self, "chain_used" + sfx, used and not err)
         if used or err:
-            self._xdec_checked = True
+            setattr(self, "_xdec%s_checked" % sfx, True)
         else:
-            self._nochain_shapes.add((self.shape.B, self.shape.H, self.shape.W))      # this shape takes the launch-per-step kernels: no need to look again
+            getattr(self, "_nochain_shapes" + sfx).add((self.shape.B, self.shape.H, self.shape.W))
         if err:
-            self._chain_fallback("forward", err)
-            self._ck(self.lib.lxo_decoder_train_fwd(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), _p(self._formula), st),
-                     "decoder_train_fwd")
+            self._chain_fallback("backward" if backward else "forward", err)
+        return err
 
     def _chain_fallback(self, which, err):
         import warnings
@@ -439,16 +448,7 @@ class Engine(object):
             return
         decoder_bwd(chain)
         if chain and not self._xdec_bwd_checked and (self.shape.B, self.shape.H, self.shape.W) not in self._nochain_shapes_bwd:
-            # as for the forward chain, after the first backward that RAN it: a chain that did not assemble leaves an error word -> launch
-            # chain from now on.  (The words are cleared by every call, chain or not, so `err` is this call's.)
-            used, err = self.chain_status(backward=True)
-            self.chain_used_bwd = used and not err
-            if used or err:
-                self._xdec_bwd_checked = True
-            else:
-                self._nochain_shapes_bwd.add((self.shape.B, self.shape.H, self.shape.W))
-            if err:
-                self._chain_fallback("backward", err)
+            if self._check_chain(backward=True):      # as for the forward chain, after the first backward that RAN it
                 chain = False
                 decoder_bwd(False)
         if comm:
@@ -641,7 +641,7 @@ class Engine(object):
             # (with alternatives: + ids [n, k] | their logp [n, k] | rank | entropy in front of the sync words)
             na = 2 * n + B                                          # where the alternatives start
             ns = na + (2 * n * k + 2 * n if k else 0)               # ... and the sync words
-            buf = torch.empty(ns + (8 * 64 + 1 if chain else 0), dtype=torch.int32, device=self.device)
+            buf = torch.empty(ns + (XDEC_STATUS_WORDS if chain else 0), dtype=torch.int32, device=self.device)
             logp, top1, seq = buf[:n].view(torch.float32), buf[n:2 * n] if top1_on else None, buf[2 * n:2 * n + B].view(torch.float32)
             self._ck(self.lib.lxo_score_tokens(self.sref(), _p(self.ws), _p(self._formula), _p(ln_dev), _p(logp), _p(top1), _p(seq),
                                                self._stream()), "score_tokens")
@@ -652,7 +652,7 @@ class Engine(object):
                                                          _p(buf[na + 2 * n * k:na + 2 * n * k + n]), _p(buf[na + 2 * n * k + n:ns].view(torch.float32)),
                                                          self._stream()), "score_alternatives")
             if chain:
-                buf[ns:].copy_(self.region("xdec_sync", "i32")[:8 * 64 + 1])
+                buf[ns:].copy_(self.region("xdec_sync", "i32")[:XDEC_STATUS_WORDS])
             h = buf.cpu().numpy()
             out = (h[:n].view(np.float32).reshape(B, T)[:live].copy(), h[n:2 * n].reshape(B, T)[:live].copy() if top1_on else None,
                    h[2 * n:2 * n + B].view(np.float32)[:live].copy())
@@ -663,8 +663,7 @@ class Engine(object):
             if chain:
                 # a chain that did not assemble (forward() checks the first one itself): the launch-per-step kernels from now on, and
                 # this piece again
-                w = h[ns:]
-                used, err = bool(w[32:512:64].any()), int(w[512])
+                used, err = _chain_words(h[ns:])
                 self.chain_used = used and not err
                 if err:
                     self._chain_fallback("forward", err)
