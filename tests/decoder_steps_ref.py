@@ -1,5 +1,5 @@
 """float64 reference of the decoder's training step, one stage at a time, for tests/test_decoder_steps_sim.py (hipsim) and
-tests/test_gpu_decoder_steps.py.  Torch float64 only (on whatever device the tensors live); never calls the library.
+tests/test_gpu_decoder_steps.py, and of the decode step (tests/decode_steps_walk.py: test_decode_steps_sim.py, test_gpu_decode_steps.py).  Torch float64 only (on whatever device the tensors live); never calls the library.
 
 Every function takes the values the kernel actually READ -- a stored workspace region, a weight rounded to the compute dtype, an f32
 operand rounded to bf16 where the bf16 kernels convert it on load -- and returns the exact result with
@@ -75,6 +75,16 @@ def embed_rows(table, start, formula, T):
     return torch.cat([s, rows], 0)
 
 
+def token_table(table, start, Dp):
+    """the decode's input rows, one per possible previous token: row v < V = embedding_table[v], row V = start_token, columns D..Dp zero
+    (embed_table_kernel) -> [V + 1, Dp]"""
+    V, D = table.shape
+    t = torch.zeros(V + 1, Dp, dtype=torch.float64, device=table.device)
+    t[:V, :D] = f64(table)
+    t[V, :D] = f64(start).reshape(-1)
+    return t
+
+
 # -------------------------------------------------------------------------------------------------------------------- forward step --
 def lstm_gates(zx_t, a, kr, absf):
     """z = zx_t (stored) + a K[D:]; gates [B, 4U] as stored (i, j, f, o): (gates, bound)"""
@@ -102,6 +112,23 @@ def lstm_h(gates, c):
     U = c.shape[1]
     h = f64(gates)[:, 3 * U:] * torch.tanh(f64(c))
     return h, torch.full_like(h, EPS_CH)
+
+
+def lstm_state_from(gates, b_g, c_prev):
+    """the decode keeps no gates: c = f c_prev + i j from the gates the stage computes itself (lstm_gates' value and bound) and the stored
+    c_prev; bound = |c_prev| b_f + |j| b_i + |i| b_j + EPS_CH: (c, bound)"""
+    U = c_prev.shape[1]
+    cp = f64(c_prev)
+    i, j, f = gates[:, :U], gates[:, U:2 * U], gates[:, 2 * U:3 * U]
+    bi, bj, bf_ = b_g[:, :U], b_g[:, U:2 * U], b_g[:, 2 * U:3 * U]
+    return f * cp + i * j, cp.abs() * bf_ + j.abs() * bi + i.abs() * bj + EPS_CH
+
+
+def lstm_h_from(gates, b_g, c):
+    """h = o tanh(c) from the o gate the stage computes itself and the stored c; bound = |tanh c| b_o + EPS_CH: (h, bound)"""
+    U = c.shape[1]
+    tc = torch.tanh(f64(c))
+    return gates[:, 3 * U:] * tc, tc.abs() * b_g[:, 3 * U:] + EPS_CH
 
 
 def dropped(v, scale):
@@ -136,6 +163,20 @@ def context(alpha, img):
     """ctx = sum_r alpha_r img_r on the stored alpha: (ctx [B, C], S)"""
     a, x = f64(alpha), f64(img)
     return torch.einsum("br,brc->bc", a, x), torch.einsum("br,brc->bc", a.abs(), x.abs())
+
+
+def context_from_att_h(att_h, S_h, att_x, expd, beta, img, absf):
+    """the chain of a step that stores neither att_h nor alpha (the persistent greedy-decode chain): att_h (the float64 product, its sum
+    bound delta_k = absf S_h) -> alpha -> ctx.  tanh is 1-Lipschitz, so a region's score moves by at most eps = sum_k |beta_k| delta_k and
+    |d alpha_r| <= alpha_r (e^{2 eps} - 1) + attention_alpha's own bound; the context then moves by sum_r |d alpha_r| |img_r|, beside its own
+    sum (absf S) and the 28-bit hand-over of the chunk partials (PACK28 S): (ctx [B, C], bound)"""
+    tau, _ = tanh_tau(att_x, att_h, expd)
+    al, b_al = attention_alpha(tau, beta, absf)
+    eps = (f64(beta).reshape(1, -1).abs() * absf * S_h).sum(1, keepdim=True)
+    d_al = al * torch.expm1(2.0 * eps) + b_al
+    x = f64(img)
+    ctx, S = context(al, x)
+    return ctx, torch.einsum("br,brc->bc", d_al, x.abs()) + (absf + PACK28) * S
 
 
 def output_o(a, w, scale, absf):

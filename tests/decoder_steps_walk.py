@@ -87,30 +87,18 @@ def fused_steps(step_kernels, bf, U, O, E, C):
     return all(rstep_k_ok(k, bf) and rstep_k_ok(k, False) for k in (O + U, U, U + C, O, E, 4 * U, C))
 
 
-class Walk(object):
-    """One case: forward() checks the stored record, backward() the backward record and every decoder gradient; `worst` collects
-    err / bound per check."""
+class Checks(object):
+    """What a walk of this kind holds its stages with (shared with tests/decode_steps_walk.py): the operands as a GEMM of the mode reads them,
+    the bounds of tests/decoder_steps_ref.py, and `worst`, which collects err / bound per check."""
 
-    def __init__(self, io, case, formula_seed=11, first_len=None):
+    def __init__(self, io, case):
         self.io, self.case = io, case
         if io.bf:
             self.rel, self.absf = DR.REL_BF16, DR.ABS_BF16
         else:
             self.rel, self.absf = 0.0, DR.ABS_F32
         self.worst = {}
-        self.Vp, self.Dp = (io.V + 31) // 32 * 32, (io.D + 63) // 64 * 64
-        self.XH, self.HC = io.O + io.U, io.U + io.C
-        self.OFF_HT, self.OFF_CTX, self.REC = io.O + io.U, io.O + 2 * io.U, io.O + 2 * io.U + io.C
-        self.fused = fused_steps(io.step_kernels, io.bf, io.U, io.O, io.E, io.C) and not (io.dual and io.B >= 2 and io.B % 2 == 0)
-        self.mirr = io.bf and self.fused                     # the bf16 mirrors of the record / g / d_z exist and are what the GEMMs read
-        self.expd = io.bf and io.E <= 256 and (io.B * io.R * io.E) % 8 == 0      # csrc/plan.hip: Plan::att_exp
-        self.keep_on = 0.0 < io.keep < 1.0
-        self.formula, self.lengths = formulas(io.B, io.T, io.V, io.live_B, formula_seed, first_len)
-        self.ftor = torch.from_numpy(self.formula).to(io.dev)
-        io.set_formula(self.formula, self.lengths)
-        self.st = {}
 
-    # ---------------------------------------------------------------------------------------------------------------- helpers --
     def q(self, t):
         """an operand as a GEMM of this mode reads it: rounded to bf16 in bf16 mode (weights are packed as bf16, f32 operands are converted
         on load), as it is in the f32 mode"""
@@ -148,6 +136,28 @@ class Walk(object):
     def f32(self, name, shape):
         return self.io.values(name, shape, "f32")
 
+    def report(self):
+        print("%s: worst err / bound: %s" % (self.case, ", ".join("%s %.3f" % (k, v) for k, v in self.worst.items())))
+
+
+class Walk(Checks):
+    """One case: forward() checks the stored record, backward() the backward record and every decoder gradient."""
+
+    def __init__(self, io, case, formula_seed=11, first_len=None):
+        Checks.__init__(self, io, case)
+        self.Vp, self.Dp = (io.V + 31) // 32 * 32, (io.D + 63) // 64 * 64
+        self.XH, self.HC = io.O + io.U, io.U + io.C
+        self.OFF_HT, self.OFF_CTX, self.REC = io.O + io.U, io.O + 2 * io.U, io.O + 2 * io.U + io.C
+        self.fused = fused_steps(io.step_kernels, io.bf, io.U, io.O, io.E, io.C) and not (io.dual and io.B >= 2 and io.B % 2 == 0)
+        self.mirr = io.bf and self.fused                     # the bf16 mirrors of the record / g / d_z exist and are what the GEMMs read
+        self.expd = io.bf and io.E <= 256 and (io.B * io.R * io.E) % 8 == 0      # csrc/plan.hip: Plan::att_exp
+        self.keep_on = 0.0 < io.keep < 1.0
+        self.formula, self.lengths = formulas(io.B, io.T, io.V, io.live_B, formula_seed, first_len)
+        self.ftor = torch.from_numpy(self.formula).to(io.dev)
+        io.set_formula(self.formula, self.lengths)
+        self.st = {}
+
+    # ---------------------------------------------------------------------------------------------------------------- helpers --
     def scale(self, which, t, width):
         io = self.io
         return DR.masks(io.keep, io.seed, which, t, io.B, width, io.dev)[0]
@@ -397,6 +407,3 @@ class Walk(object):
 
     def _datth_terms(self, de_t, dtau, beta):
         return DR.f64(beta).reshape(1, -1).abs() * torch.einsum("br,brk->bk", DR.f64(de_t).abs(), dtau.abs())
-
-    def report(self):
-        print("%s: worst err / bound: %s" % (self.case, ", ".join("%s %.3f" % (k, v) for k, v in self.worst.items())))
