@@ -228,6 +228,29 @@ int lxo_ce_loss_fwd_bwd(const lxo_shape* s, void* ws, const int32_t* formula,
  * synchronisation sits between forward and backward (img2seq.py:69-71 takes the mean over all tokens of the batch). */
 int lxo_ce_loss_fwd_bwd_dev(const lxo_shape* s, void* ws, const int32_t* formula,
                             const int32_t* lengths, const float* ntok_dev, void* stream);
+/* The weighted loss: token (b, t) weighs w = w_tok[b][t] * w_row[b] (device f32 [B, T] / [B]; ONE f32 product, a NULL factor is 1; at least one of the
+ * two is given, else -1).  d(logits)[t * B + b][j] = (softmax_j - [j == target]) * (w * inv_norm) for t < lengths[b] -- the scale is the single f32
+ * product w * inv_norm -- and 0 for t >= lengths[b] and in the padding columns [V, Vp), as in lxo_ce_loss_fwd_bwd.  A weight may be negative (a
+ * transcription to train AGAINST) or 0 (a live row of weight 0 gets zeros of either sign); weights are not checked for NaN.  norm_dev (nullable,
+ * device f32 [1]): 1 / norm_dev[0] replaces inv_norm, as ntok_dev does in lxo_ce_loss_fwd_bwd_dev.
+ * ws region "loss" = {sum w CE, live token count (whatever the weights), sum w, sum CE (unweighted)} over the live tokens; the forward chain's error
+ * word turns [0] into NaN.  The four go through the ordered per-workgroup slots of ws region "det_part" in every mode.
+ * With w_tok == 1 everywhere d(logits) and "loss"[0..1] are lxo_ce_loss_fwd_bwd's bit for bit; with w_row == c, d(logits) is the one it leaves
+ * for inv_ntok = c * inv_norm (the f32 product).  The rest of the training step is linear in d(logits): lxo_train_bwd after this call leaves the
+ * gradient of sum w CE * inv_norm. */
+int lxo_ce_loss_weighted(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
+                         const float* w_tok, const float* w_row, float inv_norm, const float* norm_dev, void* stream);
+/* Minimum-risk weights on the device, shape-free: rows group_off[g] .. group_off[g + 1] - 1 (device int32 [G + 1], ascending, group_off[0] == 0,
+ * group_off[G] <= rows) are the candidate transcriptions of image g, seq_logp their sequence log-probs (lxo_score_tokens' seq_out) and cost their costs
+ * (device f32 [rows]).  Q_c = softmax_c(alpha * seq_logp_c) over the group (maximum subtracted), R_g = sum_c Q_c cost_c,
+ * w_out[c] = alpha * Q_c * (R_g - cost_c) (f32 [rows], NOT NULL), q_out[c] = Q_c (nullable), risk_out[0] = sum_g R_g (nullable), added in ascending g.
+ * THE IDENTITY: with CE_c = -seq_logp_c, d(sum_c Q_c cost_c) / d(CE_c) = w_c exactly, and sum_c w_c = 0 per group -- so lxo_ce_loss_weighted with
+ * w_row = w_out, no token weights and inv_norm = 1 / G leaves the gradient of the mean expected cost.
+ * Rows in [group_off[G], rows) (a chain batch's dead rows) get w = q = 0; a group may have any size >= 0, one candidate gives w = 0 exactly; G == 0
+ * zeroes w_out[0 .. rows).  One wave per group, fixed-order reductions, expf in both dtype modes, no atomics: the same bytes in every run.  The
+ * device clamps an offset into [0, rows].  -1: a NULL w_out, seq_logp, cost or group_off, G < 0, rows < 0, alpha not finite. */
+int lxo_mrt_weights(const float* seq_logp, const float* cost, const int32_t* group_off, int G, int rows, float alpha,
+                    float* w_out, float* q_out, float* risk_out, void* stream);
 /* Teacher-forced scoring, after lxo_decoder_train_fwd with the same shape and formula: per-token log-probs, the model's top-1 token per
  * position and per-sequence sums; reads ws region "logits", writes only the caller's outputs (device, [B, T] / [B]).
  * logp_out f32 [B, T] (NOT NULL): log_softmax(logits of step t)[formula[b][t]] for t < lengths[b], 0 after.

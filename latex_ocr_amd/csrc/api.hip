@@ -130,6 +130,21 @@ extern "C" int lxo_ce_loss_fwd_bwd_dev(const lxo_shape* s, void* ws, const int32
     CHECK_LAUNCH(lxo_impl_ce_loss(P, ws, formula, lengths, 0.f, ntok_dev, (hipStream_t)stream), "lxo_ce_loss_fwd_bwd_dev");
     return 0;
 }
+extern "C" int lxo_ce_loss_weighted(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths, const float* w_tok, const float* w_row,
+                                    float inv_norm, const float* norm_dev, void* stream) {
+    MAKE_PLAN(P, s);
+    if (!w_tok && !w_row) return fail(-1, "lxo_ce_loss_weighted: w_tok and w_row are both NULL (the unweighted loss is lxo_ce_loss_fwd_bwd)");
+    CHECK_LAUNCH(lxo_impl_ce_loss(P, ws, formula, lengths, inv_norm, norm_dev, (hipStream_t)stream, w_tok, w_row), "lxo_ce_loss_weighted");
+    return 0;
+}
+extern "C" int lxo_mrt_weights(const float* seq_logp, const float* cost, const int32_t* group_off, int G, int rows, float alpha,
+                               float* w_out, float* q_out, float* risk_out, void* stream) {
+    if (!w_out || !seq_logp || !cost || !group_off) return fail(-1, "lxo_mrt_weights: null w_out, seq_logp, cost or group_off");
+    if (G < 0 || rows < 0) return fail(-1, "lxo_mrt_weights: G < 0 or rows < 0");
+    if (!(alpha - alpha == 0.f)) return fail(-1, "lxo_mrt_weights: alpha is not finite");
+    CHECK_LAUNCH(lxo_k_mrt_weights(seq_logp, cost, group_off, G, rows, alpha, w_out, q_out, risk_out, (hipStream_t)stream), "lxo_mrt_weights");
+    return 0;
+}
 extern "C" int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
                                 float* logp_out, int32_t* top1_out, float* seq_out, void* stream) {
     MAKE_PLAN(P, s);

@@ -2,8 +2,18 @@
 #pragma once
 #include "decoder_kernels.h"
 // ntok_dev (nullable): device scalar holding the global token count; when set the kernel uses 1 / *ntok_dev instead of inv_ntok
+// weights (nullable, lxo_ce_loss_weighted): device f32 tok [B][T] and row [B], either nullable -- token (b, t) weighs tok[b][t] * row[b] (a NULL factor is 1, any
+// sign); d(logits) of a live row is scaled by w * inv_ntok and loss_acc = {sum w CE, token count, sum w, sum CE}: four statistics per slot of `det`
+// (512 x 4 floats, else -2).  Without weights: {sum CE, token count} and the kernels of before
+struct CeWeights { const float* tok; const float* row; };
 int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
-                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st);      // chain_err (nullable): error word of the persistent decoder chain; non-zero poisons the loss (NaN)
+                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st,      // chain_err (nullable): error word of the persistent decoder chain; non-zero poisons the loss (NaN)
+                  const CeWeights* weights = nullptr);
+// minimum-risk weights of candidate rows grouped by image (rows group_off[g] .. group_off[g + 1] - 1, G groups): Q = softmax(alpha seq_logp) over a group,
+// R_g = sum Q cost, w_out = alpha Q (R_g - cost), q_out (nullable) = Q, risk_out (nullable) [1] = sum_g R_g added in ascending g; rows behind the last group: 0.
+// Offsets are clamped into [0, rows] on the device.  No atomics: the same bytes in every run
+int lxo_k_mrt_weights(const float* seq_logp, const float* cost, const int* group_off, int G, int rows, float alpha, float* w_out, float* q_out,
+                      float* risk_out, hipStream_t st);
 // teacher-forced scoring: logp_out [B][T] (logits[t * B + b][formula[b][t]] - lse), top1_out [B][T] (nullable), seq_out [B] (nullable, ordered f32
 // sum); rows t >= lengths[b]: 0 / -1; chain_err set: NaN / -1.  Reads the logits only.
 int lxo_k_score(int dt, const float* logits, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out,

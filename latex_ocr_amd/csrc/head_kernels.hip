@@ -1,5 +1,6 @@
-// The output head: every kernel that reads a row of logits and turns it into a loss (ce_loss*), a log-prob (score*), a choice list (score_alt*) or a token
-// (argmax_kernel, beam_step*), their launchers, and -- first -- the row steps they are made of.
+// The output head: every kernel that reads a row of logits and turns it into a loss (ce_loss*, weighted or not), a log-prob (score*), a choice list
+// (score_alt*) or a token (argmax_kernel, beam_step*), the minimum-risk weights made from sequence log-probs (mrt_*), their launchers, and -- first --
+// the row steps they are made of.
 #include "head_kernels.h"
 #include "drop.h"
 #include <stdlib.h>
@@ -411,6 +412,33 @@ LXO_DEV void ce_end(float* red, float ce_sum, float n_sum, float* loss_acc, floa
     }
 }
 
+// Weights of the loss (lxo_ce_loss_weighted): the CE kernels end in a parameter pack W that is empty -- the unweighted kernels, argument for argument
+// the kernels they were -- or one CeWeights (WT): token (b, t) then weighs tok[b][t] * row[b], ONE f32 product, a NULL factor is 1, any sign
+LXO_DEV float ce_weight(const RowTok&) { return 1.f; }
+LXO_DEV float ce_weight(const RowTok& r, const CeWeights& q) { return (q.tok ? q.tok[r.o] : 1.f) * (q.row ? q.row[r.b] : 1.f); }
+// d(logits) scale of a row: inv_ntok on a live unweighted row, the single f32 product w * inv_norm on a weighted one, 0 past lengths[b]
+template <bool WT>
+LXO_DEV float ce_scale(const RowTok& r, float w, float inv_ntok) {
+    if constexpr (WT) return r.live ? w * inv_ntok : 0.f;
+    else return r.live ? inv_ntok : 0.f;
+}
+// a live row's statistics: {CE, 1}, weighted {w CE, 1, w, CE}
+template <bool WT>
+LXO_DEV void ce_stats(float& ce_sum, float& n_sum, float& w_sum, float& u_sum, float w, float ce) {
+    if constexpr (WT) { ce_sum += w * ce; w_sum += w; u_sum += ce; } else ce_sum += ce;
+    n_sum += 1.0f;
+}
+// ce_end for the four: always through the ordered slots, 4 per workgroup, each added as ce_end adds its two
+LXO_DEV void ce_end_w(float* red, float ce_sum, float n_sum, float w_sum, float u_sum, float* loss_part) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[wave] = ce_sum; red[4 + wave] = n_sum; red[8 + wave] = w_sum; red[12 + wave] = u_sum; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const float* q = red + 4 * threadIdx.x;
+        loss_part[4 * blockIdx.x + threadIdx.x] = q[0] + q[1] + q[2] + q[3];
+    }
+}
+
 // Score of the beam candidate (slot, token c) from the token's raw logit x: log_softmax, a finished slot masked (0 at END, f32 lowest elsewhere),
 // plus the slot's running log-prob; AL: a banned token scores -inf, also for a finished slot
 template <bool AL>
@@ -437,44 +465,48 @@ LXO_DEV void beam_emit(int b, int k, int tid, int time, int id, int par, float v
 
 // ---- loss ----
 // loss of img2seq.py:68-75 + gradient; one wave per (t, b) row, rows strided over the grid, three strided passes per row
-template <typename CT>
+// W = CeWeights (lxo_ce_loss_weighted): the row's scale is w * inv_norm and the statistics are the four of ce_stats; everything else is the same row
+template <typename CT, typename... W>
 __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
                                                      const int* __restrict__ lengths, CT* __restrict__ dlogits,
                                                      float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
-                                                     const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
-    __shared__ float red[8];
+                                                     const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp, W... wt) {
+    constexpr bool WT = sizeof...(W) != 0;
+    __shared__ float red[WT ? 16 : 8];
     inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float ce_sum = 0.f, n_sum = 0.f;
+    float ce_sum = 0.f, n_sum = 0.f, w_sum = 0.f, u_sum = 0.f;
     for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
         const RowTok r = row_tok(row, B, T, lengths);
         const float* lg = logits + (long long)row * Vp;
         CT* dl = dlogits + (long long)row * Vp;
         const int tgt = row_target(formula, r.o, V);
         const float lse = strided_lse<false>(lg, lane, V, nullptr);
-        const float scale = r.live ? inv_ntok : 0.f;
+        const float w = ce_weight(r, wt...);
+        const float scale = ce_scale<WT>(r, w, inv_ntok);
         for (int j = lane; j < Vp; j += 64) {
             float g = 0.f;
             if (j < V) g = (expf(lg[j] - lse) - (j == tgt ? 1.f : 0.f)) * scale;
             dl[j] = from_f32<CT>(g);
         }
-        if (r.live) { ce_sum += lse - lg[tgt]; n_sum += 1.0f; }
+        if (r.live) ce_stats<WT>(ce_sum, n_sum, w_sum, u_sum, w, lse - lg[tgt]);
     }
-    ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
+    if constexpr (WT) ce_end_w(red, ce_sum, n_sum, w_sum, u_sum, loss_part); else ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
 }
 
 // The same with the row held in registers (Vp <= 64 * KV): ONE pass over the logits instead of three passes of 4-byte loads, and every row
 // has its own wave from the start (the three-pass kernel: 31 us for 13 MB at the benchmark shape, a chain of dependent passes per row; this one 8).
-template <typename CT, int KV>
+template <typename CT, int KV, typename... W>
 __global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
                                                           const int* __restrict__ lengths, CT* __restrict__ dlogits,
                                                           float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
-                                                          const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp) {
+                                                          const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp, W... wt) {
+    constexpr bool WT = sizeof...(W) != 0;
     constexpr bool BF = is_bf16<CT>::value;
-    __shared__ float red[8];
+    __shared__ float red[WT ? 16 : 8];
     inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float ce_sum = 0.f, n_sum = 0.f;
+    float ce_sum = 0.f, n_sum = 0.f, w_sum = 0.f, u_sum = 0.f;
     for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
         const RowTok r = row_tok(row, B, T, lengths);
         const float* lg = logits + (long long)row * Vp;
@@ -484,7 +516,8 @@ __global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restri
         float x[KV];
         row_load<KV>(lg, lane, V, Vp, x);
         const float lse = row_lse<BF, KV>(x);
-        const float scale = r.live ? inv_ntok : 0.f;
+        const float w = ce_weight(r, wt...);
+        const float scale = ce_scale<WT>(r, w, inv_ntok);
 #pragma unroll
         for (int q = 0; q < KV / 4; ++q) {
             const int j0 = 4 * (lane + 64 * q);
@@ -499,9 +532,9 @@ __global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restri
             if constexpr (BF) { const u32x2 pk = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])}; *reinterpret_cast<u32x2*>(dl + j0) = pk; }
             else { const f32x4 gv = {g[0], g[1], g[2], g[3]}; *reinterpret_cast<f32x4*>(dl + j0) = gv; }
         }
-        if (r.live) { ce_sum += lse - xt; n_sum += 1.0f; }
+        if (r.live) ce_stats<WT>(ce_sum, n_sum, w_sum, u_sum, w, lse - xt);
     }
-    ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
+    if constexpr (WT) ce_end_w(red, ce_sum, n_sum, w_sum, u_sum, loss_part); else ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
 }
 
 // ---- teacher-forced scoring (lxo_score_tokens) ----
@@ -585,6 +618,67 @@ __global__ __launch_bounds__(256) void score_seq_kernel(const float* __restrict_
         for (int e = 0; e < 16; ++e) if (t0 + e < n) s += v[e];
     }
     seq_out[b] = (chain_err && chain_err[0] != 0u) ? __uint_as_float(0x7fc00000u) : s;
+}
+
+// ---- minimum-risk weights (lxo_mrt_weights) ----
+// Rows [lo, hi) are the candidates of one image: Q_c = softmax_c(alpha seq_logp_c) around the group's maximum, R = sum_c Q_c cost_c, w_c = alpha Q_c (R - cost_c)
+// = d R / d CE_c with CE_c = -seq_logp_c, so the weighted loss kernel's d(logits) is the gradient of the expected cost.  One wave per group, lanes striding
+// it in steps of 64; wave_max / wave_sum add in a fixed order and the exponential is expf in both dtype modes: the same bytes in every run and every mode.
+// -> R (0 for an empty group); w_out NULL: nothing is written (mrt_risk_kernel adds the groups' R this way).  alpha seq_logp is smp_y's rounded product
+LXO_DEV float mrt_group(const float* lp, const float* cost, int lo, int hi, float alpha, int lane, float* w_out, float* q_out) {
+    float m = -3.0e38f;
+    for (int c = lo + lane; c < hi; c += 64) m = fmaxf(m, smp_y(lp[c], alpha));
+    m = wave_max(m);
+    float l = 0.f;
+    for (int c = lo + lane; c < hi; c += 64) l += expf(smp_y(lp[c], alpha) - m);
+    l = wave_sum(l);
+    const float inv = 1.0f / l;
+    float R = 0.f;
+    for (int c = lo + lane; c < hi; c += 64) R += (expf(smp_y(lp[c], alpha) - m) * inv) * cost[c];
+    R = wave_sum(R);
+    if (w_out)
+        for (int c = lo + lane; c < hi; c += 64) {
+            const float q = expf(smp_y(lp[c], alpha) - m) * inv;
+            w_out[c] = alpha * q * (R - cost[c]);
+            if (q_out) q_out[c] = q;
+        }
+    return R;
+}
+// what the device holds is read defensively: an offset is clamped into [0, rows] and a group never ends in front of its start
+LXO_DEV void mrt_bounds(const int* off, int g, int rows, int& lo, int& hi) {
+    lo = min(max(off[g], 0), rows);
+    hi = max(min(max(off[g + 1], 0), rows), lo);
+}
+__global__ __launch_bounds__(256) void mrt_weights_kernel(const float* __restrict__ lp, const float* __restrict__ cost, const int* __restrict__ off, int G,
+                                                         int rows, float alpha, float* __restrict__ w_out, float* __restrict__ q_out) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g < G) {
+        int lo, hi;
+        mrt_bounds(off, g, rows, lo, hi);
+        mrt_group(lp, cost, lo, hi, alpha, lane, w_out, q_out);
+    }
+    // the rows behind the last group (the chain batch's dead rows; G == 0: every row) weigh nothing
+    for (int i = min(max(off[G], 0), rows) + blockIdx.x * 256 + threadIdx.x; i < rows; i += gridDim.x * 256) { w_out[i] = 0.f; if (q_out) q_out[i] = 0.f; }
+}
+// risk_out[0] = R_0 + R_1 + ... in ascending g, added by one thread: ONE workgroup, its four waves take four groups at a time
+__global__ __launch_bounds__(256) void mrt_risk_kernel(const float* __restrict__ lp, const float* __restrict__ cost, const int* __restrict__ off, int G,
+                                                      int rows, float alpha, float* __restrict__ risk_out) {
+    __shared__ float red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float risk = 0.f;
+    for (int g0 = 0; g0 < G; g0 += 4) {
+        float R = 0.f;
+        if (g0 + wave < G) {
+            int lo, hi;
+            mrt_bounds(off, g0 + wave, rows, lo, hi);
+            R = mrt_group(lp, cost, lo, hi, alpha, lane, nullptr, nullptr);
+        }
+        if (lane == 0) red[wave] = R;
+        __syncthreads();
+        if (threadIdx.x == 0) for (int e = 0; e < 4 && g0 + e < G; ++e) risk += red[e];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) risk_out[0] = risk;
 }
 
 // ---- alternatives per position (lxo_score_alternatives) ----
@@ -1003,23 +1097,35 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
 #define BY_KV(Vp, ROWS) do { if ((Vp) <= 256) ROWS(4); else if ((Vp) <= 512) ROWS(8); else ROWS(16); } while (0)
 
 int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
-                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st) {
+                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st, const CeWeights* weights) {
     int g = cdiv(T * B, 4);
     float* part = (det.p && det.floats >= 1024) ? det.p : nullptr;      // loss_acc is zero on entry (lxo_impl_ce_loss)
+    const int nst = weights ? 4 : 2;                                    // statistics per workgroup slot
+    if (weights && !(det.p && det.floats >= 2048)) return -2;           // the four weighted statistics go through the ordered slots only
+    const CeWeights wt = weights ? *weights : CeWeights{};
 #define CE_ARGS(CT_) logits, formula, lengths, (CT_*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp
+    // CE_WT(CT, KERNEL<...): KERNEL<...> or, with weights, KERNEL<..., CeWeights>
+#define CE_WT(CT_, ...) do { if (weights) LAUNCH((__VA_ARGS__, CeWeights>), g, CE_ARGS(CT_), wt); else LAUNCH((__VA_ARGS__>), g, CE_ARGS(CT_)); } while (0)
     if (Vp % 4 == 0 && Vp <= 1024 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0) {
         // a wave per row, the row in registers (one pass); the f32 parity mode keeps at most 512 workgroups (its ordered partial sums)
         if (g > (part ? 512 : 2048)) g = part ? 512 : 2048;
-#define CE_ROWS(KV_) do { if (dt == LXO_BF16) LAUNCH((ce_loss_rows_kernel<bf16_t, KV_>), g, CE_ARGS(bf16_t)); else LAUNCH((ce_loss_rows_kernel<float, KV_>), g, CE_ARGS(float)); } while (0)
+#define CE_ROWS(KV_) do { if (dt == LXO_BF16) CE_WT(bf16_t, ce_loss_rows_kernel<bf16_t, KV_); else CE_WT(float, ce_loss_rows_kernel<float, KV_); } while (0)
         BY_KV(Vp, CE_ROWS);
 #undef CE_ROWS
     } else {
         if (g > 512) g = 512;
-        if (dt == LXO_BF16) LAUNCH((ce_loss_kernel<bf16_t>), g, CE_ARGS(bf16_t));
-        else LAUNCH((ce_loss_kernel<float>), g, CE_ARGS(float));
+        if (dt == LXO_BF16) CE_WT(bf16_t, ce_loss_kernel<bf16_t);
+        else CE_WT(float, ce_loss_kernel<float);
     }
+#undef CE_WT
 #undef CE_ARGS
-    if (part) return lxo_k_det_reduce(part, g, 2, 2, loss_acc, st);
+    if (part) return lxo_k_det_reduce(part, g, nst, nst, loss_acc, st);
+    DONE;
+}
+int lxo_k_mrt_weights(const float* seq_logp, const float* cost, const int* group_off, int G, int rows, float alpha, float* w_out, float* q_out,
+                      float* risk_out, hipStream_t st) {
+    LAUNCH(mrt_weights_kernel, G > 4 ? cdiv(G, 4) : 1, seq_logp, cost, group_off, G, rows, alpha, w_out, q_out);
+    if (risk_out) LAUNCH(mrt_risk_kernel, 1, seq_logp, cost, group_off, G, rows, alpha, risk_out);
     DONE;
 }
 int lxo_k_score(int dt, const float* logits, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out,

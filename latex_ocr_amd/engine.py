@@ -374,9 +374,7 @@ class Engine(object):
         self._ck(self.lib.lxo_set_encoder_side_stream(ctypes.c_void_p(es.cuda_stream) if es is not None else ctypes.c_void_p(0)),
                  "set_encoder_side_stream")
 
-    def loss(self, lengths, inv_ntok=None, ntok_dev=None, ntok_event=None):
-        """Loss statistics + d(logits).  Either inv_ntok (host float) or ntok_dev (device float32 [1] = the global token count,
-        e.g. from DataParallel.sum_count_async; the compute stream waits for ntok_event, the host does not)."""
+    def _bind_lengths(self, lengths):
         dead = int(self.shape.B) - int(getattr(self, "live_B", self.shape.B))
         if dead > 0:                                               # the dead rows forward() appended: length 0 = outside the loss mask
             if isinstance(lengths, torch.Tensor):
@@ -388,12 +386,73 @@ class Engine(object):
             else:
                 lengths = np.concatenate([np.asarray(lengths, dtype=np.int32).reshape(-1), np.zeros(dead, np.int32)])
         self._lengths = self._lengths_dev(lengths)
+
+    @staticmethod
+    def _check_weights(who, weights, row_weights, B, T):
+        """The loss weights before any launch: a host array is checked for shape and finiteness (-> f32), a device tensor for its shape only (a
+        look at its values would cost a synchronisation).  B, T: the caller's batch, without the chain batch's dead rows."""
+        out = []
+        for name, w, shp in (("weights", weights, (B, T)), ("row_weights", row_weights, (B,))):
+            if w is None or isinstance(w, torch.Tensor):
+                if w is not None and tuple(w.shape) != shp:
+                    raise ValueError("%s: %s must be %s, got %s" % (who, name, list(shp), list(w.shape)))
+                out.append(w)
+                continue
+            a = np.asarray(w)
+            if a.shape != shp or a.dtype.kind not in "fiu":
+                raise ValueError("%s: %s must be a real array of shape %s, got %s %s" % (who, name, list(shp), a.dtype, list(a.shape)))
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if not np.isfinite(a).all():
+                raise ValueError("%s: %s holds a NaN or an infinity (or a value beyond f32)" % (who, name))
+            out.append(a)
+        return out
+
+    def _weights_dev(self, w, dead):
+        """f32 on the device, zero rows appended for the dead rows forward() added (weight 0 on a length of 0); a host array goes through pinned
+        memory and an asynchronous copy, as the lengths do"""
+        if isinstance(w, torch.Tensor):
+            w = w.to(device=self.device, dtype=torch.float32).contiguous()
+            if dead > 0:
+                w = torch.cat([w, torch.zeros((dead,) + tuple(w.shape[1:]), dtype=torch.float32, device=self.device)])
+            return w
+        if dead > 0:
+            w = np.concatenate([w, np.zeros((dead,) + w.shape[1:], np.float32)])
+        t = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+        if self.device.type != "cuda":
+            return t
+        return t.pin_memory().to(self.device, non_blocking=True)
+
+    def loss(self, lengths, inv_ntok=None, ntok_dev=None, ntok_event=None, weights=None, row_weights=None, _padded=False):
+        """Loss statistics + d(logits).  Either inv_ntok (host float) or ntok_dev (device float32 [1] = the global token count,
+        e.g. from DataParallel.sum_count_async; the compute stream waits for ntok_event, the host does not).
+        weights [B, T] / row_weights [B] (host arrays or device tensors, either or both): the weighted loss lxo_ce_loss_weighted -- token (b, t)
+        weighs weights[b, t] * row_weights[b], of any sign; inv_ntok / ntok_dev are then its normaliser, whatever the caller chose, and the
+        statistics are the four {sum w CE, token count, sum w, sum CE}.  Without weights: {sum CE, token count}, as ever."""
+        if weights is None and row_weights is None:
+            self._bind_lengths(lengths)
+            wt = wr = None
+        else:
+            live = int(getattr(self, "live_B", self.shape.B))
+            dead = int(self.shape.B) - live
+            if not _padded:                                        # (mrt_grads hands over what it built for the chain batch)
+                weights, row_weights = self._check_weights("loss", weights, row_weights, live, int(self.shape.T))
+                weights = self._weights_dev(weights, dead) if weights is not None else None
+                row_weights = self._weights_dev(row_weights, dead) if row_weights is not None else None
+            if lengths is not None:
+                self._bind_lengths(lengths)
+            wt, wr = self._loss_weights = (weights, row_weights)      # alive until the next call
         if ntok_dev is not None:
             if ntok_event is not None:
                 torch.cuda.current_stream(self.device).wait_event(ntok_event)
             self._ntok_dev = ntok_dev          # keep alive until the kernel has been enqueued
             if ntok_dev.is_cuda:               # allocated on the count stream, read on this one: the allocator must not hand the
                 ntok_dev.record_stream(torch.cuda.current_stream(self.device))   # block to a later upload before this kernel ran
+        if wt is not None or wr is not None:
+            self._ck(self.lib.lxo_ce_loss_weighted(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), _p(wt), _p(wr),
+                                                   ctypes.c_float(0.0 if ntok_dev is not None else inv_ntok), _p(ntok_dev), self._stream()),
+                     "ce_loss_weighted")
+            return self.region("loss")[:4]
+        if ntok_dev is not None:
             self._ck(self.lib.lxo_ce_loss_fwd_bwd_dev(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), _p(ntok_dev),
                                                       self._stream()), "ce_loss_dev")
         else:
@@ -535,10 +594,20 @@ class Engine(object):
                                         _p(scale), st), "adam")
         self.pack()
 
-    def train_step(self, img, formula, lengths, lr, clip=-1.0, dist=None, sync_loss=True, dropout=1.0, dropout_seed=None):
+    def train_step(self, img, formula, lengths, lr, clip=-1.0, dist=None, sync_loss=True, dropout=1.0, dropout_seed=None,
+                   weights=None, row_weights=None, norm=None):
         """One optimisation step of img2seq.py:_run_train's body.  Returns the batch loss
         (token mean over the global batch) or None when sync_loss is False.  dropout = config.dropout
-        (keep probability, img2seq.py:166); masks are keyed by (dropout_seed or a per-engine step counter)."""
+        (keep probability, img2seq.py:166); masks are keyed by (dropout_seed or a per-engine step counter).
+        weights [B, T] / row_weights [B] (host arrays or device tensors): the step minimises sum_{b,t} weights[b, t] row_weights[b] CE[b, t] / norm
+        (loss()); norm = None: the global token count, as without weights (data parallel: the device-side count); norm = a float: the caller's
+        own normaliser, the GLOBAL one under dist.  Returns that weighted loss."""
+        weighted = weights is not None or row_weights is not None
+        if weighted:
+            weights, row_weights = self._check_weights("train_step", weights, row_weights, int(img.shape[0]), int(formula.shape[1]))
+        if norm is not None and not (math.isfinite(float(norm)) and float(norm) != 0.0):
+            raise ValueError("train_step: norm must be a finite non-zero number, got %r" % (norm,))
+        wkw = dict(weights=weights, row_weights=row_weights) if weighted else {}
         drop = None
         if dropout is not None and 0.0 < float(dropout) < 1.0:
             self.drop_step = getattr(self, "drop_step", 0) + 1
@@ -550,14 +619,14 @@ class Engine(object):
             # finished step differs from rank to rank, and the Adam time step a dropped update gives back enters lr_t -- there every rank
             # looks at a step's words at the same distance (the ring slot's reuse, four steps later, or a synchronising caller's wait)
             self._chain_health_poll()
-        if dist is not None:
+        if dist is not None and norm is None:
             # the global token count travels rank -> device -> all-reduce -> loss kernel; no host sync inside the step
             ntok, ev = dist.sum_count_async(n_local)
             self.forward(img, formula, dropout=drop, before_decoder=ev)
-            stats = self.loss(lengths, ntok_dev=ntok, ntok_event=ev)
+            stats = self.loss(lengths, ntok_dev=ntok, ntok_event=ev, **wkw)
         else:
             self.forward(img, formula, dropout=drop)
-            stats = self.loss(lengths, 1.0 / float(n_local))
+            stats = self.loss(lengths, 1.0 / (float(n_local) if norm is None else float(norm)), **wkw)
         self.backward(comm=dist.reduce_range_fn(self.grads) if dist is not None else None)
         if dist is not None:
             dist.finish()
@@ -577,10 +646,87 @@ class Engine(object):
             self._redoing = True
             try:
                 return self.train_step(img, formula, lengths, lr, clip=clip, dist=None, sync_loss=True, dropout=dropout,
-                                       dropout_seed=drop[1] if drop is not None else None)
+                                       dropout_seed=drop[1] if drop is not None else None, norm=norm, **wkw)
             finally:
                 self._redoing = False
-        return float(s[0]) / float(s[1])
+        return float(s[0]) / (float(s[1]) if norm is None else float(norm))
+
+    def mrt_grads(self, img, cand, cand_lengths, group_sizes, cost, alpha, dropout=None):
+        """Forward and backward of one minimum-risk step, into self.grads: the gradient of (1 / G) sum_g sum_c Q_c cost_c, Q = softmax over image g's
+        candidates of alpha * log p(candidate | image) -- the mean expected cost under the model's own, sharpened, distribution over the candidates.
+        img [G, H, W]; cand [rows, T] int32 (pad_batch_formulas' padding) and cand_lengths / cost [rows]: image g's candidates are the
+        group_sizes[g] consecutive rows behind those of image g - 1.  Image g is repeated for each of its candidates (the encoder runs per
+        row), then: forward, lxo_score_tokens (sequence log-probs, device), lxo_mrt_weights (w_c = alpha Q_c (R_g - cost_c) = d R_g / d CE_c,
+        device), the weighted loss with row_weights = w and normaliser G, backward.  No host synchronisation in between.
+        -> device tensors (risk [1] = sum_g R_g, q [rows], w [rows])."""
+        cand_h = cand.detach().cpu().numpy() if isinstance(cand, torch.Tensor) else np.asarray(cand)
+        ln = np.ascontiguousarray(np.asarray(cand_lengths), dtype=np.int64).reshape(-1)
+        gs = np.ascontiguousarray(np.asarray(group_sizes), dtype=np.int64).reshape(-1)
+        c = np.asarray(cost, dtype=np.float64).reshape(-1)
+        G, rows = int(img.shape[0]), int(cand_h.shape[0])
+        if cand_h.ndim != 2 or ln.shape[0] != rows or c.shape[0] != rows or gs.shape[0] != G:
+            raise ValueError("mrt_step: cand must be [rows, T], cand_lengths and cost [rows] and group_sizes [G = %d images], got %s, %s, %s and %s"
+                             % (G, list(cand_h.shape), list(ln.shape), list(c.shape), list(gs.shape)))
+        if G < 1 or (gs < 1).any():
+            raise ValueError("mrt_step: every image needs at least one candidate, got group sizes %s" % gs.tolist())
+        if int(gs.sum()) != rows:
+            raise ValueError("mrt_step: the group sizes add up to %d, cand has %d rows" % (int(gs.sum()), rows))
+        if ln.size and (ln.min() < 0 or ln.max() > cand_h.shape[1]):
+            raise ValueError("mrt_step: cand_lengths must lie in [0, T = %d], got %d .. %d" % (cand_h.shape[1], int(ln.min()), int(ln.max())))
+        with np.errstate(over="ignore"):
+            c32 = c.astype(np.float32)
+        if not np.isfinite(c32).all():
+            raise ValueError("mrt_step: cost holds a NaN or an infinity (or a value beyond f32)")
+        if not (math.isfinite(float(alpha)) and float(alpha) > 0.0 and math.isfinite(float(np.float32(alpha)))):
+            raise ValueError("mrt_step: alpha must be positive and finite, got %r" % (alpha,))
+        rep = np.repeat(np.arange(G), gs)
+        if isinstance(img, torch.Tensor):
+            img = img.index_select(0, torch.from_numpy(rep).to(img.device))
+        else:
+            img = np.ascontiguousarray(np.asarray(img)[rep])
+        # ONE upload, in front of the forward (a pageable copy behind it would wait for it): cost (f32) | the group offsets (int32).  The chain batch's
+        # dead rows lie behind the last group: lxo_mrt_weights reads no cost of theirs.  One device buffer: seq | w | risk | q | logp
+        host = np.zeros(rows + G + 1, np.int32)
+        host[:rows].view(np.float32)[:] = c32
+        host[rows + 1:] = np.cumsum(gs)
+        up = self._to_dev(host, torch.int32)
+        self.forward(img, np.ascontiguousarray(cand_h, dtype=np.int32), dropout=dropout)
+        Bp = int(self.shape.B)
+        self._bind_lengths(ln.astype(np.int32))
+        buf = torch.empty(3 * Bp + 1 + Bp * int(self.shape.T), dtype=torch.float32, device=self.device)
+        seq, w, out, logp = buf[:Bp], buf[Bp:2 * Bp], buf[2 * Bp:3 * Bp + 1], buf[3 * Bp + 1:]
+        st = self._stream()
+        self._ck(self.lib.lxo_score_tokens(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), _p(logp), None, _p(seq), st), "score_tokens")
+        self._ck(self.lib.lxo_mrt_weights(_p(seq), _p(up[:rows]), _p(up[rows:]), G, Bp, ctypes.c_float(float(alpha)), _p(w), _p(out[1:]), _p(out[:1]), st),
+                 "mrt_weights")
+        self.loss(None, 1.0 / float(G), row_weights=w, _padded=True)
+        self.backward()
+        self._mrt_keep = (up, buf)
+        return out[:1], out[1:1 + rows], w[:rows]
+
+    def mrt_step(self, img, cand, cand_lengths, group_sizes, cost, lr, alpha, clip=-1.0, dropout=1.0):
+        """One minimum-risk training step (mrt_grads + the optimizer; single process): -> (risk / G = the mean expected cost BEFORE the update,
+        q f32 [rows] = each candidate's probability among its image's candidates).  The host synchronises once, for that copy at the end; the
+        chain guard and the redo of a step a chain failed in are train_step's."""
+        drop = None
+        if dropout is not None and 0.0 < float(dropout) < 1.0:
+            self.drop_step = getattr(self, "drop_step", 0) + 1
+            drop = (float(dropout), self.drop_step)
+        if self._health_ring is not None:
+            self._chain_health_poll()
+        risk, q, _ = self.mrt_grads(img, cand, cand_lengths, group_sizes, cost, alpha, dropout=drop)
+        self.optimizer_step(lr, clip, guard=True)
+        h = torch.cat([risk, q]).cpu().numpy()
+        if (self._health_ring is not None and self._chain_health_poll(wait=True) and getattr(self, "_last_dropped_seq", -1) == self._health_i
+                and not getattr(self, "_redoing", False)):
+            self._redoing = True                                   # as train_step: the step a chain failed in was dropped on the device; again, on the launch-per-step kernels
+            if drop is not None:
+                self.drop_step -= 1                                # ... under the same dropout masks
+            try:
+                return self.mrt_step(img, cand, cand_lengths, group_sizes, cost, lr, alpha, clip=clip, dropout=dropout)
+            finally:
+                self._redoing = False
+        return float(h[0]) / int(img.shape[0]), h[1:].copy()
 
     def evaluate_batch(self, img, formula, lengths):
         """(sum CE, n_words) of img2seq.py:74-75 for one batch (teacher forced)."""

@@ -8,7 +8,7 @@ uint8 [H,W,1] arrays and lists of int lists; the facade owns padding.
 import numpy as np
 
 from .base import BaseModel
-from .evaluation.text import score_files, truncate_end, write_answers
+from .evaluation.text import levenshtein, score_files, truncate_end, write_answers
 from .params import dims_from_config
 from .utils.general import Config, Progbar, minibatches
 from .utils.image import pad_batch_images
@@ -88,6 +88,9 @@ class Img2SeqModel(BaseModel):
         keep = getattr(config, "dropout", 1)
         if not keep > 0:
             raise ValueError("dropout is a keep probability and must be > 0, got {}".format(keep))
+        mrt = getattr(config, "mrt", None)
+        if mrt is not None:
+            return self._run_train_mrt(config, train_set, val_set, epoch, lr_schedule, mrt, keep)
         depth = int(getattr(config, "prefetch_depth", 2))
         # steps per pass are counted once per (dataset, batch size, world): another train() call with other arguments must not reuse the count
         key = (id(train_set), batch_size, world)
@@ -123,6 +126,66 @@ class Img2SeqModel(BaseModel):
             score = self.dist.broadcast_scalar(score)
         lr_schedule.update(score=score)
         return score
+
+    MRT_KEYS = ("n", "alpha", "temperature", "top_k", "top_p")
+
+    def _run_train_mrt(self, config, train_set, val_set, epoch, lr_schedule, mrt, keep):
+        """One epoch of minimum-risk training: the training config's optional "mrt": {"n", "alpha", "temperature", "top_k", "top_p"} key makes every
+        batch one mrt_batch instead of one cross-entropy step; the sampling seed is the step counter.  Single process; the feed is the
+        synchronous one (the candidates are built on the host from the batch's own formulas).  The epoch ends as _run_train's does."""
+        if self.dist is not None:
+            raise NotImplementedError("minimum-risk training (the training config's \"mrt\" key) runs in a single process: the data-parallel "
+                                      "mrt_step is not built -- train with one GPU, or drop the key")
+        mrt = dict(mrt) if isinstance(mrt, dict) else {k: getattr(mrt, k) for k in self.MRT_KEYS if hasattr(mrt, k)}
+        unknown = sorted(set(mrt) - set(self.MRT_KEYS))
+        if unknown:
+            raise ValueError("training config: unknown key(s) %s under \"mrt\" (known: %s)" % (unknown, list(self.MRT_KEYS)))
+        batch_size = config.batch_size
+        nbatches = (len(train_set) + batch_size - 1) // batch_size
+        prog = Progbar(nbatches)
+        for i, (img, formula) in enumerate(minibatches(train_set, batch_size)):
+            out = self.mrt_batch(img, formula, lr_schedule.lr, seed=epoch * nbatches + i, dropout=keep, **mrt)
+            prog.update(i + 1, [("risk", out["risk"]), ("lr", lr_schedule.lr)])
+            lr_schedule.update(batch_no=epoch * nbatches + i)
+        self.logger.info("- Training (minimum risk): {}".format(prog.info))
+        scores = self.evaluate(Config({"dir_answers": self._dir_output + "formulas_val/", "batch_size": config.batch_size}), val_set)
+        lr_schedule.update(score=scores["perplexity"])
+        return scores["perplexity"]
+
+    def mrt_batch(self, images, formulas, lr, n=5, alpha=0.005, temperature=1.0, top_k=0, top_p=1.0, seed=0, include_reference=True, dropout=1):
+        """One minimum-risk training step on a batch (Engine.mrt_step): the model draws n transcriptions per image (Engine.sample_decode with
+        temperature / top_k / top_p / seed); an image's candidates are its DISTINCT draws, each cut at its first END, and -- include_reference --
+        its reference formula; a candidate costs levenshtein(candidate, reference) / max(len(reference), 1) (evaluation/text.py, the edit distance
+        the model is evaluated with); the step then lowers the expected cost under softmax(alpha * log p(candidate | image)) over each image's
+        candidates.  formulas: token-id lists or space-separated token strings, as score_batch takes them.
+        -> {"risk": the mean expected cost before the update, "candidates": per image [{"text", "q": its probability among the candidates, "cost"}]}"""
+        if len(images) != len(formulas):
+            raise ValueError("mrt_batch: %d images but %d formulas" % (len(images), len(formulas)))
+        prepro = self._vocab.form_prepro
+        refs = [tuple(prepro(f)) if isinstance(f, str) else tuple(int(x) for x in f) for f in formulas]
+        id_end = self._vocab.id_end
+        img = pad_batch_images(images)
+        ids = self.engine.sample_decode(img, id_end, n=n, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                        max_iter=getattr(self._config, "max_length_formula", 150) + 1)
+        cands, sizes, costs = [], [], []
+        for b, ref in enumerate(refs):
+            mine = [ref] if include_reference else []
+            for j in range(ids.shape[2]):
+                c = tuple(int(x) for x in truncate_end(ids[b, :, j], id_end))
+                if c not in mine:
+                    mine.append(c)
+            cands += mine
+            sizes.append(len(mine))
+            costs += [levenshtein(c, ref) / float(max(len(ref), 1)) for c in mine]
+        f, ln = pad_batch_formulas([list(c) for c in cands], self._vocab.id_pad, id_end)
+        risk, q = self.engine.mrt_step(img, f, ln, np.asarray(sizes), np.asarray(costs, np.float32), lr, alpha,
+                                       clip=getattr(self, "_clip", -1), dropout=dropout)
+        tok = self._vocab.id_to_tok
+        out, at = [], 0
+        for m in sizes:
+            out.append([{"text": " ".join(tok[i] for i in cands[at + k]), "q": float(q[at + k]), "cost": float(costs[at + k])} for k in range(m)])
+            at += m
+        return {"risk": risk, "candidates": out}
 
     def _run_evaluate(self, config, test_set):
         """Reference: model/img2seq.py:198-213."""
