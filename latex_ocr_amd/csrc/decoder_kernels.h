@@ -30,7 +30,7 @@ int lxo_k_attn_bwd(int dt, const void* att_img, const void* att_exp, const void*
                    Slabs dcs, int dcoff, float* dctx_out, int lddc, const float* ctx, int ldctx, float* de, float* datth,
                    int nv, int R, int Rp, int E, int C, int nch, int rev, hipStream_t st);
 int lxo_k_datt_img(int dt, const void* att_img, const float* att_h, const float* beta, const float* de, void* dout, float* dbeta,
-                   int T, int B, int R, int Rp, int E, DetScratch det, hipStream_t st);
+                   int T, int B, int R, int Rp, int E, float* atth_exp, DetScratch det, hipStream_t st);   // atth_exp: bf16, E <= 256: [T][B][E] f32 scratch for e^{2 att_h} (written here); else unused
 int lxo_k_add_mean_grad(float* dimg, const float* dmean, int B, int R, int C, hipStream_t st);
 int lxo_k_colsum_det(const void* a, int bf16, long long lda, float* out, long long M, int N, DetScratch det, hipStream_t st);      // ordered column sums of an f32 / bf16 matrix (no atomics)
 int lxo_k_colsum(const float* a, long long lda, float* out, long long M, int N, DetScratch det, hipStream_t st);

@@ -1184,6 +1184,149 @@ __global__ __launch_bounds__(256) void datt_img_kernel(const CT* __restrict__ at
     for (int k = tid; k < E; k += 256) atomicAdd(&dbeta[k], redb[0][k] + redb[1][k] + redb[2][k] + redb[3][k]);
 }
 
+// E_a = e^{2 att_h} of every (step, sample) row (f32 -> f32), once per backward pass: what datt_img_live_kernel reads instead of att_h.
+// The clamp and the exponential are the ones of datt_img_kernel, so every value is the one its waves formed per step.
+__global__ __launch_bounds__(256) void atth_exp_kernel(const float* __restrict__ a, float* __restrict__ out, long long n4) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        float v[4];
+        load4(a + i * 4, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __builtin_amdgcn_exp2f(fminf(fmaxf(v[j] * 2.8853900817779268f, -120.f), 120.f));
+        store4(out + i * 4, v);
+    }
+}
+
+// One step of RW regions x 4 channels per lane in the E domain: w = 1 + E_x E_a, r = 1 / w, q = r - r^2 (= (1 - tau^2) / 4), acc += d q,
+// db += d r, sumd += d (region by region, the order datt_img_kernel adds them in: d_beta stays bit for bit).  d is wave-uniform; nothing is
+// tested or masked: r and q are finite (E_x E_a = inf gives r = q = 0), so d = 0 adds an exact zero.
+template <int RW>
+LXO_DEV void datt_live_step(const float (&x)[RW][4], const f32x4 a, const f32x4 (&d)[RW / 4], float (&acc)[RW][4], float (&db)[4], float& sumd) {
+    const f32x2 one = {1.f, 1.f};
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr) {
+        const float dd = d[rr >> 2][rr & 3];
+        const f32x2 d2 = {dd, dd};
+        sumd += dd;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x2 xs = {x[rr][2 * h], x[rr][2 * h + 1]}, as = {a[2 * h], a[2 * h + 1]};
+            const f32x2 w = __builtin_elementwise_fma(xs, as, one);
+            const f32x2 r = {__builtin_amdgcn_rcpf(w[0]), __builtin_amdgcn_rcpf(w[1])};
+            const f32x2 q = __builtin_elementwise_fma(-r, r, r);
+            f32x2 ac = {acc[rr][2 * h], acc[rr][2 * h + 1]}, dv = {db[2 * h], db[2 * h + 1]};
+            ac = __builtin_elementwise_fma(d2, q, ac);
+            dv = __builtin_elementwise_fma(d2, r, dv);
+            acc[rr][2 * h] = ac[0]; acc[rr][2 * h + 1] = ac[1];
+            db[2 * h] = dv[0]; db[2 * h + 1] = dv[1];
+        }
+    }
+}
+
+// The bf16, E <= 256 form of datt_img_kernel: the same element arithmetic in the same order over t, without the work the result does not need.
+//  * the step factor e^{2 att_h} comes from the table of atth_exp_kernel (one 16-byte load per lane and step, no exponential in the loop);
+//  * the workgroup stages its 4 RW columns of d_e for kDattTC steps at a time in LDS (rows >= R as zeros; the padding columns R..Rp are never read
+//    unmasked), and every wave reads its RW values of a step from there as one broadcast read;
+//  * a wave walks t < n only, n = 1 + the last step at which any of its regions has d != 0: the steps behind it add exact zeros (all regions
+//    of a wave belong to one sample, whose d_e is 0 from its length on; a dead row of a filled-up batch has n = 0);
+//  * the factor 4 of 1 - tau^2 = 4 q is applied to the finished sum (exact); sum d (for d_beta = sum d - 2 sum d r) stays a per-step add in
+//    datt_img_kernel's order, so d_att_img and, with one slot per workgroup in both kernels, d_beta are bit for bit what that kernel stores.
+constexpr int kDattTC = 128;
+// regions per wave: 4 (96 VGPRs, 5 waves per SIMD) against 8 (166 VGPRs, 3 waves per SIMD, half the row loads): 153 against 166 us at the
+// headline shape (profiles/datt_img_live_steps.txt)
+constexpr int kDattRW = 4;
+template <int RW>
+__global__ __launch_bounds__(256) void datt_img_live_kernel(const bf16_t* __restrict__ att_img, const float* __restrict__ atth_exp,
+                                                           const float* __restrict__ beta, const float* __restrict__ de,
+                                                           bf16_t* __restrict__ dout, float* __restrict__ dbeta, float* __restrict__ dbeta_part,
+                                                           int T, int B, int R, int Rp, int E) {
+    constexpr int WR = 4 * RW, Q = RW / 4, TU = 16 / RW;   // regions per workgroup, 16-byte pieces of a wave's d per step, steps per group
+    __shared__ f32x4 sd[kDattTC][WR / 4];
+    __shared__ float redb[4][256];
+    const int b = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int k0 = lane * 4;
+    const bool kon = k0 < E;
+    const int rb0 = blockIdx.x * WR, rbase = rb0 + wave * RW;
+    float x[RW][4], acc[RW][4], db[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { x[rr][j] = 0.f; acc[rr][j] = 0.f; }
+        if (rbase + rr < R && kon) load4(att_img + ((long long)b * R + rbase + rr) * E + k0, x[rr]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[rr][j] = __builtin_amdgcn_exp2f(fminf(fmaxf(x[rr][j] * 2.8853900817779268f, -120.f), 120.f));
+    }
+    float sumd = 0.f;
+    for (int tb = 0; tb < T; tb += kDattTC) {
+        const int tn = min(kDattTC, T - tb);
+        if (tb) __syncthreads();                           // the waves are done with the chunk before
+        for (int i = tid; i < tn * (WR / 4); i += 256) {
+            const int t = i / (WR / 4), c = i % (WR / 4), r = rb0 + 4 * c;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (r < R) {                                   // r % 4 == 0 and Rp % 8 == 0: the 16 bytes are inside the row; its columns >= R may hold anything
+                v = *reinterpret_cast<const f32x4*>(de + ((long long)(tb + t) * B + b) * Rp + r);
+#pragma unroll
+                for (int e = 1; e < 4; ++e) if (r + e >= R) v[e] = 0.f;
+            }
+            sd[t][c] = v;
+        }
+        __syncthreads();
+        // the end of this wave's live range (lane l looks at the steps l, l + 64, ...)
+        float pn = 0.f;
+        for (int t = lane; t < tn; t += 64) {
+#pragma unroll
+            for (int c = 0; c < Q; ++c) {
+                const f32x4 v = sd[t][wave * Q + c];
+                if (v[0] != 0.f || v[1] != 0.f || v[2] != 0.f || v[3] != 0.f) pn = (float)(t + 1);
+            }
+        }
+        const int n = __builtin_amdgcn_readfirstlane((int)wave_max(pn));
+        if (kon) {
+            const float* ap = atth_exp + ((long long)tb * B + b) * E + k0;
+            const long long pitch = (long long)B * E;
+            int t0 = 0;
+            for (; t0 + TU <= n; t0 += TU) {               // TU steps of loads in flight
+                f32x4 a[TU], d[TU][Q];
+#pragma unroll
+                for (int tt = 0; tt < TU; ++tt) {
+                    a[tt] = *reinterpret_cast<const f32x4*>(ap + (t0 + tt) * pitch);
+#pragma unroll
+                    for (int c = 0; c < Q; ++c) d[tt][c] = sd[t0 + tt][wave * Q + c];
+                }
+#pragma unroll
+                for (int tt = 0; tt < TU; ++tt) datt_live_step<RW>(x, a[tt], d[tt], acc, db, sumd);
+            }
+            for (; t0 < n; ++t0) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(ap + t0 * pitch);
+                f32x4 d[Q];
+#pragma unroll
+                for (int c = 0; c < Q; ++c) d[c] = sd[t0][wave * Q + c];
+                datt_live_step<RW>(x, a, d, acc, db, sumd);
+            }
+        }
+    }
+    if (kon) {
+        float bt[4];
+        load4(beta + k0, bt);
+#pragma unroll
+        for (int rr = 0; rr < RW; ++rr)
+            if (rbase + rr < R) {
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = (acc[rr][j] * 4.f) * bt[j];
+                store4(dout + ((long long)b * R + rbase + rr) * E + k0, o);
+            }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) redb[wave][k0 + j] = sumd - 2.f * db[j];
+    }
+    __syncthreads();
+    if (tid < E) {
+        const float s = redb[0][tid] + redb[1][tid] + redb[2][tid] + redb[3][tid];
+        if (dbeta_part) dbeta_part[((long long)blockIdx.y * gridDim.x + blockIdx.x) * E + tid] = s;      // deterministic mode: lxo_k_det_reduce adds the slots in order
+        else atomicAdd(&dbeta[tid], s);
+    }
+}
+
 // d_img[b][r][c] += dmean[b][c] / R      (backward of the region mean)
 __global__ __launch_bounds__(256) void add_mean_grad_kernel(float* __restrict__ dimg, const float* __restrict__ dmean, int B, int R, int C) {
     const long long total = (long long)B * R * C;
@@ -1688,14 +1831,19 @@ int lxo_k_det_reduce(const float* part, int nslot, long long stride, int N, floa
     DONE;
 }
 int lxo_k_datt_img(int dt, const void* att_img, const float* att_h, const float* beta, const float* de, void* dout, float* dbeta,
-                   int T, int B, int R, int Rp, int E, DetScratch det, hipStream_t st) {
-    dim3 grid(cdiv(R, 16), B);
+                   int T, int B, int R, int Rp, int E, float* atth_exp, DetScratch det, hipStream_t st) {
     if (E > 1024) return -2;
+    const bool live = dt == LXO_BF16 && E <= 256;          // bf16, E <= 256: the table of e^{2 att_h} and the live-steps kernel
+    if (live && (!atth_exp || E % 4)) return -2;
+    dim3 grid(cdiv(R, live ? 4 * kDattRW : 16), B);      // both forms: at most one workgroup per 16 regions and sample, the slots the scratch is sized for
     float* part = nullptr;
     if (det.p) { if ((size_t)grid.x * grid.y * E > det.floats) return -6; part = det.p; }
-    if (dt == LXO_BF16) {
-        if (E <= 256) hipLaunchKernelGGL((datt_img_kernel<bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)att_img, att_h, beta, de, (bf16_t*)dout, dbeta, part, T, B, R, Rp, E);
-        else hipLaunchKernelGGL((datt_img_kernel<bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)att_img, att_h, beta, de, (bf16_t*)dout, dbeta, part, T, B, R, Rp, E);
+    if (live) {
+        const long long n4 = (long long)T * B * E / 4;
+        LAUNCH(atth_exp_kernel, grid1(n4), att_h, atth_exp, n4);
+        hipLaunchKernelGGL((datt_img_live_kernel<kDattRW>), grid, dim3(256), 0, st, (const bf16_t*)att_img, atth_exp, beta, de, (bf16_t*)dout, dbeta, part, T, B, R, Rp, E);
+    } else if (dt == LXO_BF16) {
+        hipLaunchKernelGGL((datt_img_kernel<bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)att_img, att_h, beta, de, (bf16_t*)dout, dbeta, part, T, B, R, Rp, E);
     } else {
         if (E <= 256) hipLaunchKernelGGL((datt_img_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)att_img, att_h, beta, de, (float*)dout, dbeta, part, T, B, R, Rp, E);
         else hipLaunchKernelGGL((datt_img_kernel<float, 4>), grid, dim3(256), 0, st, (const float*)att_img, att_h, beta, de, (float*)dout, dbeta, part, T, B, R, Rp, E);

@@ -382,13 +382,17 @@ int lxo_impl_score_alternatives(const Plan& P, void* ws, const int* formula, con
 
 // The weight-gradient side stream of the encoder backward (model_encoder.hip: lxo_set_encoder_side_stream) also takes the decoder's
 // deferred work (round 5): behind the recurrence the critical path is d_att_img (bound by the transcendental rate) -> d_img -> conv6;
-// the initial-state gradients, the dense dW GEMMs, d_z's column sum, the embedding gradient and dW_att_img feed nothing downstream
-// but d_mean, and run beside it.  Enqueue order top to bottom, an arrow = an event recorded at its tail and waited for at its head:
+// the initial-state gradients, the dense dW GEMMs, d_z's column sum and dW_att_img feed nothing downstream but d_mean, and run
+// beside it.  The embedding gradient feeds nothing either, but follows d_img on the MAIN stream: from here to the end of the step the side
+// stream (deferred GEMMs, then the encoder's five weight gradients) is the longer one, and the main stream stops for it before it may
+// rewrite a gradient buffer (profiles/datt_img_live_steps.txt: 0.10 ms per step together with the shorter d_att_img pass, nothing alone).
+// Enqueue order top to bottom, an arrow = an event recorded at its tail and waited for at its head:
 //      main stream: recurrence                            side stream
 //      fork ----------------------------------------->    initial states: d_pre, d_mean
 //      d_att_img (masked d_img) / alpha (x) d_ctx    .--  dmean_ready
-//      wait_dmean  <---------------------------------'    dW, db of the initial states; deferred dW GEMMs; d_z column sum; embedding gradient
+//      wait_dmean  <---------------------------------'    dW, db of the initial states; deferred dW GEMMs; d_z column sum
 //      d_img's readers of d_mean
+//      embedding gradient
 //      datt_img_ready (masked form: recorded right behind d_att_img, before wait_dmean; plain form: d_att_img runs here, behind d_mean's readers)
 //             `-------------------------------------->    wait_datt_img: dW_att_img
 //      join  <----------------------------------------    (none under defer_join: lxo_impl_encoder_bwd follows on both streams and joins them once)
@@ -630,7 +634,7 @@ static int bwd_embedding(const Train& w, const int* formula, float* grads, const
 static int bwd_datt_img(const Train& w, float* grads) {
     const Plan& P = w.P;
     return lxo_k_datt_img(P.s.dtype, P.ws<void>(w.ws, W_ATT_IMG), w.atth, w.prm + P.poff[P_BETA], w.de, P.ws<void>(w.ws, W_DATTIMG), grads + P.poff[P_BETA],
-                          P.s.T, P.s.B, P.R, P.Rp, P.s.E, P.det_scratch(w.ws), w.st);
+                          P.s.T, P.s.B, P.R, P.Rp, P.s.E, P.wbytes[W_ATTH_EXP] ? P.ws<float>(w.ws, W_ATTH_EXP) : nullptr, P.det_scratch(w.ws), w.st);
 }
 // d_img = sum_t alpha_t (x) d_ctx_t  (batched over samples)  + d_mean / R + d_att_img W_att_img^T, masked form:
 // one batched GEMM contracts both products, adds the mean gradient and applies conv6's ReLU mask + bias-gradient sum
@@ -694,8 +698,8 @@ int lxo_impl_decoder_train_bwd(const Plan& P, const float* prm, const void* wp, 
     RC(s.fork());
     RC(bwd_init_states(w, grads, s, det_s));                       // deferred stream
     RC(bwd_weight_grads(w, grads, chain, s, det_s));               // deferred stream (the main one off the fused kernels)
-    RC(bwd_embedding(w, formula, grads, s));                       // deferred stream
     RC(P.dimg_masked() ? bwd_dimg_masked(w, grads, s) : bwd_dimg_plain(w, grads, s));      // main stream
+    RC(bwd_embedding(w, formula, grads, BwdStreams{st, nullptr}));                          // main stream (see above)
     RC(s.wait_datt_img());
     RC(tn(P, false, false, P.ws<void>(ws, W_IMG), P.s.C, P.ws<void>(ws, W_DATTIMG), P.s.E, grads + P.poff[P_ATT_IMG], P.s.E, P.s.B * P.R, P.s.C, P.s.E,
           s.deferred(), det_s));                                   // dW_att_img, deferred stream

@@ -60,6 +60,7 @@ enum WsId {
     W_XSYNC,            // persistent decoder chain (xdec.hip): per-XCD flag lines, tickets, error word
     W_DET,              // f32 parity mode: slots of per-workgroup partial sums for the ordered (atomic-free) reductions (DetScratch)
     W_DATTHB,           // bf16 mirror of d_att_h [T][B][E], left by the backward chain: operand of the deferred dW_att_h product
+    W_ATTH_EXP,         // bf16 mode, E <= 256: e^{2 att_h} [T][B][E] (f32), written and read by the deferred d_att_img pass (lxo_k_datt_img)
     W_COUNT
 };
 
