@@ -251,6 +251,38 @@ int lxo_ce_loss_weighted(const lxo_shape* s, void* ws, const int32_t* formula, c
  * device clamps an offset into [0, rows].  -1: a NULL w_out, seq_logp, cost or group_off, G < 0, rows < 0, alpha not finite. */
 int lxo_mrt_weights(const float* seq_logp, const float* cost, const int32_t* group_off, int G, int rows, float alpha,
                     float* w_out, float* q_out, float* risk_out, void* stream);
+/* Batched Levenshtein distance over int32 token rows on the device, shape-free.  Pair p (0 <= p < pairs) compares hypothesis row p with reference
+ * row ref_of[p] (device int32 [pairs]; NULL: row p / per_ref, per_ref >= 1), an index the device clamps into [0, G).
+ * HYPOTHESES: row p starts at element (p / hyp_block) * hyp_block_stride + (p % hyp_block) * hyp_row_stride of `hyp` and its tokens lie hyp_tok_stride
+ * elements apart, T of them.  Plain rows [pairs, T]: hyp_block 1, hyp_block_stride T, hyp_tok_stride 1.  The ids [B, max_steps, n] that
+ * lxo_sample_decode writes are read in place with hyp_block n, hyp_block_stride max_steps * n, hyp_row_stride 1, hyp_tok_stride n, T = the steps run.
+ * REFERENCES: ref int32 [G, ref_ld], 1 <= ref_ld <= LXO_EDIT_MAX_REF.
+ * A side's sequence is its first len tokens -- hyp_len [pairs] / ref_len [G], device int32, clamped into the row; NULL: T / ref_ld -- cut at the
+ * first id_end (truncate_end's rule; id_end < 0: no cut), so a reference in pad_batch_formulas' layout with its lengths is passed as it is.
+ * dist_out int32 [pairs] (NOT NULL): insertions + deletions + substitutions, exact.  cost_out f32 [pairs] (nullable): (float)dist /
+ * (float)max(reference tokens, 1), ONE correctly rounded f32 division -- for these integers bit for bit np.float32(dist / max(len, 1)).
+ * One wave per pair, integer arithmetic only: the same bytes in every run.  The hypothesis side has no limit beyond T.
+ * -1: a NULL hyp, ref or dist_out; pairs, T, G, a stride or hyp_block negative, hyp_block or per_ref < 1, G < 1 with pairs > 0; ref_ld outside
+ * 1 .. LXO_EDIT_MAX_REF. */
+#define LXO_EDIT_MAX_REF 1024
+int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                      const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
+                      int pairs, int id_end, int32_t* dist_out, float* cost_out, void* stream);
+/* The candidate rows of a minimum-risk step, built on the device from a sampled decode: three launches, no host synchronisation.
+ * ids int32 [B, max_steps, n] as lxo_sample_decode leaves them and steps = the steps it ran (0 <= steps <= max_steps, 1 <= n <= 16);
+ * ref int32 [B, Tr] with ref_len [B] in pad_batch_formulas' layout (tokens, END, PAD; length = tokens + 1), 1 <= Tr <= LXO_EDIT_MAX_REF.
+ * With R = B * (n + include_reference) and Tc = max(steps + 1, Tr), all outputs device, NOT NULL:
+ * cand int32 [R, Tc]: image g's candidates are the consecutive rows group_off[g] .. group_off[g + 1] - 1 -- its reference first (include_reference;
+ * its first ref_len tokens cut at END), then its DISTINCT draws in ascending draw index, each cut at its first END within `steps`: of equal draws
+ * (equal length, equal tokens) the first is kept, a draw equal to the reference is dropped.  A row is its tokens, then id_end, then id_pad up to Tc.
+ * cand_len int32 [R] = tokens + 1; row_image int32 [R] = g; group_off int32 [B + 1]; cost f32 [R] = lxo_edit_distance's cost_out of the row against
+ * its image's reference (the same kernel), 0 exactly for the reference's own row.
+ * Rows at and behind group_off[B] are DEAD: all id_pad, length 0, cost 0, row_image 0 -- lxo_mrt_weights gives them w = q = 0, the weighted loss
+ * leaves a length of 0 out.  cost doubles as the launches' scratch: its content is final only after the call's last kernel.
+ * -1: a NULL argument, B < 0, n outside 1 .. 16, steps outside [0, max_steps], Tr outside 1 .. LXO_EDIT_MAX_REF, id_end < 0. */
+int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
+                       int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
+                       int32_t* row_image, void* stream);
 /* Teacher-forced scoring, after lxo_decoder_train_fwd with the same shape and formula: per-token log-probs, the model's top-1 token per
  * position and per-sequence sums; reads ws region "logits", writes only the caller's outputs (device, [B, T] / [B]).
  * logp_out f32 [B, T] (NOT NULL): log_softmax(logits of step t)[formula[b][t]] for t < lengths[b], 0 after.

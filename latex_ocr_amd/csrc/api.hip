@@ -145,6 +145,32 @@ extern "C" int lxo_mrt_weights(const float* seq_logp, const float* cost, const i
     CHECK_LAUNCH(lxo_k_mrt_weights(seq_logp, cost, group_off, G, rows, alpha, w_out, q_out, risk_out, (hipStream_t)stream), "lxo_mrt_weights");
     return 0;
 }
+#include "seqcost.h"
+static_assert(LXO_EDIT_MAX_REF == kEditMaxRef, "include/lxo.h and csrc/seqcost.h disagree on the reference limit");
+extern "C" int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                                 const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of,
+                                 int per_ref, int pairs, int id_end, int32_t* dist_out, float* cost_out, void* stream) {
+    if (!hyp || !ref || !dist_out) return fail(-1, "lxo_edit_distance: null hyp, ref or dist_out");
+    if (pairs < 0 || T < 0 || G < 0 || hyp_block_stride < 0 || hyp_row_stride < 0 || hyp_tok_stride < 0)
+        return fail(-1, "lxo_edit_distance: a negative count or stride");
+    if (hyp_block < 1 || per_ref < 1 || (pairs > 0 && G < 1)) return fail(-1, "lxo_edit_distance: hyp_block < 1, per_ref < 1 or no reference row");
+    if (ref_ld < 1 || ref_ld > LXO_EDIT_MAX_REF) return fail(-1, "lxo_edit_distance: ref_ld outside 1 .. LXO_EDIT_MAX_REF (a reference longer than the kernel's column limit)");
+    const EditArgs a = {hyp, hyp_len, ref, ref_len, ref_of, nullptr, dist_out, cost_out, hyp_block_stride, hyp_row_stride, hyp_tok_stride,
+                        hyp_block, T, G, ref_ld, per_ref, pairs, id_end};
+    CHECK_LAUNCH(lxo_k_edit_distance(a, (hipStream_t)stream), "lxo_edit_distance");
+    return 0;
+}
+extern "C" int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
+                                  int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
+                                  int32_t* row_image, void* stream) {
+    if (!ids || !ref || !ref_len || !cand || !cand_len || !cost || !group_off || !row_image) return fail(-1, "lxo_mrt_candidates: a null argument");
+    if (B < 0 || n < 1 || n > 16 || max_steps < 0 || steps < 0 || steps > max_steps) return fail(-1, "lxo_mrt_candidates: B < 0, n outside 1 .. 16 or steps outside [0, max_steps]");
+    if (Tr < 1 || Tr > LXO_EDIT_MAX_REF) return fail(-1, "lxo_mrt_candidates: Tr outside 1 .. LXO_EDIT_MAX_REF");
+    if (id_end < 0) return fail(-1, "lxo_mrt_candidates: id_end < 0");
+    const CandArgs a = {ids, ref, ref_len, cand, cand_len, cost, group_off, row_image, B, max_steps, n, steps, Tr, id_end, id_pad, include_reference ? 1 : 0};
+    CHECK_LAUNCH(lxo_k_mrt_candidates(a, (hipStream_t)stream), "lxo_mrt_candidates");
+    return 0;
+}
 extern "C" int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
                                 float* logp_out, int32_t* top1_out, float* seq_out, void* stream) {
     MAKE_PLAN(P, s);

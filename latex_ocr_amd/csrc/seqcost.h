@@ -1,0 +1,31 @@
+// Launchers of the sequence-cost kernels (seqcost.hip): batched Levenshtein distance over token rows, and the candidate rows of a minimum-risk
+// step built on the device from sampled ids and references.
+#pragma once
+#include "lxo_common.h"
+
+// the widest reference a pair may have: 64 lanes x the widest strip of DP columns a lane owns (edit_kernel<16>)
+constexpr int kEditMaxRef = 1024;
+
+// Pair p: hypothesis row p against reference row ref_of[p] (NULL: p / per_ref), clamped into [0, G).  Hypothesis row p starts at element
+// (p / hyp_block) * hb_stride + (p % hyp_block) * hr_stride of `hyp` and its tokens are ht_stride apart; its sequence is the first
+// hyp_len[p] (NULL: T; clamped into [0, T]) tokens cut at the first id_end (id_end < 0: no cut).  The reference side likewise: row r of
+// ref [G][ref_ld], ref_len[r] (NULL: ref_ld), the same cut.  dist (nullable) int32 [pairs], cost (nullable) f32 [pairs] =
+// (float)dist / (float)max(reference tokens, 1), one IEEE division.  live (nullable, device int [1]): pairs p >= live[0] get dist = cost = 0
+// and read nothing.  ref_ld > kEditMaxRef: -2.
+struct EditArgs {
+    const int* hyp; const int* hyp_len; const int* ref; const int* ref_len; const int* ref_of; const int* live;
+    int* dist; float* cost;
+    long long hb_stride, hr_stride, ht_stride;
+    int hyp_block, T, G, ref_ld, per_ref, pairs, id_end;
+};
+int lxo_k_edit_distance(const EditArgs& a, hipStream_t st);
+
+// The candidate rows of a minimum-risk step (lxo_mrt_candidates): ids [B][max_steps][n] of a sampled decode that ran `steps` steps, ref [B][Tr] with
+// ref_len [B].  R = B (n + inc) rows of Tc = max(steps + 1, Tr) tokens; three launches, no host synchronisation: the draws' lengths and which of them
+// repeat (into cost_out, as scratch), the rows, their costs through lxo_k_edit_distance.
+struct CandArgs {
+    const int* ids; const int* ref; const int* ref_len;
+    int* cand; int* cand_len; float* cost; int* group_off; int* row_image;
+    int B, max_steps, n, steps, Tr, id_end, id_pad, inc;
+};
+int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st);

@@ -1,0 +1,198 @@
+// Sequence costs on the device: the batched Levenshtein distance (lxo_edit_distance) and the candidate rows of a minimum-risk step built from
+// sampled ids (lxo_mrt_candidates).  Integer arithmetic throughout: exact, and the same in every order.
+#include "seqcost.h"
+
+namespace {
+
+// A side's sequence: the first `len` tokens of a strided row, cut at the first id_end (truncate_end's rule; id_end < 0: no cut).  The whole
+// wave calls it; every lane returns the same length.
+LXO_DEV int cut_len(const int* p, long long stride, int len, int id_end, int lane) {
+    if (id_end < 0) return len;
+    for (int t0 = 0; t0 < len; t0 += 64) {
+        const int t = t0 + lane;
+        const unsigned long long hit = __ballot(t < len && p[t * stride] == id_end);
+        if (hit) return t0 + (int)__builtin_ctzll(hit);
+    }
+    return len;
+}
+
+// ---- Levenshtein distance, one wave per pair ----
+// The DP table has a row per hypothesis token and a column per reference token; lane l owns the CPL columns l CPL + 1 .. l CPL + CPL (column 0 is
+// the row number).  With t[j] = min(prev[j] + 1, prev[j - 1] + (x != b[j])) -- what a cell gets from the row above -- and t[0] = i, the horizontal
+// dependency cur[j] = min(t[j], cur[j - 1] + 1) unrolls to cur[j] = j + min_{k <= j} (t[k] - k): a min-plus prefix.  So a row costs one neighbour
+// exchange (prev of the column left of the strip), a serial prefix-min over the strip and one exclusive prefix-min scan over the 64 lanes.
+// Columns beyond the reference's n tokens compute values nobody reads (a cell depends on columns to its left only).
+// m hypothesis tokens at hp (stride hts), n <= 64 CPL reference tokens at rp -> the distance, in every lane.
+template <int CPL>
+LXO_DEV int edit_wave(const int* hp, long long hts, int m, const int* rp, int n, int lane) {
+    int b[CPL], prev[CPL];
+#pragma unroll
+    for (int e = 0; e < CPL; ++e) {
+        const int j = lane * CPL + e;
+        b[e] = j < n ? rp[j] : -1;
+        prev[e] = j + 1;
+    }
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const int xi = hp[(i0 + lane < m ? i0 + lane : i0) * hts];      // 64 hypothesis tokens per load, handed out lane by lane below
+        const int cnt = min(64, m - i0);
+        for (int k = 0; k < cnt; ++k) {
+            const int x = __shfl(xi, k), i = i0 + k + 1;
+            int left = __shfl_up(prev[CPL - 1], 1);
+            if (lane == 0) left = i - 1;
+            int s[CPL], run = 0x3fffffff;
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) {
+                const int diag = e ? prev[e - 1] : left;
+                const int t = min(prev[e] + 1, diag + (x != b[e] ? 1 : 0));
+                run = min(run, t - (lane * CPL + e + 1));
+                s[e] = run;
+            }
+            int v = lane == 0 ? min(run, i) : run;                       // t[0] - 0 = i joins lane 0's strip
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(v, d);
+                if (lane >= d) v = min(v, o);
+            }
+            int ex = __shfl_up(v, 1);
+            if (lane == 0) ex = i;
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) prev[e] = lane * CPL + e + 1 + min(s[e], ex);
+        }
+    }
+    if (n == 0) return m;
+    int r = 0;
+#pragma unroll
+    for (int e = 0; e < CPL; ++e) if (e == (n - 1) % CPL) r = prev[e];
+    return __shfl(r, (n - 1) / CPL);
+}
+
+template <int CPL>
+__global__ __launch_bounds__(256) void edit_kernel(EditArgs a) {
+    const int lane = threadIdx.x & 63, p = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= a.pairs) return;
+    if (a.live && p >= a.live[0]) {
+        if (lane == 0) { if (a.dist) a.dist[p] = 0; if (a.cost) a.cost[p] = 0.f; }
+        return;
+    }
+    // what the device holds is read defensively: a reference index is clamped into [0, G), a length into its row
+    const int r = min(max(a.ref_of ? a.ref_of[p] : p / a.per_ref, 0), a.G - 1);
+    const int* hp = a.hyp + (long long)(p / a.hyp_block) * a.hb_stride + (long long)(p % a.hyp_block) * a.hr_stride;
+    const int* rp = a.ref + (long long)r * a.ref_ld;
+    const int m = cut_len(hp, a.ht_stride, a.hyp_len ? min(max(a.hyp_len[p], 0), a.T) : a.T, a.id_end, lane);
+    const int n = cut_len(rp, 1, min(a.ref_len ? min(max(a.ref_len[r], 0), a.ref_ld) : a.ref_ld, 64 * CPL), a.id_end, lane);
+    const int d = edit_wave<CPL>(hp, a.ht_stride, m, rp, n, lane);
+    if (lane == 0) {
+        if (a.dist) a.dist[p] = d;
+        if (a.cost) a.cost[p] = (float)d / (float)max(n, 1);
+    }
+}
+
+// ---- candidate rows of a minimum-risk step ----
+// Launch 1, one workgroup per image: the length of each draw and of the reference (cut at END), and which draws repeat the reference or an earlier
+// draw (equal length, equal tokens).  slot[g (n + inc) + k], k = the reference (inc) then the draws: the length of a row that is kept, -1 for a
+// draw that is dropped.  The slots live in cost_out until launch 3 overwrites them.
+LXO_DEV const int* cand_src(const CandArgs& a, int g, int k, long long& stride) {      // k = -1: the reference
+    if (k < 0) { stride = 1; return a.ref + (long long)g * a.Tr; }
+    stride = a.n;
+    return a.ids + (long long)g * a.max_steps * a.n + k;
+}
+LXO_DEV int cand_Tc(const CandArgs& a) { return max(a.steps + 1, a.Tr); }
+
+__global__ __launch_bounds__(256) void cand_analyse_kernel(CandArgs a, int* slot) {
+    __shared__ int len[17], dup[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = blockIdx.x;
+    if (threadIdx.x < 16) dup[threadIdx.x] = 0;
+    for (int j = wave; j < a.n; j += 4) {
+        long long st;
+        const int* p = cand_src(a, g, j, st);
+        const int L = cut_len(p, st, a.steps, a.id_end, lane);
+        if (lane == 0) len[j + 1] = L;
+    }
+    if (wave == 0 && a.inc) {
+        // (a reference without END inside its length would not fit its row with the END behind it: cut to Tc - 1 tokens)
+        const int L = min(cut_len(a.ref + (long long)g * a.Tr, 1, min(max(a.ref_len[g], 0), a.Tr), a.id_end, lane), cand_Tc(a) - 1);
+        if (lane == 0) len[0] = L;
+    }
+    __syncthreads();
+    int q = 0;
+    for (int j = 0; j < a.n; ++j)
+        for (int i = a.inc ? -1 : 0; i < j; ++i, ++q) {
+            if ((q & 3) != wave || len[i + 1] != len[j + 1]) continue;
+            long long si, sj;
+            const int* pi = cand_src(a, g, i, si);
+            const int* pj = cand_src(a, g, j, sj);
+            const int L = len[j + 1];
+            bool same = true;
+            for (int t0 = 0; t0 < L && same; t0 += 64) {
+                const int t = t0 + lane;
+                same = __ballot(t < L && pi[t * si] != pj[t * sj]) == 0ull;
+            }
+            if (same && lane == 0) dup[j] = 1;
+        }
+    __syncthreads();
+    const int k = threadIdx.x, per = a.n + a.inc;
+    if (k < per) slot[(long long)g * per + k] = (a.inc && k == 0) ? len[0] : (dup[k - a.inc] ? -1 : len[k - a.inc + 1]);
+}
+
+// Launch 2, one workgroup per image: its first row = the rows kept by the images in front of it (every workgroup counts for itself: B (n + inc)
+// slots), then its rows -- tokens, END, PAD up to Tc -- with their lengths (tokens + 1) and image, group_off, and its share of the dead rows
+// behind the last group (all PAD, length 0, image 0; their cost is launch 3's)
+__global__ __launch_bounds__(256) void cand_emit_kernel(CandArgs a, const int* slot) {
+    __shared__ int red[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = blockIdx.x, per = a.n + a.inc, Tc = cand_Tc(a);
+    int before = 0, all = 0;
+    for (int i = threadIdx.x; i < a.B * per; i += 256) {
+        const int kept = slot[i] >= 0 ? 1 : 0;
+        all += kept;
+        if (i < g * per) before += kept;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o); all += __shfl_xor(all, o); }
+    if (lane == 0) { red[0][wave] = before; red[1][wave] = all; }
+    __syncthreads();
+    before = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    all = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    int r = before;
+    for (int k = 0; k < per; ++k) {
+        const int L = slot[(long long)g * per + k];
+        if (L < 0) continue;
+        long long st;
+        const int* p = cand_src(a, g, k - a.inc, st);
+        for (int t = threadIdx.x; t < Tc; t += 256) a.cand[(long long)r * Tc + t] = t < L ? p[t * st] : (t == L ? a.id_end : a.id_pad);
+        if (threadIdx.x == 0) { a.cand_len[r] = L + 1; a.row_image[r] = g; }
+        ++r;
+    }
+    if (threadIdx.x == 0) { a.group_off[g + 1] = r; if (g == 0) a.group_off[0] = 0; }
+    for (int d = all + g; d < a.B * per; d += a.B) {
+        for (int t = threadIdx.x; t < Tc; t += 256) a.cand[(long long)d * Tc + t] = a.id_pad;
+        if (threadIdx.x == 0) { a.cand_len[d] = 0; a.row_image[d] = 0; }
+    }
+}
+
+}  // namespace
+
+#define LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, __VA_ARGS__)
+
+int lxo_k_edit_distance(const EditArgs& a, hipStream_t st) {
+    if (a.ref_ld > kEditMaxRef) return -2;
+    if (a.pairs == 0) return 0;
+    const int grid = cdiv(a.pairs, 4);
+    if (a.ref_ld <= 64) LAUNCH(edit_kernel<1>, grid, a);
+    else if (a.ref_ld <= 128) LAUNCH(edit_kernel<2>, grid, a);
+    else if (a.ref_ld <= 256) LAUNCH(edit_kernel<4>, grid, a);
+    else if (a.ref_ld <= 512) LAUNCH(edit_kernel<8>, grid, a);
+    else LAUNCH(edit_kernel<16>, grid, a);
+    return (int)hipGetLastError();
+}
+
+int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st) {
+    if (a.Tr > kEditMaxRef) return -2;
+    if (a.B == 0) return (int)hipMemsetAsync(a.group_off, 0, sizeof(int), st);
+    int* slot = reinterpret_cast<int*>(a.cost);
+    LAUNCH(cand_analyse_kernel, a.B, a, slot);
+    LAUNCH(cand_emit_kernel, a.B, a, slot);
+    const int Tc = a.steps + 1 > a.Tr ? a.steps + 1 : a.Tr;
+    EditArgs e = {a.cand, nullptr, a.ref, a.ref_len, a.row_image, a.group_off + a.B, nullptr, a.cost, Tc, 0, 1, 1, Tc, a.B, a.Tr, 1,
+                  a.B * (a.n + a.inc), a.id_end};
+    return lxo_k_edit_distance(e, st);
+}

@@ -690,18 +690,25 @@ class Engine(object):
         host[:rows].view(np.float32)[:] = c32
         host[rows + 1:] = np.cumsum(gs)
         up = self._to_dev(host, torch.int32)
-        self.forward(img, np.ascontiguousarray(cand_h, dtype=np.int32), dropout=dropout)
+        return self._mrt_grads_dev(img, np.ascontiguousarray(cand_h, dtype=np.int32), ln.astype(np.int32), up[:rows].view(torch.float32), up[rows:], G, rows,
+                                   alpha, dropout, keep=up)
+
+    def _mrt_grads_dev(self, img, cand, cand_lengths, cost, group_off, G, rows, alpha, dropout, keep=None):
+        """mrt_grads behind its checks: img [rows, H, W] (one image per candidate row), cand [rows, T] and cand_lengths [rows] as host arrays or device
+        tensors, cost f32 [rows] and group_off int32 [G + 1] on the device.  Rows at and behind group_off[G] (and the chain batch's own dead rows) carry
+        length 0 and get w = q = 0."""
+        self.forward(img, cand, dropout=dropout)
         Bp = int(self.shape.B)
-        self._bind_lengths(ln.astype(np.int32))
+        self._bind_lengths(cand_lengths)
         buf = torch.empty(3 * Bp + 1 + Bp * int(self.shape.T), dtype=torch.float32, device=self.device)
         seq, w, out, logp = buf[:Bp], buf[Bp:2 * Bp], buf[2 * Bp:3 * Bp + 1], buf[3 * Bp + 1:]
         st = self._stream()
         self._ck(self.lib.lxo_score_tokens(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), _p(logp), None, _p(seq), st), "score_tokens")
-        self._ck(self.lib.lxo_mrt_weights(_p(seq), _p(up[:rows]), _p(up[rows:]), G, Bp, ctypes.c_float(float(alpha)), _p(w), _p(out[1:]), _p(out[:1]), st),
+        self._ck(self.lib.lxo_mrt_weights(_p(seq), _p(cost), _p(group_off), G, Bp, ctypes.c_float(float(alpha)), _p(w), _p(out[1:]), _p(out[:1]), st),
                  "mrt_weights")
         self.loss(None, 1.0 / float(G), row_weights=w, _padded=True)
         self.backward()
-        self._mrt_keep = (up, buf)
+        self._mrt_keep = (keep, cost, group_off, buf)
         return out[:1], out[1:1 + rows], w[:rows]
 
     def mrt_step(self, img, cand, cand_lengths, group_sizes, cost, lr, alpha, clip=-1.0, dropout=1.0):
@@ -727,6 +734,116 @@ class Engine(object):
             finally:
                 self._redoing = False
         return float(h[0]) / int(img.shape[0]), h[1:].copy()
+
+    def mrt_sample_step(self, img, ref, ref_lengths, id_end, id_pad, lr, alpha, n=5, temperature=1.0, top_k=0, top_p=1.0, seed=0, include_reference=True,
+                        max_iter=151, clip=-1.0, dropout=1.0):
+        """One minimum-risk training step from pixels, the candidates never leaving the device: the sampled decode (sample_decode's draws at the same
+        arguments, its ids kept on the device), lxo_mrt_candidates (each image's reference -- include_reference -- and its distinct draws as padded rows
+        with their edit-distance costs, as Img2SeqModel.mrt_batch builds them on the host, in the same order), ONE index_select of the images by the
+        rows' image, then mrt_step's sequence on those R = B (n + include_reference) rows -- forward, lxo_score_tokens, lxo_mrt_weights, the weighted
+        loss with row_weights = w and normaliser B, backward, the guarded optimizer step -- with lengths, group offsets and costs read from the device.
+        The rows the duplicates leave empty are dead: length 0, w = q = 0.
+        ref int32 [B, Tr] and ref_lengths [B] in pad_batch_formulas' layout (host arrays or device tensors).
+        -> (risk / B = the mean expected cost BEFORE the update, info): info holds host arrays, dead rows stripped -- "cand" int32 [rows, Tc],
+        "cand_lengths" [rows], "group_sizes" [B], "cost" f32 [rows], "q" f32 [rows].
+        The host sees the decode loop's step count (as in every decode) and makes one copy at the end; because of that count the call cannot be
+        captured into a graph.  A step a chain failed in is redone on the same device candidates, not on a fresh draw.  Single process: there is no
+        data-parallel form."""
+        B = int(img.shape[0])
+        ref_d, rl_d = self._to_dev(ref, torch.int32), self._to_dev(ref_lengths, torch.int32).reshape(-1)
+        if ref_d.dim() != 2 or int(ref_d.shape[0]) != B or int(rl_d.shape[0]) != B or int(ref_d.shape[1]) < 1:
+            raise ValueError("mrt_sample_step: ref must be [B, Tr >= 1] and ref_lengths [B] for B = %d images, got %s and %s"
+                             % (B, list(ref_d.shape), list(rl_d.shape)))
+        Tr = int(ref_d.shape[1])
+        if Tr > _abi.LXO_EDIT_MAX_REF:
+            raise ValueError("mrt_sample_step: references of %d tokens exceed the edit-distance kernel's limit of %d" % (Tr, _abi.LXO_EDIT_MAX_REF))
+        if not (0 <= int(id_end) < self.n_tok and 0 <= int(id_pad) < self.n_tok):
+            raise ValueError("mrt_sample_step: id_end = %d and id_pad = %d must lie in [0, %d)" % (int(id_end), int(id_pad), self.n_tok))
+        if not (math.isfinite(float(alpha)) and float(alpha) > 0.0 and math.isfinite(float(np.float32(alpha)))):
+            raise ValueError("mrt_sample_step: alpha must be positive and finite, got %r" % (alpha,))
+        drop = None
+        if dropout is not None and 0.0 < float(dropout) < 1.0:
+            self.drop_step = getattr(self, "drop_step", 0) + 1
+            drop = (float(dropout), self.drop_step)
+        if self._health_ring is not None:
+            self._chain_health_poll()
+        img_d = self._to_dev(img, torch.uint8)
+        ids, _, _, _, steps, _ = self._sample_device(img_d, id_end, n, temperature, top_k, top_p, seed, max_iter)
+        n, inc = int(n), 1 if include_reference else 0
+        R, Tc = B * (n + inc), max(steps + 1, Tr)
+        # ONE device buffer for what the candidate kernels write: cand [R, Tc] | cand_len [R] | cost f32 [R] | group_off [B + 1] | row_image [R]
+        cbuf = torch.empty(R * Tc + 3 * R + B + 1, dtype=torch.int32, device=self.device)
+        o = np.cumsum([0, R * Tc, R, R, B + 1, R])
+        cand, cand_len, cost, group_off, row_image = [cbuf[o[i]:o[i + 1]] for i in range(5)]
+        self._ck(self.lib.lxo_mrt_candidates(_p(ids), B, int(ids.shape[1]), n, steps, _p(ref_d), Tr, _p(rl_d), int(id_end), int(id_pad), inc,
+                                             _p(cand), _p(cand_len), _p(cost.view(torch.float32)), _p(group_off), _p(row_image), self._stream()),
+                 "mrt_candidates")
+        rows_img = img_d.index_select(0, row_image.to(torch.int64))
+        redone = False
+        while True:
+            risk, q, _ = self._mrt_grads_dev(rows_img, cand.view(R, Tc), cand_len, cost.view(torch.float32), group_off, B, R, alpha, drop, keep=cbuf)
+            self.optimizer_step(lr, clip, guard=True)
+            h = torch.cat([cbuf, risk.view(torch.int32), q.view(torch.int32)]).cpu().numpy()
+            if (self._health_ring is not None and self._chain_health_poll(wait=True) and getattr(self, "_last_dropped_seq", -1) == self._health_i
+                    and not redone):
+                redone = True                                      # as mrt_step: dropped on the device; again on the launch-per-step kernels, same candidates and masks
+                continue
+            break
+        off = h[o[3]:o[4]]
+        live = int(off[B])
+        info = {"cand": h[:R * Tc].reshape(R, Tc)[:live].copy(), "cand_lengths": h[o[1]:o[2]][:live].copy(), "group_sizes": np.diff(off).astype(np.int32),
+                "cost": h[o[2]:o[3]].view(np.float32)[:live].copy(), "q": h[o[5] + 1:].view(np.float32)[:live].copy()}
+        return float(h[o[5]:o[5] + 1].view(np.float32)[0]) / B, info
+
+    def edit_distance(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None, return_cost=False):
+        """Batched Levenshtein distance on the device (lxo_edit_distance): hyp [pairs, T] and ref [G, Tr] token ids, host arrays or device tensors.
+        Pair p compares hyp[p] with ref[ref_index[p]]; without ref_index, pairs must be a multiple of G and hypothesis p belongs to reference
+        p // (pairs // G) (G = pairs: row by row).  A side's sequence is its first *_lengths tokens (None: the whole row) cut at the first id_end
+        (None: no cut) -- pad_batch_formulas' rows and lengths are taken as they are.  -> int32 [pairs], with return_cost also f32 [pairs] =
+        distance / max(reference tokens, 1), bit for bit np.float32 of the host's quotient.  A ValueError before any launch for a shape mismatch, a
+        reference row longer than the kernel's limit (LXO_EDIT_MAX_REF), or an index outside [0, G) in a host ref_index."""
+        h, r = self._to_dev(hyp, torch.int32), self._to_dev(ref, torch.int32)
+        if h.dim() != 2 or r.dim() != 2:
+            raise ValueError("edit_distance: hyp must be [pairs, T] and ref [G, Tr], got %s and %s" % (list(h.shape), list(r.shape)))
+        pairs, T, G, Tr = int(h.shape[0]), int(h.shape[1]), int(r.shape[0]), int(r.shape[1])
+        if Tr > _abi.LXO_EDIT_MAX_REF:
+            raise ValueError("edit_distance: reference rows of %d tokens exceed the kernel's limit of %d (the hypothesis side has none)" % (Tr, _abi.LXO_EDIT_MAX_REF))
+        if pairs > 0 and G < 1:
+            raise ValueError("edit_distance: %d hypotheses but no reference" % pairs)
+        hl = rl = ri = None
+        if hyp_lengths is not None:
+            hl = self._to_dev(hyp_lengths, torch.int32)
+            if tuple(hl.shape) != (pairs,):
+                raise ValueError("edit_distance: hyp_lengths must be [pairs = %d], got %s" % (pairs, list(hl.shape)))
+        if ref_lengths is not None:
+            rl = self._to_dev(ref_lengths, torch.int32)
+            if tuple(rl.shape) != (G,):
+                raise ValueError("edit_distance: ref_lengths must be [G = %d], got %s" % (G, list(rl.shape)))
+        per_ref = 1
+        if ref_index is not None:
+            if not isinstance(ref_index, torch.Tensor):
+                a = np.asarray(ref_index)
+                if a.shape == (pairs,) and a.size and (a.min() < 0 or a.max() >= G):
+                    raise ValueError("edit_distance: ref_index must lie in [0, G = %d), got %d .. %d" % (G, int(a.min()), int(a.max())))
+            ri = self._to_dev(ref_index, torch.int32)
+            if tuple(ri.shape) != (pairs,):
+                raise ValueError("edit_distance: ref_index must be [pairs = %d], got %s" % (pairs, list(ri.shape)))
+        elif pairs:
+            if pairs % G:
+                raise ValueError("edit_distance: without ref_index the %d hypotheses must be a multiple of the %d references" % (pairs, G))
+            per_ref = pairs // G
+        if pairs == 0:
+            return (np.zeros(0, np.int32), np.zeros(0, np.float32)) if return_cost else np.zeros(0, np.int32)
+        dist = torch.empty(pairs, dtype=torch.int32, device=self.device)
+        cost = torch.empty(pairs, dtype=torch.float32, device=self.device) if return_cost else None
+        if T == 0:                                                 # hypotheses without a column: a row to point at, none of it read
+            h = torch.zeros(pairs, 1, dtype=torch.int32, device=self.device)
+        if Tr == 0:                                                # references without a column: every distance is the hypothesis' length
+            r, Tr = torch.zeros(max(G, 1), 1, dtype=torch.int32, device=self.device), 1
+            rl = torch.zeros(max(G, 1), dtype=torch.int32, device=self.device)
+        self._ck(self.lib.lxo_edit_distance(_p(h), 1, T, 0, 1, T, _p(hl), _p(r), G, Tr, _p(rl), _p(ri), per_ref, pairs, -1 if id_end is None else int(id_end),
+                                            _p(dist), _p(cost), self._stream()), "edit_distance")
+        return (dist.cpu().numpy(), cost.cpu().numpy()) if return_cost else dist.cpu().numpy()
 
     def evaluate_batch(self, img, formula, lengths):
         """(sum CE, n_words) of img2seq.py:74-75 for one batch (teacher forced)."""
@@ -1158,6 +1275,21 @@ class Engine(object):
         sequence log-prob of a draw is the sum through its first END.  return_attention: alpha f32 [B, T', n, H', W'].
         prefix / prefix_lengths / allowed: per image, as in greedy_decode.  A ValueError before any launch for what greedy_decode refuses, n outside
         1 .. min(16, V), temperature < 0 or not finite, top_k < 0, top_p outside (0, 1]."""
+        ids, logp, logq, alpha, steps, geo = self._sample_device(img, id_end, n, temperature, top_k, top_p, seed, max_iter, return_scores, return_attention,
+                                                                 prefix, prefix_lengths, allowed)
+        B, n, R, Hp, Wp = geo
+        out = [ids[:, :steps]]
+        if return_attention:
+            out.append(alpha[:steps, :, :R].reshape(steps, B, n, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
+        if return_scores:
+            out += [logp[:, :steps], logq[:, :steps]]
+        out = tuple(a.cpu().numpy() for a in out)
+        return out if len(out) > 1 else out[0]
+
+    def _sample_device(self, img, id_end, n, temperature, top_k, top_p, seed, max_iter, return_scores=False, return_attention=False,
+                       prefix=None, prefix_lengths=None, allowed=None):
+        """sample_decode's checks and its lxo_sample_decode call, the outputs left on the device: -> (ids int32 [B, max_steps, n], logp, logq, alpha
+        (None where not asked for), the steps the loop ran -- the one number the host learns -- and (B, n, R, H', W') for the attention maps)"""
         so = self._sample_opts(n, temperature, top_k, top_p, seed)
         n = int(n)
         if n > self.n_tok:                                             # the decode calls' shape limit (rows per image <= V); the select step alone has none
@@ -1176,13 +1308,7 @@ class Engine(object):
         pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
         steps = self._run_decode((self.lib.lxo_sample_decode, "sample_decode",
                                   (ctypes.byref(so), _p(alw[0]), alw[1]) + pa + (_p(ids), _p(logp), _p(logq), _p(alpha))), id_end, max_iter)
-        out = [ids[:, :steps]]
-        if return_attention:
-            out.append(alpha[:steps, :, :R].reshape(steps, B, n, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
-        if return_scores:
-            out += [logp[:, :steps], logq[:, :steps]]
-        out = tuple(a.cpu().numpy() for a in out)
-        return out if len(out) > 1 else out[0]
+        return ids, logp, logq, alpha, steps, (B, n, R, Hp, Wp)
 
     def sample_tokens(self, logits, n=1, time=0, temperature=1.0, top_k=0, top_p=1.0, seed=0, allowed=None):
         """The sampled select step alone (lxo_sample_tokens) on logits [rows, V] the caller holds (host array or tensor): row r is draw r % n of

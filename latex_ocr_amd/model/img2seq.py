@@ -127,12 +127,13 @@ class Img2SeqModel(BaseModel):
         lr_schedule.update(score=score)
         return score
 
-    MRT_KEYS = ("n", "alpha", "temperature", "top_k", "top_p")
+    MRT_KEYS = ("n", "alpha", "temperature", "top_k", "top_p", "on_device")
 
     def _run_train_mrt(self, config, train_set, val_set, epoch, lr_schedule, mrt, keep):
-        """One epoch of minimum-risk training: the training config's optional "mrt": {"n", "alpha", "temperature", "top_k", "top_p"} key makes every
-        batch one mrt_batch instead of one cross-entropy step; the sampling seed is the step counter.  Single process; the feed is the
-        synchronous one (the candidates are built on the host from the batch's own formulas).  The epoch ends as _run_train's does."""
+        """One epoch of minimum-risk training: the training config's optional "mrt": {"n", "alpha", "temperature", "top_k", "top_p", "on_device"} key
+        makes every batch one mrt_batch instead of one cross-entropy step; the sampling seed is the step counter.  Single process; the feed is the
+        synchronous one (the candidates are built from the batch's own formulas: on the host, or with "on_device": true by Engine.mrt_sample_step).
+        The epoch ends as _run_train's does."""
         if self.dist is not None:
             raise NotImplementedError("minimum-risk training (the training config's \"mrt\" key) runs in a single process: the data-parallel "
                                       "mrt_step is not built -- train with one GPU, or drop the key")
@@ -152,12 +153,15 @@ class Img2SeqModel(BaseModel):
         lr_schedule.update(score=scores["perplexity"])
         return scores["perplexity"]
 
-    def mrt_batch(self, images, formulas, lr, n=5, alpha=0.005, temperature=1.0, top_k=0, top_p=1.0, seed=0, include_reference=True, dropout=1):
+    def mrt_batch(self, images, formulas, lr, n=5, alpha=0.005, temperature=1.0, top_k=0, top_p=1.0, seed=0, include_reference=True, dropout=1,
+                  on_device=False):
         """One minimum-risk training step on a batch (Engine.mrt_step): the model draws n transcriptions per image (Engine.sample_decode with
         temperature / top_k / top_p / seed); an image's candidates are its DISTINCT draws, each cut at its first END, and -- include_reference --
         its reference formula; a candidate costs levenshtein(candidate, reference) / max(len(reference), 1) (evaluation/text.py, the edit distance
         the model is evaluated with); the step then lowers the expected cost under softmax(alpha * log p(candidate | image)) over each image's
         candidates.  formulas: token-id lists or space-separated token strings, as score_batch takes them.
+        on_device: the same candidates, costs and step through Engine.mrt_sample_step -- the draws are cut, compared and costed by device kernels and
+        never visit the host; the default builds them here, as ever.
         -> {"risk": the mean expected cost before the update, "candidates": per image [{"text", "q": its probability among the candidates, "cost"}]}"""
         if len(images) != len(formulas):
             raise ValueError("mrt_batch: %d images but %d formulas" % (len(images), len(formulas)))
@@ -165,6 +169,19 @@ class Img2SeqModel(BaseModel):
         refs = [tuple(prepro(f)) if isinstance(f, str) else tuple(int(x) for x in f) for f in formulas]
         id_end = self._vocab.id_end
         img = pad_batch_images(images)
+        tok = self._vocab.id_to_tok
+        if on_device:
+            f, ln = pad_batch_formulas([list(r) for r in refs], self._vocab.id_pad, id_end)
+            risk, info = self.engine.mrt_sample_step(img, f, ln, id_end, self._vocab.id_pad, lr, alpha, n=n, temperature=temperature, top_k=top_k, top_p=top_p,
+                                                     seed=seed, include_reference=include_reference,
+                                                     max_iter=getattr(self._config, "max_length_formula", 150) + 1, clip=getattr(self, "_clip", -1),
+                                                     dropout=dropout)
+            out, at = [], 0
+            for m in info["group_sizes"]:
+                out.append([{"text": " ".join(tok[int(i)] for i in info["cand"][r, :info["cand_lengths"][r] - 1]), "q": float(info["q"][r]),
+                             "cost": float(info["cost"][r])} for r in range(at, at + int(m))])
+                at += int(m)
+            return {"risk": risk, "candidates": out}
         ids = self.engine.sample_decode(img, id_end, n=n, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                         max_iter=getattr(self._config, "max_length_formula", 150) + 1)
         cands, sizes, costs = [], [], []
@@ -180,7 +197,6 @@ class Img2SeqModel(BaseModel):
         f, ln = pad_batch_formulas([list(c) for c in cands], self._vocab.id_pad, id_end)
         risk, q = self.engine.mrt_step(img, f, ln, np.asarray(sizes), np.asarray(costs, np.float32), lr, alpha,
                                        clip=getattr(self, "_clip", -1), dropout=dropout)
-        tok = self._vocab.id_to_tok
         out, at = [], 0
         for m in sizes:
             out.append([{"text": " ".join(tok[i] for i in cands[at + k]), "q": float(q[at + k]), "cost": float(costs[at + k])} for k in range(m)])
