@@ -13,7 +13,7 @@
 #include "api_util.h"
 #include "decoder_kernels.h"      // lxo_k_det_reduce
 #include "lxo_debug.h"
-#include <stdlib.h>
+#include "switches.h"
 
 namespace {
 
@@ -751,16 +751,14 @@ int lxo_launch_conv_igemm(const GemmNT& p0, hipStream_t s) {
     GemmNT p = p0;
     p.dbg = g_conv_dbg;
 #ifdef LXO_DIAG      // diagnostic builds only (make EXTRA=-DLXO_DIAG=1): LXO_CONV_DIAG removes parts of the kernel's work -- results are WRONG by design
-    { static int diag = -1; if (diag < 0) { const char* e = getenv("LXO_CONV_DIAG"); diag = e ? atoi(e) : 0; } p.diag = diag; }
+    p.diag = lxo_conv_diag();
 #else
     p.diag = 0;
 #endif
     if (!p.conv || p.Cin % 64 || p.K % 64) return -2;
-    static int use_2wg = -1;
-    if (use_2wg < 0) { const char* e = getenv("LXO_CONV_2WG"); use_2wg = (e && e[0] == '0') ? 0 : 1; }
     // the halo kernel addresses its input through 32-bit buffer offsets (2^31 = its out-of-range marker): tensors below 2 GB only
     const bool in_32bit = (long long)(p.M / (p.Ho * p.Wo)) * p.H * p.W * p.Cin * 2 < (1LL << 31);
-    if (use_2wg && in_32bit && (p.N % 64) == 0 && p.act != 2 && p.alpha == 1.f) {
+    if (lxo_switch(SW_CONV_2WG) && in_32bit && (p.N % 64) == 0 && p.act != 2 && p.alpha == 1.f) {
         constexpr int LDS4 = WLDS, LDS2 = WLDS;                                                    // 77824: the patch + four waves' two private weight stages
         if (attr_needed(0)) {
             HIPRC(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo2wg_kernel<4, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS4));
@@ -791,9 +789,7 @@ int lxo_launch_conv_igemm(const GemmNT& p0, hipStream_t s) {
         // A launch of 128-channel tiles that cannot give every CU a workgroup (the reference's own batches: 3 .. 20 images of 50 x 120 .. 100 x 360) runs on
         // 64-channel tiles instead: twice the workgroups, half the matrix work per workgroup -- a tile's time is its K loop (Cin / 32 slices x 9 taps x
         // 2 RI MFMAs per wave, ~35 us at Cin = 512 whatever the grid), so the layer takes about half as long.  Same arithmetic per output element.
-        static int small_thr = -1;
-        if (small_thr < 0) { const char* e = getenv("LXO_CONV_SMALL"); small_thr = e ? atoi(e) : 256; }
-        if (p.N % 128 == 0 && (int)g4.x >= small_thr) {
+        if (p.N % 128 == 0 && (int)g4.x >= lxo_switch(SW_CONV_SMALL)) {      // LXO_CONV_SMALL=0: 128-channel tiles always
             if (epi == 0) hipLaunchKernelGGL((conv_halo2wg_kernel<4, 0>), g4, dim3(WTHR), LDS4, s, p, p.N / 128, tiles_x, tiles_y);
             else if (epi == 1) hipLaunchKernelGGL((conv_halo2wg_kernel<4, 1>), g4, dim3(WTHR), LDS4, s, p, p.N / 128, tiles_x, tiles_y);
             else if (epi == 2) hipLaunchKernelGGL((conv_halo2wg_kernel<4, 2>), g4, dim3(WTHR), LDS4, s, p, p.N / 128, tiles_x, tiles_y);

@@ -5,7 +5,6 @@
 #include "decoder_kernels.h"
 #include "api_util.h"
 #include "drop.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -629,145 +628,6 @@ __global__ __launch_bounds__(256) void attn_fwd_combine_kernel(const float* __re
         alpha[(long long)v * Rp + rr] = expf(alpha[(long long)v * Rp + rr] - m) * inv;
 }
 
-// ---- forward attention WITHOUT a merge step (round 3 experiment, opt-in: LXO_ATT_SPLIT=1; measured SLOWER than part + combine:
-// 11.1 + 12.2 us against 16.6 + 4.9 us per decoder step -- the scores kernel moves 28 MB in one burst per workgroup and pays the
-// launch ramp, the att_h / beta round trip and the tail without anything to overlap them with, i.e. the fixed costs twice) ----
-// The part / combine pair splits a sample's regions over workgroups, so the softmax needs a second launch that merges the
-// chunk partials (4.9 us per decoder step for 1 MB of data).  Here the two streams are split instead: (1) the scores
-// e[v][r] = sum_k beta_k tanh(att_img[r][k] + att_h[k]) need only `att_img` (a third of the bytes) and no merge at all;
-// (2) the context is split over CHANNEL slices of 64: every workgroup of a sample recomputes the softmax statistics from the
-// <= 1024 raw scores (868 exps) and accumulates its 64 channels of sum_r alpha_r img[r][:] -- no cross-workgroup step.
-// Rows are fetched in 16-byte pieces (scores: 32 lanes per 512-byte row, two rows per instruction; context: 8 lanes per
-// 128-byte row segment, eight rows per instruction), ATT_U instructions in flight per wave.
-template <typename CT, int ATT_U>
-__global__ __launch_bounds__(512) void attn_scores_kernel(const CT* __restrict__ att_img, const float* __restrict__ att_h,
-                                                         const float* __restrict__ beta, float* __restrict__ raw,
-                                                         int R, int Rp, int E, int beam, int rows_per) {
-    constexpr int EPL = 16 / (int)sizeof(CT);                  // elements per lane and load: 8 (bf16) / 4 (f32)
-    const int ch = blockIdx.x, v = blockIdx.y, bi = v / beam;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lpr = (E + EPL - 1) / EPL;                       // lanes per row (E <= 64 * EPL: one instruction covers >= 1 row)
-    const int rpi = 64 / lpr;                                  // rows per load instruction
-    const int rl = lane / lpr, kl = (lane - rl * lpr) * EPL;   // this lane's row within the instruction, first k
-    const int r0 = ch * rows_per;
-    const int n = min(R, r0 + rows_per) - r0;
-    if (n <= 0) return;
-    const CT* ai = att_img + ((long long)bi * R + r0) * E;
-    const bool kok = rl < rpi && kl < E;
-    const int kc = kok ? kl : 0;
-    float ah[EPL], bt[EPL];
-    {
-        const float* ap = att_h + (long long)v * E + kc;
-        const float* bp = beta + kc;
-#pragma unroll
-        for (int j = 0; j < EPL; j += 4) {
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + j), b4 = *reinterpret_cast<const f32x4*>(bp + j);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { ah[j + e] = a4[e]; bt[j + e] = kok ? b4[e] : 0.f; }
-        }
-    }
-    const int rows_it = ATT_W * ATT_U * rpi;                    // rows a workgroup covers per iteration
-    for (int base = 0; base < n; base += rows_it) {
-        float x[ATT_U][EPL];
-#pragma unroll
-        for (int u = 0; u < ATT_U; ++u) {                      // unconditional (clamped) loads: all ATT_U requests in flight together
-            const int r = min(base + (u * ATT_W + wave) * rpi + rl, n - 1);
-            if constexpr (EPL == 8) load8(ai + (long long)r * E + kc, x[u]);
-            else load4(ai + (long long)r * E + kc, x[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < ATT_U; ++u) {
-            float a = 0.f;
-#pragma unroll
-            for (int j = 0; j < EPL; ++j) a = fmaf(tanh_ct<CT>(x[u][j] + ah[j]), bt[j], a);
-            for (int o = 1; o < lpr; o <<= 1) a += __shfl_xor(a, o);      // lpr is a power of two (E = 256: 32 / 64 lanes)
-            const int r = base + (u * ATT_W + wave) * rpi + rl;
-            if (kok && kl == 0 && r < n) raw[(long long)v * Rp + r0 + r] = a;
-        }
-    }
-}
-
-template <typename CT, int ATT_U>
-__global__ __launch_bounds__(512) void attn_ctx_kernel(const CT* __restrict__ img, const float* __restrict__ raw, float* __restrict__ alpha,
-                                                      float* __restrict__ ctx, int ldctx, bf16_t* __restrict__ ctxb, int ldcb,
-                                                      int R, int Rp, int C, int beam) {
-    constexpr int EPL = 16 / (int)sizeof(CT);                  // channels per lane: 8 (bf16) / 4 (f32)
-    constexpr int LPR = 64 / EPL;                              // lanes per 64-channel row segment: 8 / 16
-    constexpr int RPI = 64 / LPR;                              // rows per load instruction: 8 / 4
-    __shared__ float sc[1024];
-    __shared__ float red[ATT_W];
-    __shared__ float accs[ATT_W][64];
-    const int sl = blockIdx.x, ns = gridDim.x, v = blockIdx.y, bi = v / beam;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // softmax statistics of the whole sample (every slice recomputes them: R <= 1024 scores)
-    const float* rv = raw + (long long)v * Rp;
-    const float e0 = rv[min(tid, R - 1)], e1 = rv[min(tid + 512, R - 1)];
-    float m = fmaxf(tid < R ? e0 : -3.0e38f, tid + 512 < R ? e1 : -3.0e38f);
-    m = wave_max(m);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    m = red[0];
-#pragma unroll
-    for (int w = 1; w < ATT_W; ++w) m = fmaxf(m, red[w]);
-    const float p0 = tid < R ? expf(e0 - m) : 0.f, p1 = tid + 512 < R ? expf(e1 - m) : 0.f;
-    float l = wave_sum(p0 + p1);
-    __syncthreads();
-    if (lane == 0) red[wave] = l;
-    __syncthreads();
-    l = 0.f;
-#pragma unroll
-    for (int w = 0; w < ATT_W; ++w) l += red[w];
-    const float inv = 1.0f / l;
-    if (tid < R) sc[tid] = p0 * inv;
-    if (tid + 512 < R) sc[tid + 512] = p1 * inv;
-    // the normalised weights (kept for the backward pass / the visualisation export): slice s writes its share of the rows
-    const int rq = (R + ns - 1) / ns;
-    if (tid < R && tid / rq == sl) alpha[(long long)v * Rp + tid] = p0 * inv;
-    if (tid + 512 < R && (tid + 512) / rq == sl) alpha[(long long)v * Rp + tid + 512] = p1 * inv;
-    __syncthreads();
-    // context of this slice's 64 channels
-    const int rl = lane / LPR, cl = (lane - rl * LPR) * EPL;
-    const CT* im = img + (long long)bi * R * C + sl * 64 + cl;
-    float acc[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-    constexpr int ROWS_IT = ATT_W * ATT_U * RPI;
-    for (int base = 0; base < R; base += ROWS_IT) {
-        float x[ATT_U][EPL];
-#pragma unroll
-        for (int u = 0; u < ATT_U; ++u) {
-            const int r = min(base + (u * ATT_W + wave) * RPI + rl, R - 1);
-            if constexpr (EPL == 8) load8(im + (long long)r * C, x[u]);
-            else load4(im + (long long)r * C, x[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < ATT_U; ++u) {
-            const int r = base + (u * ATT_W + wave) * RPI + rl;
-            const float w = r < R ? sc[r] : 0.f;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[e] = fmaf(w, x[u][e], acc[e]);
-        }
-    }
-#pragma unroll
-    for (int o = LPR; o < 64; o <<= 1) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] += __shfl_xor(acc[e], o);
-    }
-    if (rl == 0) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) accs[wave][cl + e] = acc[e];
-    }
-    __syncthreads();
-    if (tid < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < ATT_W; ++w) t += accs[w][tid];
-        const int c = sl * 64 + tid;
-        ctx[(long long)v * ldctx + c] = t;
-        if (ctxb) ctxb[(long long)v * ldcb + c] = f2bf(t);
-    }
-}
-
 // ---- attention backward (per step): d_e and d_att_h in one pass; d_img / d_att_img are deferred ----
 // EXPD (bf16 mode): `att_img` holds E_x = e^{2x} (ws region "att_exp") instead of x.  With E_a = e^{2 att_h} formed once per launch,
 // r = 1 / (1 + E_x E_a) gives tanh(x + a) = 1 - 2r and 1 - tanh^2 = 4 r (1 - r): ONE transcendental (the reciprocal) and three plain
@@ -931,117 +791,6 @@ __global__ __launch_bounds__(512) void attn_bwd_part_kernel(const CT* __restrict
 #pragma unroll
         for (int w = 0; w < ATT_W; ++w) t += rede[w][k];
         atomicAdd(&datth[(long long)v * E + k], t);
-    }
-}
-
-// The same for the shipped widths in bf16 mode (E = 256, C = 512, d_ctx as final values): the chunk is walked in blocks of 8 waves x ATT_U
-// rows with TWO blocks in flight -- block i + 1 is requested before block i is computed (the kernel above issues a block, waits for
-// all of it, computes, issues the next: one memory round trip per block with nothing under it: 16.2 us for 85 MB where the forward
-// chain's stream phase moves the same bytes in 11.5).  Loads are buffer loads whose row offset is SCALAR (the row is wave-uniform) and
-// whose per-lane offset is one loop-invariant register; rows beyond the chunk are clamped and masked.
-typedef __amdgpu_buffer_rsrc_t ab_rsrc_t;
-template <int ATT_U>
-LXO_DEV void attb_load(u32x4 (&xi)[ATT_U], u32x2 (&xa)[ATT_U], float (&al)[ATT_U], ab_rsrc_t rim, ab_rsrc_t rai, ab_rsrc_t ral, int base, int n, int lane) {
-#pragma unroll
-    for (int u = 0; u < ATT_U; ++u) {
-        const int r = max(min(base + ATT_W * u, n - 1), 0);
-        xi[u] = __builtin_amdgcn_raw_buffer_load_b128(rim, lane * 16, r * 1024, 0);
-        xa[u] = __builtin_amdgcn_raw_buffer_load_b64(rai, lane * 8, r * 512, 0);
-        al[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ral, 0, r * 4, 0));
-    }
-}
-template <int ATT_U>
-LXO_DEV void attb_block(const u32x4 (&xi)[ATT_U], const u32x2 (&xa)[ATT_U], const float (&al)[ATT_U], int base, int n, const float (&dc)[8],
-                        const float (&ah)[4], float s, float (&acc)[4], float* de_row, int lane) {
-    float pt[ATT_U];
-#pragma unroll
-    for (int u = 0; u < ATT_U; ++u) {
-        float a = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            a = fmaf(__uint_as_float(xi[u][e] << 16), dc[2 * e], a);
-            a = fmaf(__uint_as_float(xi[u][e] & 0xffff0000u), dc[2 * e + 1], a);
-        }
-        pt[u] = a;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int u = 0; u < ATT_U; ++u) pt[u] += __shfl_xor(pt[u], o);
-    }
-#pragma unroll
-    for (int u = 0; u < ATT_U; ++u) {
-        const int r = base + ATT_W * u;
-        if (r >= n) continue;                                           // wave-uniform: a clamped row costs its loads, not its arithmetic
-        const float d = al[u] * (pt[u] - s);                            // softmax backward
-        if (lane == 0) de_row[r] = d;
-        const float x0 = __uint_as_float(xa[u][0] << 16), x1 = __uint_as_float(xa[u][0] & 0xffff0000u);
-        const float x2 = __uint_as_float(xa[u][1] << 16), x3 = __uint_as_float(xa[u][1] & 0xffff0000u);
-        const float t0 = tanh_ct<bf16_t>(x0 + ah[0]), t1 = tanh_ct<bf16_t>(x1 + ah[1]), t2 = tanh_ct<bf16_t>(x2 + ah[2]), t3 = tanh_ct<bf16_t>(x3 + ah[3]);
-        acc[0] = fmaf(d, 1.f - t0 * t0, acc[0]); acc[1] = fmaf(d, 1.f - t1 * t1, acc[1]);
-        acc[2] = fmaf(d, 1.f - t2 * t2, acc[2]); acc[3] = fmaf(d, 1.f - t3 * t3, acc[3]);
-    }
-}
-template <int ATT_U>
-__global__ __launch_bounds__(512) void attn_bwd_stream_kernel(const bf16_t* __restrict__ att_img, const bf16_t* __restrict__ img,
-                                                             const float* __restrict__ att_h, const float* __restrict__ beta,
-                                                             const float* __restrict__ alpha, const float* __restrict__ dctx, int lddc,
-                                                             const float* __restrict__ ctx, int ldctx,
-                                                             float* __restrict__ de, float* __restrict__ datth,
-                                                             int R, int Rp, int rows_per, int rev) {
-    constexpr int E = 256, C = 512;
-    __shared__ float rede[ATT_W][E];
-    const int ch = blockIdx.x, v = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r0 = ch * rows_per;
-    const int n = min(R, r0 + rows_per) - r0;
-    if (n <= 0) return;                                  // block-uniform
-    const ab_rsrc_t rim = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(img + ((long long)v * R + r0) * C), 0, n * C * 2, 0x00020000);
-    const ab_rsrc_t rai = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(att_img + ((long long)v * R + r0) * E), 0, n * E * 2, 0x00020000);
-    const ab_rsrc_t ral = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(alpha + (long long)v * Rp + r0), 0, n * 4, 0x00020000);
-    const int nblk2 = ((n + ATT_W * ATT_U - 1) / (ATT_W * ATT_U) + 1) & ~1;          // blocks, rounded up to pairs (an extra block is all clamped rows)
-#define ABASE(i) (wave + ATT_W * ATT_U * (rev ? nblk2 - 1 - (i) : (i)))
-    u32x4 xiA[ATT_U], xiB[ATT_U]; u32x2 xaA[ATT_U], xaB[ATT_U]; float alA[ATT_U], alB[ATT_U];
-    attb_load<ATT_U>(xiA, xaA, alA, rim, rai, ral, ABASE(0), n, lane);               // the first two blocks are on their way before anything else is read
-    attb_load<ATT_U>(xiB, xaB, alB, rim, rai, ral, ABASE(1), n, lane);
-    // this lane's 8 channels of d_ctx and ctx, its 4 columns of att_h; every wave forms s = <ctx, d_ctx> = sum_r alpha_r d_alpha_r by itself
-    const int c0 = lane * 8;
-    const float* dp = dctx + (long long)v * lddc + c0;
-    const float* cp = ctx + (long long)v * ldctx + c0;
-    const f32x4 d0 = *reinterpret_cast<const f32x4*>(dp), d1 = *reinterpret_cast<const f32x4*>(dp + 4);
-    const f32x4 x0 = *reinterpret_cast<const f32x4*>(cp), x1 = *reinterpret_cast<const f32x4*>(cp + 4);
-    const f32x4 a4 = *reinterpret_cast<const f32x4*>(att_h + (long long)v * E + lane * 4);
-    const f32x4 b4 = *reinterpret_cast<const f32x4*>(beta + lane * 4);
-    float dc[8], ah[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { dc[e] = d0[e]; dc[4 + e] = d1[e]; ah[e] = a4[e]; }
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s = fmaf(x0[e], dc[e], fmaf(x1[e], dc[4 + e], s));
-    s = wave_sum(s);
-    float* de_row = de + (long long)v * Rp + r0;
-    for (int it = 0; it + 2 < nblk2; it += 2) {
-        attb_block<ATT_U>(xiA, xaA, alA, ABASE(it), n, dc, ah, s, acc, de_row, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        attb_load<ATT_U>(xiA, xaA, alA, rim, rai, ral, ABASE(it + 2), n, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        attb_block<ATT_U>(xiB, xaB, alB, ABASE(it + 1), n, dc, ah, s, acc, de_row, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        attb_load<ATT_U>(xiB, xaB, alB, rim, rai, ral, ABASE(it + 3), n, lane);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // the last pair: nothing left to request
-    attb_block<ATT_U>(xiA, xaA, alA, ABASE(nblk2 - 2), n, dc, ah, s, acc, de_row, lane);
-    attb_block<ATT_U>(xiB, xaB, alB, ABASE(nblk2 - 1), n, dc, ah, s, acc, de_row, lane);
-#undef ABASE
-#pragma unroll
-    for (int j = 0; j < 4; ++j) rede[wave][lane * 4 + j] = acc[j] * b4[j];
-    __syncthreads();
-    if (tid < E) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < ATT_W; ++w) t += rede[w][tid];
-        atomicAdd(&datth[(long long)v * E + tid], t);
     }
 }
 
@@ -1725,38 +1474,22 @@ int lxo_k_tanh_finalize(Slabs sl, float* o, int ldo, Drop dr, int rows, int cols
     DONE;
 }
 static int att_u(int rows_per) {
-    static int forced = -1;
     // rows of both streams a wave keeps in flight per iteration (8 waves per workgroup): 8, or 7 when 56 rows per iteration need no more
     // iterations than 64 would -- the benchmark's chunk of 109 rows is 2 x 56 instead of 64 + 45 (forward pair 23.3 -> 22.3 us per step).
-    // LXO_ATT_U=7 / 8 forces one instantiation.
-    if (forced < 0) { const char* e = getenv("LXO_ATT_U"); forced = e ? atoi(e) : 0; }
-    if (forced == 7 || forced == 8) return forced;
     return (rows_per + 55) / 56 <= (rows_per + 63) / 64 ? 7 : 8;
 }
+// the per-row attention kernels' instantiation from (dtype, E <= 256, att_u): K_(CT, KCT, ATT_U) with 256 * KCT >= E
+#define ATT_BY_U(K_, CT_, KCT_) do { if (att_u(rows_per) == 8) K_(CT_, KCT_, 8); else K_(CT_, KCT_, 7); } while (0)
+#define ATT_BY_CT_E(K_) do { if (dt == LXO_BF16) { if (E <= 256) ATT_BY_U(K_, bf16_t, 1); else ATT_BY_U(K_, bf16_t, 4); } \
+                             else { if (E <= 256) ATT_BY_U(K_, float, 1); else ATT_BY_U(K_, float, 4); } } while (0)
 int lxo_k_attn_fwd(int dt, const void* att_img, const void* img, const float* att_h, Slabs ahs, float* att_h_out, const float* beta, float* alpha, float* part,
                    float* ctx, int ldctx, void* ctxb, int ldcb, int nv, int R, int Rp, int E, int C, int beam, int nch, int rev, hipStream_t st, const void* att_exp) {
     if (E > 1024 || C > 512 || nch < 1 || nch > 32) return -2;
     const int rows_per = cdiv(R, nch);
     dim3 grid(nch, nv);
-    static int split = -1;      // LXO_ATT_SPLIT=1: scores + softmax-context, no merge launch (A/B, measured slower); default: part + combine
-    if (split < 0) { const char* e = getenv("LXO_ATT_SPLIT"); split = (e && e[0] == '1') ? 1 : 0; }
-    const int epl = dt == LXO_BF16 ? 8 : 4;
-    if (split && ahs.n == 0 && att_h && R <= 1024 && C % 64 == 0 && E % epl == 0 && E <= 64 * epl && ((E / epl) & (E / epl - 1)) == 0) {
-        // raw scores travel through the `part` scratch (>= nv * Rp floats); alpha receives the normalised weights
-        if (dt == LXO_BF16) {
-            hipLaunchKernelGGL((attn_scores_kernel<bf16_t, 8>), grid, dim3(512), 0, st, (const bf16_t*)att_img, att_h, beta, part, R, Rp, E, beam, rows_per);
-            hipLaunchKernelGGL((attn_ctx_kernel<bf16_t, 8>), dim3(C / 64, nv), dim3(512), 0, st, (const bf16_t*)img, part, alpha, ctx, ldctx, (bf16_t*)ctxb, ldcb, R, Rp, C, beam);
-        } else {
-            hipLaunchKernelGGL((attn_scores_kernel<float, 8>), grid, dim3(512), 0, st, (const float*)att_img, att_h, beta, part, R, Rp, E, beam, rows_per);
-            hipLaunchKernelGGL((attn_ctx_kernel<float, 8>), dim3(C / 64, nv), dim3(512), 0, st, (const float*)img, part, alpha, ctx, ldctx, (bf16_t*)ctxb, ldcb, R, Rp, C, beam);
-        }
-        DONE;
-    }
     // beam search: one pass over an image's rows for all its hypotheses (attn_fwd_part_beam_kernel); the chunk count is chosen per IMAGE
-    static int beam_shared = -1;                          // LXO_ATT_BEAM_SHARED=0: the per-row kernel for beam search too (A/B)
-    if (beam_shared < 0) { const char* e = getenv("LXO_ATT_BEAM_SHARED"); beam_shared = (e && e[0] == '0') ? 0 : 1; }
     // (beam == 1 with att_exp: greedy decode in bf16 -- the same kernel with one hypothesis per image, for its E-domain arithmetic)
-    if (beam_shared && (beam == 2 || beam == 3 || beam == 5 || (beam == 1 && att_exp && dt == LXO_BF16)) && ahs.n == 0 && att_h && E <= 256 && C <= 512 && nv % beam == 0) {
+    if ((beam == 2 || beam == 3 || beam == 5 || (beam == 1 && att_exp && dt == LXO_BF16)) && ahs.n == 0 && att_h && E <= 256 && C <= 512 && nv % beam == 0) {
         const int nimg = nv / beam;
         int nb = cdiv(512, nimg);
         if (nb > 16) nb = 16;
@@ -1774,15 +1507,10 @@ int lxo_k_attn_fwd(int dt, const void* att_img, const void* img, const float* at
         hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(4, nv), dim3(256), 0, st, part, alpha, ctx, ldctx, (bf16_t*)ctxb, ldcb, R, Rp, C, nb, rpb);
         DONE;
     }
-#define AF_ARGS att_h, ahs, att_h_out, beta, alpha, part, R, Rp, E, C, beam, nch, rows_per, rev
-    if (dt == LXO_BF16) {
-        if (E <= 256) { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_fwd_part_kernel<bf16_t, 1, 8>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AF_ARGS); else hipLaunchKernelGGL((attn_fwd_part_kernel<bf16_t, 1, 7>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AF_ARGS); }
-        else { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_fwd_part_kernel<bf16_t, 4, 8>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AF_ARGS); else hipLaunchKernelGGL((attn_fwd_part_kernel<bf16_t, 4, 7>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AF_ARGS); }
-    } else {
-        if (E <= 256) { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_fwd_part_kernel<float, 1, 8>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AF_ARGS); else hipLaunchKernelGGL((attn_fwd_part_kernel<float, 1, 7>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AF_ARGS); }
-        else { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_fwd_part_kernel<float, 4, 8>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AF_ARGS); else hipLaunchKernelGGL((attn_fwd_part_kernel<float, 4, 7>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AF_ARGS); }
-    }
-#undef AF_ARGS
+#define AF(CT_, KCT_, U_) hipLaunchKernelGGL((attn_fwd_part_kernel<CT_, KCT_, U_>), grid, dim3(512), 0, st, (const CT_*)att_img, (const CT_*)img, \
+                                             att_h, ahs, att_h_out, beta, alpha, part, R, Rp, E, C, beam, nch, rows_per, rev)
+    ATT_BY_CT_E(AF);
+#undef AF
     hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(4, nv), dim3(256), 0, st, part, alpha, ctx, ldctx, (bf16_t*)ctxb, ldcb, R, Rp, C, nch, rows_per);
     DONE;
 }
@@ -1799,32 +1527,19 @@ int lxo_k_attn_bwd(int dt, const void* att_img, const void* att_exp, const void*
     if (E > 1024 || C > 512 || nch < 1 || nch > 32) return -2;
     const int rows_per = cdiv(R, nch);
     dim3 grid(nch, nv);
-    // LXO_ATT_BWD2=1: the variant with two row blocks in flight.  Measured SLOWER (decoder backward 3.42 vs 3.33 ms): the kernel is bound by
-    // its vector arithmetic (~380 issue cycles per row and wave, 10 us per launch), not by exposed latency -- with two workgroups per CU the
-    // other waves already cover the loads -- and 32-row blocks pad a 109-row chunk to 128.  Kept for A/B runs.
-    static int stream2 = -1;
-    if (stream2 < 0) { const char* e = getenv("LXO_ATT_BWD2"); stream2 = (e && e[0] == '1') ? 1 : 0; }
-    if (stream2 && dt == LXO_BF16 && E == 256 && C == 512 && dcs.n == 1 && lddc % 4 == 0 && ldctx % 4 == 0 && (long long)rows_per * 1024 < (1LL << 31)) {
-        const float* dctx = dcs.p + dcoff;
-        if (dctx_out) return -2;                           // (the fused path never asks for the summed copy)
-        hipLaunchKernelGGL((attn_bwd_stream_kernel<4>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, att_h, beta, alpha, dctx, dcs.ld,
-                           ctx, ldctx, de, datth, R, Rp, rows_per, rev);
-        DONE;
-    }
-#define AB_ARGS att_h, beta, alpha, dcs, dcoff, dctx_out, lddc, ctx, ldctx, de, datth, R, Rp, E, C, rows_per, rev
-    if (dt == LXO_BF16 && att_exp && E <= 256) {
-        if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_bwd_part_kernel<bf16_t, 1, 8, true>), grid, dim3(512), 0, st, (const bf16_t*)att_exp, (const bf16_t*)img, AB_ARGS);
-        else hipLaunchKernelGGL((attn_bwd_part_kernel<bf16_t, 1, 7, true>), grid, dim3(512), 0, st, (const bf16_t*)att_exp, (const bf16_t*)img, AB_ARGS);
-    } else if (dt == LXO_BF16) {
-        if (E <= 256) { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_bwd_part_kernel<bf16_t, 1, 8>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AB_ARGS); else hipLaunchKernelGGL((attn_bwd_part_kernel<bf16_t, 1, 7>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AB_ARGS); }
-        else { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_bwd_part_kernel<bf16_t, 4, 8>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AB_ARGS); else hipLaunchKernelGGL((attn_bwd_part_kernel<bf16_t, 4, 7>), grid, dim3(512), 0, st, (const bf16_t*)att_img, (const bf16_t*)img, AB_ARGS); }
-    } else {
-        if (E <= 256) { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_bwd_part_kernel<float, 1, 8>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AB_ARGS); else hipLaunchKernelGGL((attn_bwd_part_kernel<float, 1, 7>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AB_ARGS); }
-        else { if (att_u(rows_per) == 8) hipLaunchKernelGGL((attn_bwd_part_kernel<float, 4, 8>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AB_ARGS); else hipLaunchKernelGGL((attn_bwd_part_kernel<float, 4, 7>), grid, dim3(512), 0, st, (const float*)att_img, (const float*)img, AB_ARGS); }
-    }
-#undef AB_ARGS
+#define AB_X(CT_, KCT_, U_, X_, AI_) hipLaunchKernelGGL((attn_bwd_part_kernel<CT_, KCT_, U_, X_>), grid, dim3(512), 0, st, (const CT_*)(AI_), (const CT_*)img, \
+                                                       att_h, beta, alpha, dcs, dcoff, dctx_out, lddc, ctx, ldctx, de, datth, R, Rp, E, C, rows_per, rev)
+#define AB_EXP(CT_, KCT_, U_) AB_X(CT_, KCT_, U_, true, att_exp)
+#define AB(CT_, KCT_, U_) AB_X(CT_, KCT_, U_, false, att_img)
+    if (dt == LXO_BF16 && att_exp && E <= 256) ATT_BY_U(AB_EXP, bf16_t, 1);
+    else ATT_BY_CT_E(AB);
+#undef AB
+#undef AB_EXP
+#undef AB_X
     DONE;
 }
+#undef ATT_BY_CT_E
+#undef ATT_BY_U
 int lxo_k_det_reduce(const float* part, int nslot, long long stride, int N, float* out, hipStream_t st) {
     if (nslot <= 0 || N <= 0) return 0;
     hipLaunchKernelGGL(det_reduce_kernel, dim3(cdiv(N, 16)), dim3(256), 0, st, part, nslot, stride, N, out);      // 16 columns x 16 slot groups per workgroup

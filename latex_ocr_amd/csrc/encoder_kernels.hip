@@ -12,7 +12,7 @@
 //   mask_convert     : d_y6 = d_img(f32) * (y6 > 0) -> compute dtype, + bias gradient
 //   timing_signal    : positional.py:42-64 table [Hp*Wp][C] f32
 #include "encoder_kernels.h"
-#include <stdlib.h>
+#include "switches.h"
 
 namespace {
 
@@ -822,16 +822,12 @@ template <typename CT> static void conv1_fwd_t(const uint8_t* img, const float* 
     hipLaunchKernelGGL((conv1_pool_fwd_kernel<CT>), dim3(grid_for((long long)B * Hp * ((Wp + 31) / 32), 1, 4096)), dim3(256), 0, s,
                        img, w, b, (CT*)out, B, H, W, Hp, Wp);
 }
-static int conv1_mfma() {       // LXO_CONV1_MFMA=0: the VALU kernels in bf16 mode too (A/B)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("LXO_CONV1_MFMA"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return v;
-}
+static int conv1_mfma() { return lxo_switch(SW_CONV1_MFMA); }       // LXO_CONV1_MFMA=0: the VALU kernels in bf16 mode too (A/B)
+constexpr int kC1FwdCap = 4096, kC1BwdCap = 512, kPoolBwdCap = 2048;      // workgroup caps of the conv1 + pool kernels and the pool backward
 int lxo_k_conv1_pool_fwd(int dt, const uint8_t* img, const float* w, const float* b, void* out, int B, int H, int W, hipStream_t s) {
     if (dt == LXO_BF16 && conv1_mfma()) {
         const int Hp = (H + 1) / 2, Wp = (W + 1) / 2;
-        static int capf = -1; if (capf < 0) { const char* e = getenv("LXO_C1_CAPF"); capf = e ? atoi(e) : 4096; }
-        hipLaunchKernelGGL(conv1_pool_fwd_mfma_kernel, dim3(grid_for((long long)B * Hp * ((Wp + C1_SEG - 1) / C1_SEG), 1, capf)), dim3(256), 0, s,
+        hipLaunchKernelGGL(conv1_pool_fwd_mfma_kernel, dim3(grid_for((long long)B * Hp * ((Wp + C1_SEG - 1) / C1_SEG), 1, kC1FwdCap)), dim3(256), 0, s,
                            img, w, b, (bf16_t*)out, B, H, W, Hp, Wp);
         return (int)hipGetLastError();
     }
@@ -854,8 +850,7 @@ template <typename CT> static int conv1_bwd_t(const uint8_t* img, const float* w
 int lxo_k_conv1_pool_bwd(int dt, const uint8_t* img, const float* w, const float* b, const void* dout, float* dw, float* db, int B, int H, int W, DetScratch det, hipStream_t s) {
     if (dt == LXO_BF16 && conv1_mfma()) {
         const int Hp = (H + 1) / 2, Wp = (W + 1) / 2;
-        static int cap = -1; if (cap < 0) { const char* e = getenv("LXO_C1_CAP"); cap = e ? atoi(e) : 512; }
-        const int g = grid_for((long long)B * Hp * ((Wp + C1_SEG - 1) / C1_SEG), 4, cap);
+        const int g = grid_for((long long)B * Hp * ((Wp + C1_SEG - 1) / C1_SEG), 4, kC1BwdCap);
         float* part = nullptr;                  // deterministic mode: one slot [dw 576 | db 64] per workgroup, added in workgroup order
         if (det.p) { if ((size_t)g * 640 > det.floats) return -6; part = det.p; }
         hipLaunchKernelGGL(conv1_pool_bwd_mfma_kernel, dim3(g), dim3(256), 0, s, img, w, b, (const bf16_t*)dout, dw, db, part, B, H, W, Hp, Wp);
@@ -889,13 +884,11 @@ int lxo_k_maxpool_mask_bwd(const unsigned char* mask, const void* dp, void* dy, 
     if (C % 8 || C > 512 || 256 % (C / 8)) return -2;
     const int Ho = (H + ph - 1) / ph, Wo = (W + pw - 1) / pw;
     const int ppb = 256 / (C / 8);
-    // Workgroup cap (LXO_POOLBWD_CAP, A/B): ALONE on the GPU 512 workgroups (two per CU, 8 rounds of four pixels per thread) run the three pools of the benchmark
+    // Workgroup cap (kPoolBwdCap): ALONE on the GPU 512 workgroups (two per CU, 8 rounds of four pixels per thread) run the three pools of the benchmark
     // shape in 61 / 48 / 47 us where 2048 take 82 / 72 / 72 (fewer, longer streams keep more of the DRAM traffic inside open pages; 384 / 768: 5-10 % behind 512) --
     // but inside the training step they run beside the weight-gradient kernel of the second stream, and there 2048 is the faster step: 7.418 / 7.422 ms against
     // 7.433 / 7.439 with 512 (same box, alternating processes).  The step is what counts: 2048.
-    static int pcap = -1;
-    if (pcap < 0) { const char* e = getenv("LXO_POOLBWD_CAP"); pcap = e ? atoi(e) : 2048; }
-    const dim3 grid(grid_for((long long)B * Ho * Wo, ppb * 8, pcap));
+    const dim3 grid(grid_for((long long)B * Ho * Wo, ppb * 8, kPoolBwdCap));
     float* db_part = nullptr;                 // deterministic mode: one slot [C] per workgroup
     if (det.p && db) { if ((size_t)grid.x * C > det.floats) return -6; db_part = det.p; }
 #define MB_ARGS mask, (const bf16_t*)dp, (bf16_t*)dy, db, db_part, B, H, W, C, Ho, Wo

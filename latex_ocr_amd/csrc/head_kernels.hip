@@ -3,7 +3,7 @@
 // the row steps they are made of.
 #include "head_kernels.h"
 #include "drop.h"
-#include <stdlib.h>
+#include "switches.h"
 
 namespace {
 
@@ -1216,8 +1216,7 @@ int lxo_k_beam_step(float* logits, int Vp, int V, int nimg, int k, int id_end, i
         dp.log_gamma = logf(div_gamma);
         dp.thr = div_prob >= 1.f ? 16777216u : (unsigned)(div_prob * 16777216.0f);
     }
-    static int fast = -1;                                      // LXO_BEAM_FAST=0: the general kernel always (A/B)
-    if (fast < 0) { const char* e = getenv("LXO_BEAM_FAST"); fast = (e && e[0] == '0') ? 0 : 1; }
+    const int fast = lxo_switch(SW_BEAM_FAST);                 // LXO_BEAM_FAST=0: the general kernel always (A/B)
     const DecPrefix pf = prefix ? *prefix : DecPrefix{};
     const DecAllow al = allow ? *allow : DecAllow{};
     if (fast && dp.log_gamma == 0.f && (long long)k * V <= BS_TH * BS_NPT && k * BS_NW <= 64) {

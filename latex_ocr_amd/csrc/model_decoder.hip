@@ -14,6 +14,7 @@
 #include "xdec.h"
 #include "dimg.h"
 #include "api_util.h"
+#include "switches.h"
 #include "timing.h"
 
 namespace {
@@ -52,11 +53,7 @@ const Slabs kNoSlabs = {nullptr, 0, 0, 0};
 }  // namespace
 
 // the attention kernels walk their row blocks in alternating directions from step to step (L2 reuse; LXO_ATT_ALT=0: always forward)
-static bool att_alternate() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("LXO_ATT_ALT"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return v == 1;
-}
+static bool att_alternate() { return lxo_switch(SW_ATT_ALT) != 0; }
 // out[M][N] (+)= act(A[M][K] W[N][K]^T + bias) for the few-row GEMMs outside the loops (initial states, their gradients) on the
 // fused step kernels (16-row tiles, one workgroup per 16 columns: 128 workgroups where gemm_skinny_kernel has 16)
 static int rs_dense(const Plan& P, const float* A, int lda, const void* W, int ldw, float* out, int ldo, int M, int N, int K,
@@ -914,7 +911,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
         HIPRC(hipMemsetAsync(x.stop, 0, sizeof(int), st));
         HIPRC(hipMemsetAsync(chain_err(P, ws, kChainFwd), 0, sizeof(unsigned), st));      // the error word: once per decode (the launcher leaves it alone)
         int chunk_steps = 16;                             // steps per launch (LXO_XDEC_DEC_CHUNK: 1 .. 16; read per call so that a test can vary it)
-        { const char* e = getenv("LXO_XDEC_DEC_CHUNK"); if (e && atoi(e) > 0 && atoi(e) < 16) chunk_steps = atoi(e); }
+        { const int c = lxo_switch(SW_XDEC_DEC_CHUNK); if (c > 0 && c < 16) chunk_steps = c; }
         bool took = true;
         const int rc = decode_loop(max_iter, chunk_steps, 32, d.flags, st, steps_out, [&](int first, int n, int* unfinished) -> int {
             XDecDec y = x; y.t0 = first; y.nsteps = n; y.unfinished = unfinished;
@@ -1029,9 +1026,7 @@ int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* 
     // the state of a step's rows is that of their PARENT hypotheses (beam_search_decoder_cell.py:176-178).  With the fused step kernels the next LSTM launch
     // reads its [o | h] and c rows through the parents in place; the launch that re-ordered the rows (beam_permute_kernel, 5.3 us + its gap) is only left for
     // the split-K step kernels and for lxo_decode_step, whose callers may look at the state between steps (LXO_BEAM_INDIRECT=0: always re-order; A/B)
-    static int indirect_on = -1;
-    if (indirect_on < 0) { const char* e = getenv("LXO_BEAM_INDIRECT"); indirect_on = (e && e[0] == '0') ? 0 : 1; }
-    const bool indirect = indirect_on && d.fused();
+    const bool indirect = lxo_switch(SW_BEAM_INDIRECT) && d.fused();
     return decode_loop_steps(max_iter, d.flags, st, steps_out, [&](int time, int* unfinished) -> int {
         RC(decode_common_step(P, prm, wp, ws, d, time, time == 0 ? nullptr : d.ids_step, st, indirect ? d.par_step : nullptr));
         return decode_select(P, d, id_end, time, out, unfinished, indirect, st);

@@ -2,7 +2,7 @@
 #include "plan.h"
 #include <stdio.h>
 #include <string.h>
-#include <stdlib.h>
+#include "switches.h"
 
 static const char* kParamNames[P_COUNT] = {
     "Encoder/convolutional_encoder/conv2d/kernel", "Encoder/convolutional_encoder/conv2d/bias",
@@ -228,8 +228,7 @@ Plan::Plan(const lxo_shape& sh, int /*unused*/) : s(sh) {
 }
 
 int Plan::attn_chunks(int nv) const {
-    static int target = -1;                        // tuning knob: workgroups wanted for the attention stream
-    if (target < 0) { const char* e = getenv("LXO_ATT_WGS"); target = (e && atoi(e) > 0) ? atoi(e) : 512; }
+    constexpr int target = 512;                    // workgroups wanted for the attention stream
     int nch = (target + nv - 1) / nv;              // ~2 workgroups per CU by default
     if (nch > 16) nch = 16;
     const int by_rows = R / 32 > 0 ? R / 32 : 1;   // keep >= 32 rows per chunk
@@ -256,17 +255,12 @@ int Plan::validate(char* msg, size_t n) const {
 }
 
 bool Plan::att_exp() const {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("LXO_ATT_EXP"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return bf && v == 1 && s.E <= 256 && (long long)s.B * R * s.E % 8 == 0;
+    return bf && lxo_switch(SW_ATT_EXP) && s.E <= 256 && (long long)s.B * R * s.E % 8 == 0;
 }
 // tf.nn.dropout(., config.dropout) masks of one decoder step (attention_cell.py:72,83)
 bool Plan::pool_fused() const {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("LXO_POOL_FUSED"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    static int halo = -1;                                 // the A/B switches that select the older conv kernels (no fused pool there)
-    if (halo < 0) { const char* b2 = getenv("LXO_CONV_2WG"); halo = (b2 && b2[0] == '0') ? 0 : 1; }
-    return bf && v == 1 && halo == 1 && s.C % 128 == 0;
+    // LXO_CONV_2WG=0 selects the older conv kernels (no fused pool there): the conv launcher reads the same table entry
+    return bf && lxo_switch(SW_POOL_FUSED) && lxo_switch(SW_CONV_2WG) && s.C % 128 == 0;
 }
 Drop Plan::drop(int t, int row0) const {
     Drop d = {0u, 1.f, (unsigned)s.dropout_seed, t, row0, s.B};

@@ -17,6 +17,7 @@
 #include "rstep.h"
 #include "drop.h"
 #include "api_util.h"
+#include "switches.h"
 
 namespace {
 
@@ -322,9 +323,7 @@ int launch_ch(const RStep& p, hipStream_t st) {
     const bool half = ((long long)ncol * cdiv(p.M, 64) <= 128 && p.M > 32) || (p.M > 64 && p.M <= 512);
     // ... and 16-row tiles when even 32-row tiles leave half the CUs idle (o projection, att_h, the LSTM backward: 64 workgroups):
     // a workgroup's fetch -- the length of these kernels -- shrinks with its A tile
-    static int q16 = -1;
-    if (q16 < 0) { const char* e = getenv("LXO_RSTEP_MT16"); q16 = (e && e[0] == '0') ? 0 : 1; }
-    const bool quarter = q16 && (long long)ncol * cdiv(p.M, 32) <= 128 && p.M > 16;
+    const bool quarter = lxo_switch(SW_RSTEP_MT16) && (long long)ncol * cdiv(p.M, 32) <= 128 && p.M > 16;
     if (kq % K0 == 0) {
         if (quarter) return launch_nch<AT, WT, EPI, 16, K0>(p, dim3(ncol, cdiv(p.M, 16)), st);
         if (half) return launch_nch<AT, WT, EPI, 32, K0>(p, dim3(ncol, cdiv(p.M, 32)), st);

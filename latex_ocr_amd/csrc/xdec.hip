@@ -24,7 +24,7 @@
 #include "xdec.h"
 #include "drop.h"
 #include "api_util.h"
-#include <stdlib.h>
+#include "switches.h"
 
 #ifdef LXO_HIPSIM
 // tests/hipsim interprets one workgroup after the other: a kernel whose workgroups wait for each other cannot run there
@@ -895,8 +895,7 @@ int xdec_launch(const P& p, hipStream_t st) {
 }
 
 template <int NB>
-int launch_nb(const XDecFwd& p, int att_u, hipStream_t st) {
-    (void)att_u;
+int launch_nb(const XDecFwd& p, hipStream_t st) {
     return p.att_exp ? xdec_launch<xdec_fwd_kernel<NB, 4, true>>(p, st) : xdec_launch<xdec_fwd_kernel<NB, 4, false>>(p, st);
 }
 
@@ -1621,12 +1620,11 @@ int launch_bwd_nb(const XDecBwd& p, hipStream_t st) {
 }  // namespace
 
 // What the three launchers ask alike.  Returns NB = B / 8 (1, 2, 4 or 8), or 0: the shape does not qualify or the chain is switched off, and
-// the launcher answers -2.  `on` is the launcher's own cached switch: LXO_XDEC=0 sends everything to the launch-per-step kernels, the launcher's
-// `own` variable (null: none) set to 0 that chain alone (A/B runs).  Only the shipped sizes run here, in chains of 1, 2, 4 or 8 samples with
+// the launcher answers -2.  LXO_XDEC=0 sends everything to the launch-per-step kernels, the launcher's
+// `own` switch (SW_XDEC: none) set to 0 that chain alone (A/B runs).  Only the shipped sizes run here, in chains of 1, 2, 4 or 8 samples with
 // attention chunks of 1 .. rows_max rows, and the chain needs 8 XCDs x 32 CUs (MI355X).
-static int xdec_gate(int& on, const char* own, int U, int O, int C, int E, int B, int R, int rows_max) {
-    if (on < 0) { const char* e = own ? getenv(own) : nullptr; const char* f = getenv("LXO_XDEC"); on = ((e && e[0] == '0') || (f && f[0] == '0')) ? 0 : 1; }
-    if (!on) return 0;
+static int xdec_gate(LxoSwitch own, int U, int O, int C, int E, int B, int R, int rows_max) {
+    if (!lxo_switch(SW_XDEC) || !lxo_switch(own)) return 0;
     if (U != XU || O != XO || C != XC || E != XE) return 0;
     if (B % 8 != 0 || B > 64) return 0;
     const int nb = B / 8;
@@ -1646,8 +1644,7 @@ extern "C" int lxo_xdec_debug(unsigned long long* buf) { g_xdbg = buf; return 0;
 int lxo_launch_xdec_fwd(const XDecFwd& p0, int U, int O, int C, int E, hipStream_t st) {
     XDecFwd p = p0;
     p.dbg = g_xdbg;
-    static int on = -1;
-    const int nb = xdec_gate(on, nullptr, U, O, C, E, p.B, p.R, SCMAX);       // (the raw scores of a chunk stay in LDS)
+    const int nb = xdec_gate(SW_XDEC, U, O, C, E, p.B, p.R, SCMAX);       // (the raw scores of a chunk stay in LDS)
     if (!nb || p.T < 1) return -2;
     if ((long long)p.B * p.RECB * 2 >= (1LL << 31) || p.ldrt % 8 || p.ldah % 8 || p.ldow % 8 || p.RECB % 8) return -2;
     HIPRC(hipMemsetAsync(p.sync, 0, kXDecBlockBytes, st));
@@ -1655,21 +1652,16 @@ int lxo_launch_xdec_fwd(const XDecFwd& p0, int U, int O, int C, int E, hipStream
 
     // rows per wave and block (two blocks in flight).  4: the largest count whose two blocks + the resident weights fit the register file
     // without spills (5 .. 7 spill 68 .. 208 bytes per lane into the serial phases and lose more there than their fewer padded rows gain:
-    // 23.9 / 28.9 / 28.3 us per step against 22.2, profiles/r04_xdec_stamps_v2.txt).  LXO_XDEC_U = 4 .. 7 forces one (measurement).
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("LXO_XDEC_U"); forced = e ? atoi(e) : 0; }
-    int att_u = 4;
-    if (forced >= 4 && forced <= 7) att_u = forced;
+    // 23.9 / 28.9 / 28.3 us per step against 22.2, profiles/r04_xdec_stamps_v2.txt).
     switch (nb) {
-    case 1: return launch_nb<1>(p, att_u, st);
-    case 2: return launch_nb<2>(p, att_u, st);
-    case 4: return launch_nb<4>(p, att_u, st);
-    default: return launch_nb<8>(p, att_u, st);
+    case 1: return launch_nb<1>(p, st);
+    case 2: return launch_nb<2>(p, st);
+    case 4: return launch_nb<4>(p, st);
+    default: return launch_nb<8>(p, st);
     }
 }
 int lxo_launch_xdec_dec(const XDecDec& p, int U, int O, int C, int E, hipStream_t st) {
-    static int on = -1;
-    const int nb = xdec_gate(on, "LXO_XDEC_DEC", U, O, C, E, p.B, p.R, 1 << 30);     // (no raw scores are kept: any chunk length)
+    const int nb = xdec_gate(SW_XDEC_DEC, U, O, C, E, p.B, p.R, 1 << 30);     // (no raw scores are kept: any chunk length)
     if (!nb || p.nsteps < 1 || p.nsteps > 16 || p.V < 1 || p.V > 512 || !p.stop) return -2;      // 32 workgroups x 16 vocabulary columns; one counter word per step and launch
     if ((long long)p.B * p.RECB * 2 >= (1LL << 31) || p.ldrt % 8 || p.ldah % 8 || p.ldow % 8 || p.ldyo % 8 || p.RECB % 8 || !p.att_exp) return -2;
     // tickets / flags and the hand-over area, but NOT the error word (int 512): an error of an earlier launch of this decode stays visible
@@ -1689,8 +1681,7 @@ extern "C" int lxo_xdec_debug_bwd(unsigned long long* buf) { g_xdbg_b = buf; ret
 int lxo_launch_xdec_bwd(const XDecBwd& p0, int U, int O, int C, int E, hipStream_t st) {
     XDecBwd p = p0;
     p.dbg = g_xdbg_b;
-    static int on = -1;
-    const int nb = xdec_gate(on, "LXO_XDEC_BWD", U, O, C, E, p.B, p.R, SCMAX);       // (the forward chain must have run the same shape)
+    const int nb = xdec_gate(SW_XDEC_BWD, U, O, C, E, p.B, p.R, SCMAX);       // (the forward chain must have run the same shape)
     if (!nb || p.T < 1) return -2;
     if (p.ldow % 8 || p.ldah % 8 || p.ldk % 8 || p.GBP % 8 || p.DZBP % 8 || p.REC % 4 || (long long)p.B * p.DZBP * 2 >= (1LL << 31)) return -2;
     HIPRC(hipMemsetAsync(p.sync, 0, kXDecBlockBytes, st));

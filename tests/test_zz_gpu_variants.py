@@ -11,8 +11,6 @@ mathematics with different kernels, so they must agree far more tightly than eit
   (LXO_GEMM_TN_TR=0): summation order;
 * dense projections (att_img, logits, d_o) with LDS-DMA staging (default)  vs  the register-staged kernel
   (LXO_GEMM_NT_DMA=0): the same products in the same order per output element;
-* forward attention as part + combine (default)  vs  scores kernel + softmax-context kernel without a merge launch
-  (LXO_ATT_SPLIT=1): summation order;
 * fused recurrent-step kernels (default)  vs  round 1's split-K kernels (step_kernels = 1);
 * the two-workgroup conv kernel with fused pools (default)  vs  the general halo conv kernel + separate pools (LXO_CONV_2WG=0: the
   kernel that shapes outside the model's -- Cout % 64 != 0, tensors of 2 GB and more -- run on);
@@ -63,11 +61,8 @@ def test_kernel_generations_agree(tmp_path, h, w):
             ("att_forward_only", {"LXO_ATT_ALT": "0"}, (1e-5, 0.99999, 1e-2)),
             ("tn_packing_kernel", {"LXO_GEMM_TN_TR": "0"}, (1e-5, 0.99999, 1e-2)),
             ("nt_register_staged", {"LXO_GEMM_NT_DMA": "0"}, (1e-5, 0.99999, 1e-2)),
-            ("att_scores_then_context", {"LXO_ATT_SPLIT": "1"}, (1e-5, 0.99999, 1e-2)),
             ("split_k_steps", {"LXO_STEP_KERNELS": "1"}, (1e-4, 0.9995, 5e-2)),
             ("fused_step_launches", {"LXO_STEP_KERNELS": "2"}, (1e-4, 0.9995, 5e-2)),
-            # attention backward with two row blocks in flight (off by default: measured slower): the same sums in another order
-            ("att_bwd_two_blocks_in_flight", {"LXO_ATT_BWD2": "1"}, (1e-5, 0.99999, 1e-2)),
             # the general halo conv kernel (what Cout % 64 != 0 or a tensor of 2 GB and more runs on) for every layer; no fused pools there
             ("general_halo_conv", {"LXO_CONV_2WG": "0"}, (1e-4, 0.9995, 5e-2)),
             # 128-channel conv tiles for every launch (the default gives a launch of fewer than 256 such tiles -- this batch of 4 -- 64-channel tiles): the

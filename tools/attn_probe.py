@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """Measurement aid: the forward attention launch pair (attn_fwd part + combine) of the benchmark shape
-(64 samples x 868 regions, E=256, C=512, bf16) in isolation, N back-to-back launches between two events.
-The env switches of csrc/decoder_kernels.hip (LXO_ATT_PIPE, LXO_ATT_U) select the variant."""
+(64 samples x 868 regions, E=256, C=512, bf16) in isolation, N back-to-back launches between two events."""
 import ctypes, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,4 +26,4 @@ best = 1e9
 for rep in range(5):
     e0.record(); run(200); e1.record(); torch.cuda.synchronize()
     best = min(best, e0.elapsed_time(e1) / 200 * 1e3)
-print("variant PIPE=%s ABL=%s U=%s: %.2f us per part+combine pair (back to back)" % (os.environ.get("LXO_ATT_PIPE", "1"), os.environ.get("LXO_ATT_ABL", "0"), os.environ.get("LXO_ATT_U", "8"), best))
+print("%.2f us per part+combine pair (back to back)" % best)

@@ -1,6 +1,5 @@
 """What the bf16 deterministic mode costs, launch family by launch family: one instrumented training step (HIP events around every conv / chain
-launch, lxo_timing_*) of the headline workload with Engine(deterministic=False) and (deterministic=True), plus free-running step times.
-The weight-gradient kernel's range spread comes from LXO_WG_STAGGER as usual (run the script once per value)."""
+launch, lxo_timing_*) of the headline workload with Engine(deterministic=False) and (deterministic=True), plus free-running step times."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -15,7 +14,6 @@ imgs, forms = synthetic.make_set(B, H, W, V, 30, 101, seed=1234)
 img = torch.from_numpy(pad_batch_images(imgs)).cuda()
 f, l = pad_batch_formulas(forms, V - 2, V - 1)
 f_d = torch.from_numpy(f).cuda()
-print("LXO_WG_STAGGER=%s" % os.environ.get("LXO_WG_STAGGER", "(default 10)"))
 for det in (False, True, False, True):
     eng = Engine(V, dtype="bf16", seed=0, deterministic=det)
     for _ in range(5):
