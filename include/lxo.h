@@ -396,7 +396,7 @@ int lxo_greedy_decode_prefix(const lxo_shape* s, const float* params, const void
  * is [B][allow_ld].  Bits at or beyond V are ignored.  The one rule: a banned vocabulary column behaves as a column outside the
  * vocabulary -- its logit is -inf before anything else happens in the select step.  So the arg-max runs over the allowed columns (ties:
  * the lower index) and logp_out (nullable) holds logit - logsumexp(allowed logits), the model's distribution renormalised over the set;
- * with every column allowed the outputs are those of lxo_greedy_decode_prefix / _scores.  The set is constant over the steps of a call.
+ * with every column allowed the outputs are those of lxo_greedy_decode_prefix / _scores.  The set is constant over the steps of a call (a set that follows the row's history: lxo_greedy_decode_grammar).
  * prefix / prefix_ld / prefix_len: as in lxo_greedy_decode_prefix, or all NULL / 0 for no prefix; a forced id is emitted as given, its
  * log-prob taken under the same renormalised distribution.  Contract: in every row id_end is allowed and at least one token is; no forced
  * prefix token is banned in its row.  The device reads defensively: a row that breaks the contract does not fault or hang (it may emit id 0
@@ -502,6 +502,58 @@ int lxo_beam_decode_constrained(const lxo_shape* s, const float* params, const v
                                 const uint32_t* allow, int allow_ld,
                                 const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
                                 int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out, int* steps_out, void* stream);
+
+/* ---- decode under a DELIMITER GRAMMAR: hypotheses that close what they open ------------------------------------------------
+ * A set that follows each decoder row's own history, on the device, inside the loop of the three decodes.  cls int8 [V] (device): 0 = a
+ * plain token, +q = an opener of delimiter kind q, -q = a closer of kind q, 1 <= q <= n_kinds <= 15; many tokens may share a kind; id_end
+ * must be class 0.  A row's state: a depth d in [0, D], D = max_depth <= LXO_GRAMMAR_MAX_DEPTH, and the stack of the d open kinds -- one
+ * state per image (greedy), per hypothesis slot (beam), per draw (sampling).  With r = max_iter - t the steps that can still follow step t,
+ * the grammar set G(state, t) of an unfinished row holds
+ *   a closer of kind q   iff d > 0 and the top of the stack is q,
+ *   id_end               iff d == 0,
+ *   an opener            iff d < D and [budget] r >= d + 2,
+ *   any other token      iff [budget] r >= d + 1,
+ * the [budget] conditions only with `budget` != 0.  With the budget d <= r holds before every step, so a row always has room to close
+ * everything and emit END by step max_iter; at r == d only the matching closer is left, or END at d == 0.  The effective set of step t is
+ * S_t = A & G(state, t), A the static set of the row's image (allow, or everything); a finished row has S_t = A and a frozen state.
+ * Everything the constrained calls do with A these calls do with S_t: arg-max, log-sum-exp, the beam's top-k and diversity rank, the
+ * sampler's cut-offs and draw, the returned log-probs; forced prefix steps too.  After the select of step t emitted id in a row that is
+ * still unfinished: an opener at d < D pushes its kind, a closer that matches the top pops, anything else (a mismatched closer, a closer at
+ * depth 0, an opener at depth D) leaves the state as it is -- no content faults.  A beam slot continues the state of its PARENT slot.
+ * Contract (checked by the caller, not by the device): A allows id_end and every closer; a prefix obeys the grammar at every forced step,
+ * budget included; for beam, slot 0's effective set at the first free step holds at least `beam` tokens.  Then, with budget set, every row /
+ * back-traced hypothesis / draw reaches END at or before step max_iter and its tokens up to that END are balanced and correctly nested. */
+#define LXO_GRAMMAR_MAX_DEPTH 32
+typedef struct lxo_grammar { const int8_t* cls; int n_kinds; int max_depth; int budget; } lxo_grammar;
+/* bytes of the device scratch a grammar call needs for `rows` decoder rows (B, B * beam, B * n); 0: rows < 1 or V < 1.  Not part of ws. */
+size_t lxo_grammar_scratch_bytes(int rows, int V);
+/* lxo_greedy_decode_constrained / lxo_beam_decode_constrained / lxo_sample_decode under a grammar: their arguments (allow may be NULL with
+ * allow_ld 0: everything) plus the grammar, depth_out (nullable: int32, laid out as ids_out, the depth of the row after each step) and scratch
+ * (device, lxo_grammar_scratch_bytes of the call's decoder rows).  One small launch more per step; the greedy call runs the launch-per-step
+ * path in both dtypes (the persistent chain holds no grammar).  -1, before any launch: NULL grammar / cls, n_kinds outside 1 .. 15,
+ * max_depth outside 1 .. LXO_GRAMMAR_MAX_DEPTH, NULL scratch, and the set / prefix / option refusals of the calls they extend. */
+int lxo_greedy_decode_grammar(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                              const uint32_t* allow, int allow_ld, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                              const lxo_grammar* grammar, int32_t* ids_out, float* logp_out, float* alpha_out, int32_t* depth_out,
+                              void* scratch, int* steps_out, void* stream);
+int lxo_beam_decode_grammar(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                            const uint32_t* allow, int allow_ld, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                            const lxo_grammar* grammar, int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out,
+                            int32_t* depth_out, void* scratch, int* steps_out, void* stream);
+int lxo_sample_decode_grammar(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                              const lxo_sample_opts* opts, const uint32_t* allow, int allow_ld,
+                              const int32_t* prefix, int prefix_ld, const int32_t* prefix_len, const lxo_grammar* grammar,
+                              int32_t* ids_out, float* logp_out, float* logq_out, float* alpha_out, int32_t* depth_out, void* scratch,
+                              int* steps_out, void* stream);
+/* The grammar kernels alone, on ids the caller holds; the states live in scratch between calls.  rows decoder rows, rows_per_image of them
+ * per image (1 .. 16, a divisor of rows); allow: one row per image.  ids == NULL: the set-up launch -- class sets, states cleared, S_0.
+ * Else the step behind the select of step `time`: ids / finished int32 [rows] (device) as the select left them, parents (nullable) int32
+ * [rows] = the slot inside the row's image whose state the row continues; the states before step `time` are those the previous call left
+ * (set-up, or the step at time - 1).  Outputs (device, nullable): sets_out uint32 [rows][(V + 31) / 32] = S_0 / S_{time + 1} (pad bits 0),
+ * depth_out int32 [rows] (step only).  -1: the grammar and set refusals above, ids without finished; -5: the shape refusals. */
+int lxo_grammar_step(const lxo_grammar* grammar, int rows, int rows_per_image, int V, int id_end, const int32_t* ids, const int32_t* parents,
+                     const int32_t* finished, int time, int max_iter, const uint32_t* allow, int allow_ld, uint32_t* sets_out,
+                     int32_t* depth_out, void* scratch, void* stream);
 
 /* ---- data parallel: one process per GPU, RCCL over xGMI -------------------------------------
  * The reference trains on one device (one sess.run per step, model/img2seq.py:169).  Samples are independent through encoder,

@@ -32,6 +32,14 @@ class LxoSampleOpts(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("seed", ctypes.c_uint)]
 
 
+class LxoGrammar(ctypes.Structure):
+    """include/lxo.h lxo_grammar (cls: device int8 [V])"""
+    _fields_ = [("cls", c_void), ("n_kinds", c_int), ("max_depth", c_int), ("budget", c_int)]
+
+
+LXO_GRAMMAR_MAX_DEPTH = 32   # include/lxo.h
+
+
 def bind(lib):
     """Attach argtypes/restypes of every entry point of include/lxo.h."""
     S = P(LxoShape)
@@ -93,6 +101,11 @@ def bind(lib):
         "lxo_beam_decode_constrained": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_int, c_void, c_void, c_void, c_void, c_void, P(c_int), c_void]),
         "lxo_sample_decode": (c_int, [S, c_void, c_void, c_void, c_int, c_int, P(LxoSampleOpts), c_void, c_int, c_void, c_int, c_void, c_void, c_void, c_void, c_void, P(c_int), c_void]),
         "lxo_sample_tokens": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, P(LxoSampleOpts), c_void, c_int, c_void, c_void, c_void, c_void]),
+        "lxo_grammar_scratch_bytes": (c_size, [c_int, c_int]),
+        "lxo_greedy_decode_grammar": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_int, c_void, P(LxoGrammar), c_void, c_void, c_void, c_void, c_void, P(c_int), c_void]),
+        "lxo_beam_decode_grammar": (c_int, [S, c_void, c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_int, c_void, P(LxoGrammar), c_void, c_void, c_void, c_void, c_void, c_void, P(c_int), c_void]),
+        "lxo_sample_decode_grammar": (c_int, [S, c_void, c_void, c_void, c_int, c_int, P(LxoSampleOpts), c_void, c_int, c_void, c_int, c_void, P(LxoGrammar), c_void, c_void, c_void, c_void, c_void, c_void, P(c_int), c_void]),
+        "lxo_grammar_step": (c_int, [P(LxoGrammar), c_int, c_int, c_int, c_int, c_void, c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_void, c_void, c_void]),
         "lxo_chain_guard": (c_int, [S, c_void, c_void, c_void, c_int, c_void, c_void]),
         "lxo_decode_state_get": (c_int, [S, c_void, c_int, c_void, c_void, c_void, c_void]),
         "lxo_decode_state_set": (c_int, [S, c_void, c_int, c_void, c_void, c_void, c_void, c_void]),
@@ -125,7 +138,8 @@ ENTRY_POINTS = ["lxo_last_error", "lxo_version", "lxo_shape_size", "lxo_ws_regio
                 "lxo_param_total", "lxo_param_info", "lxo_wpack_bytes", "lxo_workspace_bytes", "lxo_ws_region",
                 "lxo_pack_weights", "lxo_encoder_fwd", "lxo_encoder_bwd", "lxo_encoder_bwd_ready", "lxo_train_bwd", "lxo_set_side_stream", "lxo_set_encoder_side_stream", "lxo_decoder_train_fwd",
                 "lxo_ce_loss_fwd_bwd", "lxo_ce_loss_fwd_bwd_dev", "lxo_ce_loss_weighted", "lxo_mrt_weights", "lxo_edit_distance", "lxo_mrt_candidates", "lxo_decoder_train_bwd", "lxo_decoder_train_bwd_part", "lxo_global_norm_scale", "lxo_adam_step", "lxo_optimizer_step",
-                "lxo_greedy_decode", "lxo_greedy_decode_attn", "lxo_beam_decode", "lxo_beam_decode_attn", "lxo_greedy_decode_scores", "lxo_beam_decode_scores", "lxo_score_tokens", "lxo_score_alternatives", "lxo_greedy_decode_prefix", "lxo_beam_decode_prefix", "lxo_greedy_decode_constrained", "lxo_beam_decode_constrained", "lxo_sample_decode", "lxo_sample_tokens", "lxo_decode_begin", "lxo_decode_step",
+                "lxo_greedy_decode", "lxo_greedy_decode_attn", "lxo_beam_decode", "lxo_beam_decode_attn", "lxo_greedy_decode_scores", "lxo_beam_decode_scores", "lxo_score_tokens", "lxo_score_alternatives", "lxo_greedy_decode_prefix", "lxo_beam_decode_prefix", "lxo_greedy_decode_constrained", "lxo_beam_decode_constrained", "lxo_sample_decode", "lxo_sample_tokens",
+                "lxo_grammar_scratch_bytes", "lxo_greedy_decode_grammar", "lxo_beam_decode_grammar", "lxo_sample_decode_grammar", "lxo_grammar_step", "lxo_decode_begin", "lxo_decode_step",
                 "lxo_chain_guard", "lxo_decode_state_get", "lxo_decode_state_set", "lxo_decode_cell_step",
                 "lxo_comm_unique_id", "lxo_comm_init", "lxo_comm_info", "lxo_allreduce_bucket", "lxo_comm_destroy", "lxo_comm_last_error"]
 

@@ -384,6 +384,88 @@ extern "C" int lxo_beam_decode_constrained(const lxo_shape* s, const float* para
     return 0;
 }
 
+// ---- decode under a delimiter grammar (grammar.h) ----
+#include "grammar.h"
+// the grammar of the _grammar calls and their optional static sets and prefix; what is refused, or null
+static const char* make_grammar(DecGrammar* dg, const lxo_grammar* g, int32_t* depth_out, void* scratch) {
+    if (!g || !g->cls) return "lxo_*_grammar: null grammar or cls";
+    if (g->n_kinds < 1 || g->n_kinds > kGrammarMaxKinds) return "lxo_*_grammar: n_kinds outside 1 .. 15";
+    if (g->max_depth < 1 || g->max_depth > LXO_GRAMMAR_MAX_DEPTH) return "lxo_*_grammar: max_depth outside 1 .. LXO_GRAMMAR_MAX_DEPTH";
+    if (!scratch) return "lxo_*_grammar: null scratch";
+    *dg = DecGrammar{g->cls, g->n_kinds, g->max_depth, g->budget ? 1 : 0, (unsigned*)scratch, depth_out};
+    return nullptr;
+}
+static const char* make_grammar_constraint(DecAllow* al, DecPrefix* pf, bool* has_prefix, int V, const uint32_t* allow, int allow_ld,
+                                           const int32_t* prefix, int prefix_ld, const int32_t* prefix_len, int max_iter) {
+    if (!allow && allow_ld != 0) return "lxo_*_grammar: null allow with allow_ld != 0";
+    if (allow) return make_constraint(al, pf, has_prefix, V, allow, allow_ld, prefix, prefix_ld, prefix_len, max_iter);
+    *has_prefix = prefix || prefix_len || prefix_ld != 0;
+    if (*has_prefix && !make_prefix(pf, prefix, prefix_ld, prefix_len, max_iter)) return "lxo_*_grammar: a prefix needs prefix, prefix_len and prefix_ld >= 1 (none: all NULL / 0)";
+    return nullptr;
+}
+extern "C" size_t lxo_grammar_scratch_bytes(int rows, int V) {
+    if (rows < 1 || V < 1) return 0;
+    return (size_t)lxo_k_grammar_scratch_words(rows, V) * sizeof(unsigned);
+}
+extern "C" int lxo_greedy_decode_grammar(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                         const uint32_t* allow, int allow_ld, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                         const lxo_grammar* grammar, int32_t* ids_out, float* logp_out, float* alpha_out, int32_t* depth_out,
+                                         void* scratch, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    DecAllow al; DecPrefix pf; DecGrammar dg; bool has_prefix = false;
+    if (const char* why = make_grammar(&dg, grammar, depth_out, scratch)) return fail(-1, why);
+    if (const char* why = make_grammar_constraint(&al, &pf, &has_prefix, P.s.V, allow, allow_ld, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, why);
+    const DecodeOuts o = {ids_out, nullptr, logp_out, alpha_out, has_prefix ? &pf : nullptr, allow ? &al : nullptr, &dg};
+    CHECK_LAUNCH(lxo_impl_greedy_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_greedy_decode_grammar");
+    return 0;
+}
+extern "C" int lxo_beam_decode_grammar(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                       const uint32_t* allow, int allow_ld, const int32_t* prefix, int prefix_ld, const int32_t* prefix_len,
+                                       const lxo_grammar* grammar, int32_t* ids_out, int32_t* parents_out, float* scores_out, float* alpha_out,
+                                       int32_t* depth_out, void* scratch, int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    DecAllow al; DecPrefix pf; DecGrammar dg; bool has_prefix = false;
+    if (const char* why = make_grammar(&dg, grammar, depth_out, scratch)) return fail(-1, why);
+    if (const char* why = make_grammar_constraint(&al, &pf, &has_prefix, P.s.V, allow, allow_ld, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, why);
+    const DecodeOuts o = {ids_out, parents_out, scores_out, alpha_out, has_prefix ? &pf : nullptr, allow ? &al : nullptr, &dg};
+    CHECK_LAUNCH(lxo_impl_beam_decode(P, params, wpack, ws, id_end, max_iter, o, steps_out, (hipStream_t)stream), "lxo_beam_decode_grammar");
+    return 0;
+}
+extern "C" int lxo_sample_decode_grammar(const lxo_shape* s, const float* params, const void* wpack, void* ws, int id_end, int max_iter,
+                                         const lxo_sample_opts* opts, const uint32_t* allow, int allow_ld,
+                                         const int32_t* prefix, int prefix_ld, const int32_t* prefix_len, const lxo_grammar* grammar,
+                                         int32_t* ids_out, float* logp_out, float* logq_out, float* alpha_out, int32_t* depth_out, void* scratch,
+                                         int* steps_out, void* stream) {
+    MAKE_PLAN(P, s);
+    DecSample so; DecAllow al; DecPrefix pf; DecGrammar dg; bool has_prefix = false;
+    if (const char* why = make_sample(&so, opts)) return fail(-1, why);
+    if (!ids_out) return fail(-1, "lxo_sample_decode_grammar: null ids_out");
+    if (const char* why = make_grammar(&dg, grammar, depth_out, scratch)) return fail(-1, why);
+    if (const char* why = make_grammar_constraint(&al, &pf, &has_prefix, P.s.V, allow, allow_ld, prefix, prefix_ld, prefix_len, max_iter)) return fail(-1, why);
+    const DecodeOuts o = {ids_out, nullptr, logp_out, alpha_out, has_prefix ? &pf : nullptr, allow ? &al : nullptr, &dg};
+    CHECK_LAUNCH(lxo_impl_sample_decode(P, params, wpack, ws, id_end, max_iter, so, o, logq_out, steps_out, (hipStream_t)stream), "lxo_sample_decode_grammar");
+    return 0;
+}
+extern "C" int lxo_grammar_step(const lxo_grammar* grammar, int rows, int rows_per_image, int V, int id_end, const int32_t* ids,
+                                const int32_t* parents, const int32_t* finished, int time, int max_iter, const uint32_t* allow, int allow_ld,
+                                uint32_t* sets_out, int32_t* depth_out, void* scratch, void* stream) {
+    DecGrammar dg;
+    if (const char* why = make_grammar(&dg, grammar, depth_out, scratch)) return fail(-1, why);
+    if (V < 1 || rows < 1 || rows_per_image < 1 || rows_per_image > 16 || rows % rows_per_image != 0 || time < 0 || max_iter < 0)
+        return fail(-5, "lxo_grammar_step: V < 1, rows < 1, rows_per_image outside 1 .. 16 or no divisor of rows, time < 0 or max_iter < 0");
+    if (!allow && allow_ld != 0) return fail(-1, "lxo_grammar_step: null allow with allow_ld != 0");
+    if (allow && (allow_ld < 0 || (allow_ld != 0 && allow_ld < (V + 31) / 32))) return fail(-1, "lxo_grammar_step: allow_ld must be 0 or >= (V + 31) / 32");
+    if (ids && !finished) return fail(-1, "lxo_grammar_step: ids without finished");
+    const GrammarArgs a = {dg.cls, dg.n_kinds, dg.max_depth, dg.budget, allow, allow_ld, dg.scratch, rows, rows_per_image, V, id_end, max_iter};
+    hipStream_t st = (hipStream_t)stream;
+    if (!ids) CHECK_LAUNCH(lxo_k_grammar_setup(a, st), "lxo_grammar_step");
+    else CHECK_LAUNCH(lxo_k_grammar_step(a, ids, parents, finished, time, depth_out, 1, 0, st), "lxo_grammar_step");
+    if (sets_out)
+        CHECK_LAUNCH((int)hipMemcpyAsync(sets_out, lxo_k_grammar_sets(a), (size_t)rows * ((V + 31) / 32) * sizeof(unsigned), hipMemcpyDeviceToDevice, st),
+                     "lxo_grammar_step");
+    return 0;
+}
+
 extern "C" int lxo_conv3x3(int dt, const void* in, const void* wpk, const float* bias, void* out, int B, int H, int W,
                            int Cin, int Ho, int Wo, int Cout, int pad, int relu, void* stream) {
     GemmNT g; memset(&g, 0, sizeof(g));

@@ -22,8 +22,9 @@ int lxo_k_score(int dt, const float* logits, const int* formula, const int* leng
 // steps t < len[r]; lim = min(ld, max_iter) bounds a length (head_kernels.hip: how out-of-range values are read)
 struct DecPrefix { const int* ids; const int* len; int ld; int lim; };
 // Allowed-token sets (lxo_greedy_decode_constrained / lxo_beam_decode_constrained), device bit sets: bit v & 31 of word v >> 5 of row b set = image b
-// may emit token v; ld words per row, 0 = one row shared by every image.  A banned column is read as a column outside the vocabulary
-struct DecAllow { const unsigned* bits; int ld; };
+// may emit token v; ld words per row, 0 = one row shared by every image.  A banned column is read as a column outside the vocabulary.
+// per_row != 0 (a grammar call, grammar.h): one row per DECODER ROW -- beam slot b * k + j, draw b * n + j -- instead of one per image
+struct DecAllow { const unsigned* bits; int ld; int per_row; };
 // alternatives per position of the same logits: ids_out / logp_out [B][T][k] = the k first columns of row t * B + b (value descending, then column
 // ascending) and logits[id] - lse, rank_out [B][T] (nullable) = the columns in front of the clamped target, ent_out [B][T] (nullable) = sum p (lse - x);
 // allow (nullable): one row per sample b, everything then runs over its allowed columns (banned target: rank -1; no column left: -1 / -inf);

@@ -19,6 +19,10 @@ LXO_DEV int pfx_id(const DecPrefix& q, int r, int t, int V) { const int f = q.id
 // Allowed-token sets (AL instantiations, DecAllow in head_kernels.h): a banned column is a column outside the vocabulary -- its logit is
 // -inf before anything else happens in the select step.  The words of a row are read inside [0, (V + 31) / 32): nothing faults on any content.
 LXO_DEV const unsigned* alw_row(const DecAllow& q, int r) { return q.bits + (long long)r * q.ld; }
+// the set of decoder row `row` of image b: the image's, or under a grammar the row's own
+LXO_DEV const unsigned* alw_row(const DecAllow& q, int b, int row) { return q.bits + (long long)(q.per_row ? row : b) * q.ld; }
+// beam kernels: words between the sets of an image's consecutive hypothesis slots (0: they share the image's set)
+LXO_DEV long long alw_slot_stride(const DecAllow& q) { return q.per_row ? q.ld : 0; }
 LXO_DEV bool alw_ok(const unsigned* row, int v) { return (row[v >> 5] >> (v & 31)) & 1u; }
 
 // Register row (Vp <= 64 * KV): 16-byte loads, a lane owns 4 consecutive columns per quarter of KV; the load is unconditional (clamped) and a
@@ -824,7 +828,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
     const int b = row / so.n, j = row - b * so.n;
     const float* lg = logits + (long long)row * Vp;
     const unsigned* ar = nullptr;
-    if constexpr (AL) ar = alw_row(al, b);
+    if constexpr (AL) ar = alw_row(al, b, row);
     int fi = -1;
     if constexpr (PF) { if (time < pfx_len(pf, b)) fi = pfx_id(pf, b, time, V); }
     float x[KV];
@@ -859,7 +863,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
     const int b = row / so.n, j = row - b * so.n;
     const float* lg = logits + (long long)row * Vp;
     const unsigned* ar = nullptr;
-    if constexpr (AL) ar = alw_row(al, b);
+    if constexpr (AL) ar = alw_row(al, b, row);
     int fi = -1;
     if constexpr (PF) { if (time < pfx_len(pf, b)) fi = pfx_id(pf, b, time, V); }
     float xmax; int xi;
@@ -892,6 +896,7 @@ struct DivPen { float log_gamma; unsigned thr; unsigned seed; float* scratch; };
 // over slot 0 alone (what time 0 does without a prefix), later steps over all k V candidates.
 // AL (both beam kernels): the log-sum-exp runs over image b's allowed columns; a banned candidate (slot, token) scores -inf, also for a finished
 // hypothesis, and is never selected while an allowed one is left; the diversity rank of an allowed column counts the allowed columns ahead of it.
+// Under a grammar (DecAllow::per_row) every hypothesis slot j has its own set, ar + j * as; else as == 0 and the slots share the image's.
 template <bool PF, bool AL>
 __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logits, int Vp, int V, int k, int id_end, int time, DivPen dp,
                                                        float* __restrict__ logp, int* __restrict__ finished,
@@ -903,11 +908,11 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
     __shared__ float sel_v[16]; __shared__ int sel_i[16];
     __shared__ int fin_old[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned* ar = nullptr;
-    if constexpr (AL) ar = alw_row(al, b);
+    const unsigned* ar = nullptr; long long as = 0;          // AL: the set of slot j is ar + j * as
+    if constexpr (AL) { ar = alw_row(al, b, b * k); as = alw_slot_stride(al); }
     // log-sum-exp per beam (one wave per beam, round-robin)
     for (int j = wave; j < k; j += 4) {
-        const float s = strided_lse<AL>(logits + ((long long)b * k + j) * Vp, lane, V, ar);
+        const float s = strided_lse<AL>(logits + ((long long)b * k + j) * Vp, lane, V, ar + j * as);
         if (lane == 0) lse[j] = s;
     }
     if (tid < k) fin_old[tid] = finished[b * k + tid];
@@ -932,7 +937,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
         float* row0 = logits + (long long)b * k * Vp;
         for (int i = tid; i < k * V; i += 256) {            // scores of every hypothesis, in place of its logits
             const int j = i / V, c = i - j * V;
-            row0[j * Vp + c] = cand_score<AL>(row0[j * Vp + c], lse[j], fin_old[j], logp[b * k + j], c, id_end, ar);
+            row0[j * Vp + c] = cand_score<AL>(row0[j * Vp + c], lse[j], fin_old[j], logp[b * k + j], c, id_end, ar + j * as);
         }
         __syncthreads();
         for (int i = tid; i < k * V; i += 256) {
@@ -943,7 +948,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
             for (int q = 0; q < V; ++q) { const float w = row[q]; rank += (w > v || (w == v && q < c)) ? 1 : 0; }
             const Drop dd = {dp.thr, 1.f, dp.seed, time, b * k + j, (int)gridDim.x * k};
             pen[j * Vp + c] = v + dp.log_gamma * (float)rank * drop_scale(dd, 3u, 0, c, V);
-            if constexpr (AL) { if (!alw_ok(ar, c)) pen[j * Vp + c] = -INFINITY; }
+            if constexpr (AL) { if (!alw_ok(ar + j * as, c)) pen[j * Vp + c] = -INFINITY; }
         }
         __syncthreads();
     }
@@ -955,7 +960,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* __restrict__ logi
             for (int q = 0; q < sel; ++q) taken |= (sel_i[q] == i);
             if (taken) continue;
             const float val = div ? pen[j * Vp + c]
-                                  : cand_score<AL>(logits[((long long)b * k + j) * Vp + c], lse[j], fin_old[j], logp[b * k + j], c, id_end, ar);
+                                  : cand_score<AL>(logits[((long long)b * k + j) * Vp + c], lse[j], fin_old[j], logp[b * k + j], c, id_end, ar + j * as);
             if (val > best || (val == best && i < bi)) { best = val; bi = i; }
         }
         shfl_argmax(best, bi);
@@ -997,8 +1002,8 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
     __shared__ float wc_v[BS_NW * 16]; __shared__ int wc_i[BS_NW * 16];      // the waves' k best each
     int t0 = 0;                                                // PF: the image's prefix length (beam_step_kernel)
     if constexpr (PF) t0 = pfx_len(pf, b);
-    const unsigned* ar = nullptr;                              // AL: the image's allowed-token bits
-    if constexpr (AL) ar = alw_row(al, b);
+    const unsigned* ar = nullptr; long long as = 0;           // AL: the allowed-token bits of slot j are ar + j * as
+    if constexpr (AL) { ar = alw_row(al, b, b * k); as = alw_slot_stride(al); }
     const int nb = time > t0 ? k : 1;
     const int total = nb * V;
     float raw[BS_NPT];                                         // raw logits of this thread's candidates (unconditional, clamped: requested before anything is waited for)
@@ -1015,12 +1020,12 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
     // log-sum-exp per hypothesis
     if (V <= 64 * 8 && k <= BS_NW) {
         // a wave takes hypothesis `wave` (a spare wave repeats the last one), the row in registers for its two passes
-        const float s = lane_row_lse<8, AL>(logits + ((long long)b * k + min(wave, k - 1)) * Vp, lane, V, ar);
+        const float s = lane_row_lse<8, AL>(logits + ((long long)b * k + min(wave, k - 1)) * Vp, lane, V, ar + min(wave, k - 1) * as);
         if (lane == 0 && wave < k) lse[wave] = s;
     } else
     for (int j = wave; j < k; j += BS_NW) {                   // the general form: one wave per hypothesis, round-robin
         const float* lg = logits + ((long long)b * k + j) * Vp;
-        const float s = V <= 64 * 16 ? lane_row_lse<16, AL>(lg, lane, V, ar) : strided_lse<AL>(lg, lane, V, ar);
+        const float s = V <= 64 * 16 ? lane_row_lse<16, AL>(lg, lane, V, ar + j * as) : strided_lse<AL>(lg, lane, V, ar + j * as);
         if (lane == 0) lse[j] = s;
     }
     if (tid < k) { fin_old[tid] = finished[b * k + tid]; lp_old[tid] = logp[b * k + tid]; }
@@ -1047,7 +1052,7 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
             const int j = jq, c = cq;
             cq += BS_TH;
             while (cq >= V) { cq -= V; ++jq; }
-            if (i < total) val[u] = cand_score<AL>(raw[u], lse[j], fin_old[j], lp_old[j], c, id_end, ar);
+            if (i < total) val[u] = cand_score<AL>(raw[u], lse[j], fin_old[j], lp_old[j], c, id_end, ar + j * as);
         }
     }
     // top-k in two stages, ONE workgroup barrier between them (it was two per selection): every wave selects the k best of ITS candidates by itself

@@ -20,7 +20,10 @@ int lxo_impl_decoder_train_bwd(const Plan& P, const float* prm, const void* wp, 
                                bool defer_join = false, void* ready = nullptr);
 // Where a whole-loop decode writes and what it is forced to emit (device arrays; all but ids nullable): scores = the token log-probs
 // (greedy) / the running log-probs (beam), alpha = the attention maps, prefix = forced ids, allow = the images' allowed-token sets (head_kernels.h).  Greedy has no parents.
-struct DecodeOuts { int* ids; int* parents; float* scores; float* alpha; const DecPrefix* prefix; const DecAllow* allow; };
+// grammar (nullable, the _grammar calls): the delimiter grammar of the call, its scratch and where the depths go (depth laid out as ids).  Under a
+// grammar `allow` stays the images' STATIC sets; the select kernels read the per-row sets the grammar kernel leaves in the scratch (grammar.h)
+struct DecGrammar { const signed char* cls; int n_kinds, max_depth, budget; unsigned* scratch; int* depth; };
+struct DecodeOuts { int* ids; int* parents; float* scores; float* alpha; const DecPrefix* prefix; const DecAllow* allow; const DecGrammar* grammar; };
 int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int max_iter, const DecodeOuts& out, int* steps_out, hipStream_t st);
 int lxo_impl_decode_begin(const Plan& P, const float* prm, const void* wp, void* ws, hipStream_t st);
 int lxo_impl_decode_step(const Plan& P, const float* prm, const void* wp, void* ws, int id_end, int time, int* ids_out, int* parents_out, int* finished_out, int* unfinished_host, hipStream_t st);

@@ -10,6 +10,7 @@
 #include "impl.h"
 #include "gemm.h"
 #include "head_kernels.h"
+#include "grammar.h"
 #include "rstep.h"
 #include "xdec.h"
 #include "dimg.h"
@@ -874,15 +875,42 @@ static int decode_keep_alpha(const Plan& P, const Dec& d, int time, const Decode
     if (o.alpha) HIPRC(hipMemcpyAsync(o.alpha + (size_t)time * d.nv * P.Rp, d.alpha, (size_t)d.nv * P.Rp * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
-static int decode_select(const Plan& P, const Dec& d, int id_end, int time, const DecodeOuts& o, int* unfinished, bool indirect, hipStream_t st) {
+// A grammar call (DecodeOuts::grammar, grammar.h): the arguments of the grammar kernels and `rows`, the per-row sets the select kernels read in place of
+// the images' static ones.  on == false: no grammar, the call runs what it ran before
+struct DecGram { bool on; GrammarArgs a; DecAllow rows; int* depth; };
+static DecGram decode_grammar(const Plan& P, const Dec& d, int id_end, int max_iter, const DecodeOuts& o) {
+    DecGram g; memset(&g, 0, sizeof(g));
+    if (!o.grammar) return g;
+    g.on = true;
+    g.a = GrammarArgs{o.grammar->cls, o.grammar->n_kinds, o.grammar->max_depth, o.grammar->budget, o.allow ? o.allow->bits : nullptr,
+                      o.allow ? o.allow->ld : 0, o.grammar->scratch, d.nv, d.k, P.s.V, id_end, max_iter};
+    g.rows = DecAllow{lxo_k_grammar_sets(g.a), (P.s.V + 31) / 32, 1};
+    g.depth = o.grammar->depth;
+    return g;
+}
+// the outputs as the select kernels take them: under a grammar `allow` names the per-row sets
+static DecodeOuts decode_outs(const DecodeOuts& o, const DecGram& g) {
+    DecodeOuts r = o;
+    if (g.on) r.allow = &g.rows;
+    return r;
+}
+// behind a select: the rows' states after step `time` and their sets of step time + 1 (beam: through the parents the select just wrote)
+static int decode_grammar_step(const Plan& P, const Dec& d, const DecGram& g, int time, hipStream_t st) {
+    if (!g.on) return 0;
+    return lxo_k_grammar_step(g.a, d.ids_step, d.beam ? d.par_step : nullptr, d.finished, time, g.depth, P.s.max_steps, time, st);
+}
+static int decode_select(const Plan& P, const Dec& d, int id_end, int time, const DecodeOuts& o, int* unfinished, bool indirect, hipStream_t st,
+                         const DecGram* g = nullptr) {
     const int ms = P.s.max_steps, U = P.s.U, nv = d.nv, cur = (time + 1) & 1;
     RC(decode_keep_alpha(P, d, time, o, st));
     if (!d.beam) {
         RC(lxo_k_argmax(d.logits, P.Vp, P.s.V, nv, id_end, d.ids_step, o.ids, ms, time, d.finished, unfinished, st, o.scores, o.prefix, o.allow));
+        if (g) RC(decode_grammar_step(P, d, *g, time, st));
         return 0;
     }
     RC(lxo_k_beam_step(d.logits, P.Vp, P.s.V, P.s.B, d.k, id_end, time, P.s.div_gamma, P.s.div_prob, P.s.div_seed, d.tmp, d.logp, d.finished,
                        d.ids_step, d.par_step, o.ids, o.parents, ms, unfinished, st, o.scores, o.prefix, o.allow));
+    if (g) RC(decode_grammar_step(P, d, *g, time, st));
     if (indirect) return 0;
     RC(lxo_k_beam_gather(d.rec + (size_t)cur * nv * P.REC, P.REC, P.XH, d.cs + (size_t)cur * nv * U, U, d.par_step, d.k,
                          d.tmp, d.tmp + (size_t)nv * P.XH, nv, d.recb ? d.recb + (size_t)cur * nv * P.RECB : nullptr, P.RECB, st));
@@ -896,7 +924,10 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
     RC(decode_check(P, 1, max_iter + 1, prefix, out.allow));
     const Dec d = dec_of(P, ws, 1, false);
     RC(decode_setup(P, prm, wp, ws, d, false, st));
-    if (d.path.try_chain && P.att_exp() && !out.alpha) {
+    const DecGram g = decode_grammar(P, d, id_end, max_iter, out);
+    const DecodeOuts og = decode_outs(out, g);
+    if (g.on) RC(lxo_k_grammar_setup(g.a, st));
+    if (d.path.try_chain && P.att_exp() && !out.alpha && !g.on) {      // the chain holds no grammar (as it holds no sampler): launch per step
         // the persistent greedy-decode chain (xdec.hip: xdec_dec_kernel): 16 steps per launch; -2 = the shape does not qualify
         XDecDec x; memset(&x, 0, sizeof(x));
         xdec_common(x, P, prm, wp, ws);
@@ -936,7 +967,7 @@ int lxo_impl_greedy_decode(const Plan& P, const float* prm, const void* wp, void
     } else if (P.bf) HIPRC(hipMemsetAsync(chain_block(P, ws, kChainFwd), 0, kXDecTicketBytes, st));
     return decode_loop_steps(max_iter, d.flags, st, steps_out, [&](int time, int* unfinished) -> int {
         RC(decode_common_step(P, prm, wp, ws, d, time, time == 0 ? nullptr : d.ids_step, st));
-        return decode_select(P, d, id_end, time, out, unfinished, false, st);
+        return decode_select(P, d, id_end, time, og, unfinished, false, st, &g);
     });
 }
 
@@ -948,11 +979,15 @@ int lxo_impl_sample_decode(const Plan& P, const float* prm, const void* wp, void
     RC(decode_check(P, n, max_iter + 1, out.prefix, out.allow));
     const Dec d = dec_of(P, ws, n, false);
     RC(decode_setup(P, prm, wp, ws, d, false, st));
+    const DecGram g = decode_grammar(P, d, id_end, max_iter, out);
+    const DecodeOuts og = decode_outs(out, g);
+    if (g.on) RC(lxo_k_grammar_setup(g.a, st));
     return decode_loop_steps(max_iter, d.flags, st, steps_out, [&](int time, int* unfinished) -> int {
         RC(decode_common_step(P, prm, wp, ws, d, time, time == 0 ? nullptr : d.ids_step, st));
         RC(decode_keep_alpha(P, d, time, out, st));
-        return lxo_k_sample(d.logits, P.Vp, P.s.V, d.nv, n, id_end, time, opts, d.ids_step, out.ids, out.scores, logq_out, P.s.max_steps, time,
-                            d.finished, unfinished, st, out.prefix, out.allow);
+        RC(lxo_k_sample(d.logits, P.Vp, P.s.V, d.nv, n, id_end, time, opts, d.ids_step, out.ids, out.scores, logq_out, P.s.max_steps, time,
+                        d.finished, unfinished, st, og.prefix, og.allow));
+        return decode_grammar_step(P, d, g, time, st);
     });
 }
 
@@ -1023,12 +1058,15 @@ int lxo_impl_beam_decode(const Plan& P, const float* prm, const void* wp, void* 
     RC(decode_check(P, P.s.beam, max_iter + 1, out.prefix, out.allow));
     const Dec d = dec_of(P, ws, P.s.beam, true);
     RC(decode_setup(P, prm, wp, ws, d, false, st));
+    const DecGram g = decode_grammar(P, d, id_end, max_iter, out);
+    const DecodeOuts og = decode_outs(out, g);
+    if (g.on) RC(lxo_k_grammar_setup(g.a, st));
     // the state of a step's rows is that of their PARENT hypotheses (beam_search_decoder_cell.py:176-178).  With the fused step kernels the next LSTM launch
     // reads its [o | h] and c rows through the parents in place; the launch that re-ordered the rows (beam_permute_kernel, 5.3 us + its gap) is only left for
     // the split-K step kernels and for lxo_decode_step, whose callers may look at the state between steps (LXO_BEAM_INDIRECT=0: always re-order; A/B)
     const bool indirect = lxo_switch(SW_BEAM_INDIRECT) && d.fused();
     return decode_loop_steps(max_iter, d.flags, st, steps_out, [&](int time, int* unfinished) -> int {
         RC(decode_common_step(P, prm, wp, ws, d, time, time == 0 ? nullptr : d.ids_step, st, indirect ? d.par_step : nullptr));
-        return decode_select(P, d, id_end, time, out, unfinished, indirect, st);
+        return decode_select(P, d, id_end, time, og, unfinished, indirect, st, &g);
     });
 }

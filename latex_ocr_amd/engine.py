@@ -1046,6 +1046,52 @@ class Engine(object):
         return (self._to_dev(np.ascontiguousarray(pf[rows], dtype=np.int32), torch.int32), int(pf.shape[1]),
                 self._to_dev(np.ascontiguousarray(ln[rows], dtype=np.int32), torch.int32))
 
+    def _grammar_host(self, grammar, id_end, max_iter, B0, al, prefix, prefix_lengths, beam_size):
+        """Checks a grammar call's contract before any launch (include/lxo.h): -> the Grammar bound to id_end.  END is a plain token; the static
+        sets allow every closer; a prefix obeys the grammar at every forced step, budget included; the effective set of the first free step
+        holds at least max(1, beam_size) tokens.  al / prefix: as _allow_host / _prefix_args have checked them."""
+        from .grammar import Grammar
+        if not isinstance(grammar, Grammar):
+            raise ValueError("grammar must be a latex_ocr_amd.grammar.Grammar, got %r" % type(grammar).__name__)
+        if grammar.n_tok != self.n_tok:
+            raise ValueError("the grammar classifies %d tokens, the vocabulary has %d" % (grammar.n_tok, self.n_tok))
+        if int(max_iter) < 0:
+            raise ValueError("max_iter = %d < 0" % int(max_iter))
+        g = grammar if grammar.id_end == int(id_end) else Grammar(grammar.cls, grammar.max_depth, grammar.budget, int(id_end))
+        g._check_end(id_end)
+        closers = g.cls < 0
+        if al is not None and not al[:, closers].all():
+            raise ValueError("allowed rows %s ban a closer of the grammar" % np.nonzero(~al[:, closers].all(1))[0].tolist())
+        pf = ln = None
+        if prefix is not None:
+            pf = np.asarray(prefix.detach().cpu().numpy() if isinstance(prefix, torch.Tensor) else prefix, dtype=np.int64)
+            ln = np.full(B0, pf.shape[1], np.int64) if prefix_lengths is None else np.asarray(
+                prefix_lengths.detach().cpu().numpy() if isinstance(prefix_lengths, torch.Tensor) else prefix_lengths, dtype=np.int64)
+        need = max(1, int(beam_size))
+        for b in range(B0):
+            state, P = (), int(ln[b]) if pf is not None else 0
+            for t in range(P):
+                tok = int(pf[b, t])
+                if not g.allowed_at(state, t, max_iter)[tok]:
+                    raise ValueError("prefix row %d breaks the grammar at step %d: token %d at depth %d with %d steps left"
+                                     % (b, t, tok, len(state), int(max_iter) - t))
+                state = g.apply(state, tok)
+            S = g.allowed_at(state, P, max_iter)
+            if al is not None:
+                S = S & al[b % al.shape[0]]
+            if S.sum() < need:
+                raise ValueError("row %d: the grammar leaves %d tokens at its first free step %d, fewer than max(1, beam_size) = %d"
+                                 % (b, int(S.sum()), P, need))
+        return g
+
+    def _grammar_args(self, g, rows, like):
+        """Stages a checked grammar: -> (lxo_grammar, depth int32 shaped like the ids tensor `like`, scratch, the class table kept alive)"""
+        cls = self._to_dev(g.cls, torch.int8)
+        nbytes = int(self.lib.lxo_grammar_scratch_bytes(int(rows), self.n_tok))
+        scratch = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.device)
+        depth = torch.zeros_like(like)
+        return _abi.LxoGrammar(_p(cls), g.n_kinds, g.max_depth, 1 if g.budget else 0), depth, scratch, cls
+
     def _alpha_buf(self, rows, img):
         """-> (the attention-map output buffer f32 [max_steps, rows, R padded to 8], R, H', W') of a decode over the features of `img`"""
         from .model.utils.image import encoder_out_hw
@@ -1061,10 +1107,14 @@ class Engine(object):
                     self._stream()), what)
         return steps.value
 
-    def _greedy_entry(self, pfx, ids, logp, alpha, alw=None):
+    def _greedy_entry(self, pfx, ids, logp, alpha, alw=None, gram=None):
         """The entry point for the outputs that are present: _scores refuses a null logp_out, _prefix a null prefix, _constrained a null set;
-        the plain call is bench.py's."""
+        the plain call is bench.py's.  gram (_grammar_args): the _grammar call, which takes every other argument as nullable."""
         L = self.lib
+        if gram is not None:
+            pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
+            aa = (_p(alw[0]), alw[1]) if alw is not None else (None, 0)
+            return L.lxo_greedy_decode_grammar, "greedy_decode_grammar", aa + pa + (ctypes.byref(gram[0]), _p(ids), _p(logp), _p(alpha), _p(gram[1]), _p(gram[2]))
         if alw is not None:
             pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
             return L.lxo_greedy_decode_constrained, "greedy_decode_constrained", (_p(alw[0]), alw[1]) + pa + (_p(ids), _p(logp), _p(alpha))
@@ -1076,7 +1126,8 @@ class Engine(object):
             return L.lxo_greedy_decode_attn, "greedy_decode_attn", (_p(ids), _p(alpha))
         return L.lxo_greedy_decode, "greedy_decode", (_p(ids),)
 
-    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False, prefix=None, prefix_lengths=None, allowed=None):
+    def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False, prefix=None, prefix_lengths=None, allowed=None,
+                      grammar=None, return_depth=False):
         """ids int32 [B, T'] as pred_test.ids of the greedy graph (decoder.py:64,70).  With return_attention also the
         attention maps alpha f32 [B, T', H', W'] (what the reference collects through its py_func hook,
         attention_mechanism.py:96-105, for visualize_attention.py).
@@ -1092,13 +1143,22 @@ class Engine(object):
         allowed: a token constraint (lxo_greedy_decode_constrained): a boolean / 0-1 array [V] (one set for the batch) or [B, V]; a token
         outside its image's set is never emitted -- the arg-max runs over the allowed columns and logp is renormalised over them (logit -
         logsumexp of the allowed logits).  Combines with the other arguments.  A ValueError before any launch for a wrong shape, END banned
-        in a row, no token allowed in a row, or a forced prefix token banned in its row."""
+        in a row, no token allowed in a row, or a forced prefix token banned in its row.
+        grammar: a latex_ocr_amd.grammar.Grammar (lxo_greedy_decode_grammar): every step's set is `allowed` cut to what the row's own history
+        leaves open -- no closer without its opener, no END while something is open and, with the grammar's budget, always room to close
+        everything by max_iter -- so every row ends balanced.  Combines with the other arguments; runs the launch-per-step kernels (the
+        persistent chain holds no grammar).  return_depth (with grammar): one more output, last: depth int32 [B, T'], the row's open
+        delimiters after each step.  A ValueError before any launch for a grammar of another vocabulary size, END not plain, a closer that
+        `allowed` bans, a prefix that breaks the grammar."""
+        if return_depth and grammar is None:
+            raise ValueError("return_depth needs grammar=")
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
-        Bp = B0 if return_attention else self._decode_chain_batch(B0)
+        Bp = B0 if return_attention or grammar is not None else self._decode_chain_batch(B0)
         al = self._allow_host(allowed, B0, id_end, 1) if allowed is not None else None
         pfx = self._prefix_args(prefix, prefix_lengths, B0, Bp, id_end, max_iter, al) if prefix is not None else None
+        g = self._grammar_host(grammar, id_end, max_iter, B0, al, prefix, prefix_lengths, 1) if grammar is not None else None
         alw = self._allow_args(al, B0, Bp) if al is not None else None
         if Bp != B0:
             img = self._to_dev(img, torch.uint8)
@@ -1107,12 +1167,15 @@ class Engine(object):
         ids = torch.zeros(B, self.max_steps, dtype=torch.int32, device=self.device)
         logp = torch.zeros(B, self.max_steps, dtype=torch.float32, device=self.device) if return_scores else None
         alpha, R, Hp, Wp = self._alpha_buf(B, img) if return_attention else (None, 0, 0, 0)
-        n = self._run_decode(self._greedy_entry(pfx, ids, logp, alpha, alw), id_end, max_iter)
+        gram = self._grammar_args(g, B, ids) if g is not None else None
+        n = self._run_decode(self._greedy_entry(pfx, ids, logp, alpha, alw, gram), id_end, max_iter)
         out = [ids[:B0, :n]]
         if return_attention:
             out.append(alpha[:n, :B0, :R].permute(1, 0, 2).reshape(B0, n, Hp, Wp))
         if return_scores:
             out.append(logp[:B0, :n])
+        if return_depth:
+            out.append(gram[1][:B0, :n])
         out = tuple(a.cpu().numpy() for a in out)
         return out if len(out) > 1 else out[0]
 
@@ -1194,9 +1257,13 @@ class Engine(object):
         Vp = (self.n_tok + 31) // 32 * 32
         return self.region("dec_logits", "f32", (self._dec_rows(), Vp))[:, :self.n_tok].cpu().numpy()
 
-    def _beam_entry(self, pfx, ids, par, sc, alpha, alw=None):
+    def _beam_entry(self, pfx, ids, par, sc, alpha, alw=None, gram=None):
         """The entry point for the outputs that are present (as _greedy_entry; _attn refuses a null alpha_out too)."""
         L = self.lib
+        if gram is not None:
+            pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
+            aa = (_p(alw[0]), alw[1]) if alw is not None else (None, 0)
+            return L.lxo_beam_decode_grammar, "beam_decode_grammar", aa + pa + (ctypes.byref(gram[0]), _p(ids), _p(par), _p(sc), _p(alpha), _p(gram[1]), _p(gram[2]))
         if alw is not None:
             pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
             return L.lxo_beam_decode_constrained, "beam_decode_constrained", (_p(alw[0]), alw[1]) + pa + (_p(ids), _p(par), _p(sc), _p(alpha))
@@ -1209,7 +1276,7 @@ class Engine(object):
         return L.lxo_beam_decode, "beam_decode", (_p(ids), _p(par))
 
     def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False,
-                    return_scores=False, prefix=None, prefix_lengths=None, allowed=None):
+                    return_scores=False, prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False):
         """ids int32 [B, T', k] as pred_test.ids of the beam graph before the transpose at img2seq.py:241.
         div_gamma / div_prob: add_div_penalty of beam_search_decoder_cell.py:258-287 (off at 1 / 0, the shipped values).
         return_attention: -> (ids, parents, alpha f32 [B, T', k, H', W']): alpha[b, t, j] = the map decoder row j of image b attended with at
@@ -1219,13 +1286,19 @@ class Engine(object):
         prefix / prefix_lengths: per image, as in greedy_decode (lxo_beam_decode_prefix): every slot takes the forced tokens, the beam search
         starts after them.
         allowed: per image, as in greedy_decode (lxo_beam_decode_constrained): log_softmax over the allowed columns, a banned candidate is
-        never selected, the diversity penalty ranks among the allowed columns.  Every row must allow at least beam_size tokens."""
+        never selected, the diversity penalty ranks among the allowed columns.  Every row must allow at least beam_size tokens.
+        grammar / return_depth: as in greedy_decode (lxo_beam_decode_grammar), one state per hypothesis slot, continued from the slot's parent:
+        every back-traced hypothesis ends balanced.  depth int32 [B, T', k] (last output; the parents are returned with it).  The first free
+        step must leave at least beam_size tokens."""
         self._check_beam(beam_size)
+        if return_depth and grammar is None:
+            raise ValueError("return_depth needs grammar=")
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
         al = self._allow_host(allowed, B0, id_end, beam_size) if allowed is not None else None
         pfx = self._prefix_args(prefix, prefix_lengths, B0, B0, id_end, max_iter, al) if prefix is not None else None
+        g = self._grammar_host(grammar, id_end, max_iter, B0, al, prefix, prefix_lengths, beam_size) if grammar is not None else None
         alw = self._allow_args(al, B0, B0) if al is not None else None
         B = self._encode_only(img, int(beam_size))
         self._set_diversity(div_gamma, div_prob, div_seed)
@@ -1233,14 +1306,17 @@ class Engine(object):
         par = torch.zeros(B, self.max_steps, beam_size, dtype=torch.int32, device=self.device)
         sc = torch.zeros(B, self.max_steps, beam_size, dtype=torch.float32, device=self.device) if return_scores else None
         alpha, R, Hp, Wp = self._alpha_buf(B * beam_size, img) if return_attention else (None, 0, 0, 0)
-        n = self._run_decode(self._beam_entry(pfx, ids, par, sc, alpha, alw), id_end, max_iter)
+        gram = self._grammar_args(g, B * int(beam_size), ids) if g is not None else None
+        n = self._run_decode(self._beam_entry(pfx, ids, par, sc, alpha, alw, gram), id_end, max_iter)
         out = [ids[:, :n]]
-        if return_parents or return_attention or return_scores:
+        if return_parents or return_attention or return_scores or return_depth:
             out.append(par[:, :n])
         if return_attention:
             out.append(alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
         if return_scores:
             out.append(sc[:, :n])
+        if return_depth:
+            out.append(gram[1][:, :n])
         out = tuple(a.cpu().numpy() for a in out)
         return out if len(out) > 1 else out[0]
 
@@ -1265,7 +1341,7 @@ class Engine(object):
         return _abi.LxoSampleOpts(temperature, top_k, top_p, int(seed) & 0xFFFFFFFF)
 
     def sample_decode(self, img, id_end, n=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, max_iter=151, return_scores=False, return_attention=False,
-                      prefix=None, prefix_lengths=None, allowed=None):
+                      prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False):
         """n independent DRAWS of the whole sequence per image (lxo_sample_decode): ids int32 [B, T', n].  Every step draws from the model's
         distribution at `temperature`, cut to the top_k most likely tokens (0: off) and then to the smallest set of renormalised mass >= top_p
         (1: off); temperature = 0 means top_k = 1, the arg-max.  Draw (b, j) depends only on seed, b, j and the step: the same seed repeats bit for
@@ -1274,22 +1350,30 @@ class Engine(object):
         greedy_decode's, renormalised over `allowed`), logq = its log-prob under the distribution it was drawn from (0 at a forced step); the
         sequence log-prob of a draw is the sum through its first END.  return_attention: alpha f32 [B, T', n, H', W'].
         prefix / prefix_lengths / allowed: per image, as in greedy_decode.  A ValueError before any launch for what greedy_decode refuses, n outside
-        1 .. min(16, V), temperature < 0 or not finite, top_k < 0, top_p outside (0, 1]."""
+        1 .. min(16, V), temperature < 0 or not finite, top_k < 0, top_p outside (0, 1].
+        grammar / return_depth: as in greedy_decode (lxo_sample_decode_grammar), one state per draw: the cut-offs and the draw run over the
+        step's effective set, so every draw ends balanced.  depth int32 [B, T', n] (last output)."""
+        if return_depth and grammar is None:
+            raise ValueError("return_depth needs grammar=")
+        box = []
         ids, logp, logq, alpha, steps, geo = self._sample_device(img, id_end, n, temperature, top_k, top_p, seed, max_iter, return_scores, return_attention,
-                                                                 prefix, prefix_lengths, allowed)
+                                                                 prefix, prefix_lengths, allowed, grammar, box)
         B, n, R, Hp, Wp = geo
         out = [ids[:, :steps]]
         if return_attention:
             out.append(alpha[:steps, :, :R].reshape(steps, B, n, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
         if return_scores:
             out += [logp[:, :steps], logq[:, :steps]]
+        if return_depth:
+            out.append(box[0][:, :steps])
         out = tuple(a.cpu().numpy() for a in out)
         return out if len(out) > 1 else out[0]
 
     def _sample_device(self, img, id_end, n, temperature, top_k, top_p, seed, max_iter, return_scores=False, return_attention=False,
-                       prefix=None, prefix_lengths=None, allowed=None):
+                       prefix=None, prefix_lengths=None, allowed=None, grammar=None, depth_box=None):
         """sample_decode's checks and its lxo_sample_decode call, the outputs left on the device: -> (ids int32 [B, max_steps, n], logp, logq, alpha
-        (None where not asked for), the steps the loop ran -- the one number the host learns -- and (B, n, R, H', W') for the attention maps)"""
+        (None where not asked for), the steps the loop ran -- the one number the host learns -- and (B, n, R, H', W') for the attention maps).
+        grammar: lxo_sample_decode_grammar instead; its depth tensor int32 [B, max_steps, n] is appended to the list depth_box"""
         so = self._sample_opts(n, temperature, top_k, top_p, seed)
         n = int(n)
         if n > self.n_tok:                                             # the decode calls' shape limit (rows per image <= V); the select step alone has none
@@ -1299,6 +1383,7 @@ class Engine(object):
         B0 = int(img.shape[0])
         al = self._allow_host(allowed, B0, id_end, 1) if allowed is not None else None
         pfx = self._prefix_args(prefix, prefix_lengths, B0, B0, id_end, max_iter, al) if prefix is not None else None
+        g = self._grammar_host(grammar, id_end, max_iter, B0, al, prefix, prefix_lengths, 1) if grammar is not None else None
         alw = self._allow_args(al, B0, B0) if al is not None else (None, 0)
         B = self._encode_only(img, n)
         ids = torch.zeros(B, self.max_steps, n, dtype=torch.int32, device=self.device)
@@ -1306,6 +1391,14 @@ class Engine(object):
         logq = torch.zeros(B, self.max_steps, n, dtype=torch.float32, device=self.device) if return_scores else None
         alpha, R, Hp, Wp = self._alpha_buf(B * n, img) if return_attention else (None, 0, 0, 0)
         pa = (_p(pfx[0]), pfx[1], _p(pfx[2])) if pfx is not None else (None, 0, None)
+        if g is not None:
+            gram = self._grammar_args(g, B * n, ids)
+            if depth_box is not None:
+                depth_box.append(gram[1])
+            steps = self._run_decode((self.lib.lxo_sample_decode_grammar, "sample_decode_grammar",
+                                      (ctypes.byref(so), _p(alw[0]), alw[1]) + pa + (ctypes.byref(gram[0]), _p(ids), _p(logp), _p(logq), _p(alpha),
+                                                                                      _p(gram[1]), _p(gram[2]))), id_end, max_iter)
+            return ids, logp, logq, alpha, steps, (B, n, R, Hp, Wp)
         steps = self._run_decode((self.lib.lxo_sample_decode, "sample_decode",
                                   (ctypes.byref(so), _p(alw[0]), alw[1]) + pa + (_p(ids), _p(logp), _p(logq), _p(alpha))), id_end, max_iter)
         return ids, logp, logq, alpha, steps, (B, n, R, Hp, Wp)

@@ -251,6 +251,16 @@ class Img2SeqModel(BaseModel):
             m = m & mask(banned, False)
         return m[0] if m.shape[0] == 1 else m
 
+    def _grammar(self, grammar):
+        """grammar= of predict_batch / complete_batch / sample_batch: a latex_ocr_amd.grammar.Grammar, True for Grammar.latex(vocab), or
+        None / False for none -> {} or the Engine decodes' grammar keyword"""
+        if grammar is None or grammar is False:
+            return {}
+        if grammar is True:
+            from ..grammar import Grammar
+            grammar = Grammar.latex(self._vocab)
+        return {"grammar": grammar}
+
     def _decode(self, img, allowed=None):
         """pred_test.ids of the decode graph (decoder.py:60-70), shaped [B, k, T'] as after
         img2seq.py:238-241."""
@@ -285,7 +295,7 @@ class Img2SeqModel(BaseModel):
         perp = -np.exp(ce_words / float(n_words))
         return files, perp
 
-    def predict_batch(self, images, return_scores=False, banned=None, allowed=None, alternatives=0):
+    def predict_batch(self, images, return_scores=False, banned=None, allowed=None, alternatives=0, grammar=None):
         """Reference: model/img2seq.py:256-276.
         return_scores: -> (hyps, scores), scores[i][b] = (sequence log-prob, [log-prob of each token up to and including the first END]) of
         hypothesis hyps[i][b]; the sequence log-prob is the sum of the token log-probs.  Greedy: the hypotheses are the default call's.
@@ -301,12 +311,19 @@ class Img2SeqModel(BaseModel):
         token's rank and the step's entropy, under the same token sets.  They come from a SECOND, teacher-forced pass over the emitted
         tokens (Engine.score, one per hypothesis slot), not from the decode itself: at a near-tie the slot-0 token of that pass may
         differ from the emitted one, and in beam search the log-probs are the model's, not the (penalised) running scores the search
-        ranked by.  A path that ran into the length bound without END has no entry for an END it never emitted."""
+        ranked by.  A path that ran into the length bound without END has no entry for an END it never emitted.
+        grammar: a latex_ocr_amd.grammar.Grammar, or True for Grammar.latex(vocab) (Engine decodes with grammar=): every hypothesis closes the
+        delimiters it opens and ends inside the length bound.  Beam search then returns the back-traced hypotheses, as with return_scores: the
+        grammar holds along a hypothesis' own path, not along the per-step columns of the reference's read-out.  The alternatives of a
+        grammar call run under the static sets only."""
         sets = self._token_sets(len(images), banned, allowed)
+        gk = self._grammar(grammar)
         if alternatives:
-            return self._predict_scored(images, allowed=sets, alternatives=alternatives)
+            return self._predict_scored(images, allowed=sets, alternatives=alternatives, **gk)
         if return_scores:
-            return self._predict_scored(images, allowed=sets)
+            return self._predict_scored(images, allowed=sets, **gk)
+        if gk:
+            return self._predict_scored(images, allowed=sets, **gk)[0]
         fd = self._get_feed_dict(images, dropout=1)
         ids_eval = self._decode(fd["img"], sets)
         hyps = [[] for _ in range(ids_eval.shape[1])]
@@ -350,14 +367,15 @@ class Img2SeqModel(BaseModel):
                        + ((self._alt_entries(res[3], b, n),) if alternatives else ()))
         return out
 
-    def complete_batch(self, images, prefixes, return_scores=False, banned=None, allowed=None, alternatives=0):
+    def complete_batch(self, images, prefixes, return_scores=False, banned=None, allowed=None, alternatives=0, grammar=None):
         """Decode each image from a given prefix (Engine greedy_decode / beam_decode with prefix=): the prefixes are token-id lists or
         space-separated token strings (Vocab.form_prepro, as score_batch takes them, but no END is appended), one per image; "" or []
         decodes from the start.  config.decoding chooses greedy or beam search; beam hypotheses are the back-traced ones, as
         predict_batch(return_scores=True) returns them.  -> hyps (hyps[i][b]: hypothesis i of image b, its prefix included), or
         (hyps, scores) with return_scores, scores as in predict_batch (the forced tokens' log-probs included).
         banned / allowed: as in predict_batch ("and not that token again"); a prefix token must be allowed for its image.
-        alternatives = k > 0: -> (hyps, scores, alts) as in predict_batch (a second, teacher-forced pass; the forced tokens' positions included)."""
+        alternatives = k > 0: -> (hyps, scores, alts) as in predict_batch (a second, teacher-forced pass; the forced tokens' positions included).
+        grammar: as in predict_batch; the prefix itself must obey it (a ValueError otherwise)."""
         if len(images) != len(prefixes):
             raise ValueError("complete_batch: %d images but %d prefixes" % (len(images), len(prefixes)))
         prepro = self._vocab.form_prepro
@@ -366,10 +384,10 @@ class Img2SeqModel(BaseModel):
         pf = np.zeros((len(forms), max(1, int(ln.max()) if ln.size else 1)), np.int32)
         for b, f in enumerate(forms):
             pf[b, :len(f)] = f
-        out = self._predict_scored(images, pf, ln, self._token_sets(len(images), banned, allowed), alternatives=alternatives)
+        out = self._predict_scored(images, pf, ln, self._token_sets(len(images), banned, allowed), alternatives=alternatives, **self._grammar(grammar))
         return out if return_scores or alternatives else out[0]
 
-    def _predict_scored(self, images, prefix=None, prefix_lengths=None, allowed=None, alternatives=0):
+    def _predict_scored(self, images, prefix=None, prefix_lengths=None, allowed=None, alternatives=0, **gk):
         fd = self._get_feed_dict(images, dropout=1)
         cfg = self._config
         max_iter = getattr(cfg, "max_length_formula", 150) + 1
@@ -377,12 +395,12 @@ class Img2SeqModel(BaseModel):
         if getattr(cfg, "decoding", "greedy") == "beam_search":
             from .utils.text import beam_backtrace
             ids, par, sc = self.engine.beam_decode(fd["img"], id_end, cfg.beam_size, max_iter=max_iter, return_scores=True,
-                                                   prefix=prefix, prefix_lengths=prefix_lengths, allowed=allowed, **self._beam_kwargs())
+                                                   prefix=prefix, prefix_lengths=prefix_lengths, allowed=allowed, **dict(self._beam_kwargs(), **gk))
             ids, run = beam_backtrace(ids, par), beam_backtrace(sc, par)          # token paths and their running log-probs
             tok = np.diff(run, axis=1, prepend=0.0)
         else:
             ids, tok = self.engine.greedy_decode(fd["img"], id_end, max_iter=max_iter, return_scores=True, prefix=prefix,
-                                                 prefix_lengths=prefix_lengths, allowed=allowed)
+                                                 prefix_lengths=prefix_lengths, allowed=allowed, **gk)
             ids, tok = ids[:, :, None], tok[:, :, None]
         k = ids.shape[2]
         hyps, scores = [[] for _ in range(k)], [[] for _ in range(k)]
@@ -405,17 +423,18 @@ class Img2SeqModel(BaseModel):
             alts.append([self._alt_entries(alt, b, int(emitted[b, i])) for b in range(ids.shape[0])])
         return hyps, scores, alts
 
-    def sample_batch(self, images, n, temperature=1.0, top_k=0, top_p=1.0, seed=0, banned=None, allowed=None):
+    def sample_batch(self, images, n, temperature=1.0, top_k=0, top_p=1.0, seed=0, banned=None, allowed=None, grammar=None):
         """n sampled transcriptions per image (Engine.sample_decode), folded into their DISTINCT hypotheses: -> one dict per image,
         {"hypotheses": [{"text", "count", "logp": the model's sequence log-prob (sum of the token log-probs through END), "token_logp": [...]},
         ...] sorted by count, then log-prob, both descending, "agreement": top count / n}.  A hypothesis is a draw truncated at its first END; draws
         that agree share one entry (the log-probs of its first draw).  Agreement is a confidence: n draws that all say the same are a stronger
-        accept signal than the greedy path's mean token probability, and the top entry is the vote.  banned / allowed: as in predict_batch."""
+        accept signal than the greedy path's mean token probability, and the top entry is the vote.  banned / allowed / grammar: as in predict_batch
+        (under a grammar no draw is lost to an unbalanced formula)."""
         fd = self._get_feed_dict(images, dropout=1)
         max_iter = getattr(self._config, "max_length_formula", 150) + 1
         id_end = self._vocab.id_end
         ids, logp, _ = self.engine.sample_decode(fd["img"], id_end, n=n, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, max_iter=max_iter,
-                                                 return_scores=True, allowed=self._token_sets(len(images), banned, allowed))
+                                                 return_scores=True, allowed=self._token_sets(len(images), banned, allowed), **self._grammar(grammar))
         out = []
         for b in range(ids.shape[0]):
             seen = {}

@@ -13,7 +13,11 @@ entropy of the step and the model's K best tokens there with their log-probs (pr
 alternatives=K: for a decode they come from a second, teacher-forced pass over the emitted tokens); with --formula it combines with
 --ban / --allow-file, which then constrain the alternatives.  --sample N draws N transcriptions per image instead of decoding the best one
 (Img2SeqModel.sample_batch; --temperature T, --top-k K, --top-p P and --seed S shape and repeat the draws; combines with --ban /
---allow-file): one line with the agreement (top count / N), then one line per distinct hypothesis with its count and log-prob."""
+--allow-file): one line with the agreement (top count / N), then one line per distinct hypothesis with its count and log-prob.
+--balanced decodes under the delimiter grammar of the vocabulary (latex_ocr_amd.grammar.Grammar.latex: { }, \\left / \\right, \\begin{X} / \\end{X};
+--pairs "OPEN:CLOSE ..." names the pairs instead, each side a comma-separated token list): every hypothesis closes what it opens.  It
+combines with everything but --formula.  Without the flag, where the vocabulary has delimiters, a line "  balanced: yes / no" behind each
+printed hypothesis says whether it does."""
 import argparse
 
 import numpy as np
@@ -38,6 +42,8 @@ def main(argv=None):
     ap.add_argument("--top-k", type=int, default=0, help="--sample: draw among the K most likely tokens (0: off)")
     ap.add_argument("--top-p", type=float, default=1.0, help="--sample: draw among the smallest token set of mass >= P (1: off)")
     ap.add_argument("--seed", type=int, default=0, help="--sample: the same seed repeats the draws")
+    ap.add_argument("--balanced", action="store_true", help="decode under the delimiter grammar: every hypothesis closes what it opens")
+    ap.add_argument("--pairs", default=None, help='delimiter pairs "OPEN:CLOSE ..." (each side comma-separated tokens) instead of those read off the vocabulary')
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     if a.formula is not None and len(a.images) != 1:
@@ -62,6 +68,24 @@ def main(argv=None):
     if a.alternatives and not 1 <= a.alternatives <= min(16, vocab.n_tok):
         ap.error("--alternatives takes 1 .. min(16, vocabulary size)")
     alt = {"alternatives": a.alternatives} if a.alternatives else {}
+    from latex_ocr_amd.grammar import Grammar
+    try:
+        gram = Grammar.from_pairs(vocab, [tuple(side.split(",") for side in p.split(":", 1)) for p in a.pairs.split()]) if a.pairs \
+            else Grammar.latex(vocab)
+    except ValueError as e:
+        if a.balanced or a.pairs:
+            ap.error("--balanced / --pairs: %s" % e)
+        gram = None                                          # a vocabulary without delimiters: nothing to report
+    if a.balanced:
+        if a.formula is not None:
+            ap.error("--balanced constrains a decode and does not combine with --formula")
+        sets["grammar"] = gram
+    dec = dict(sets)                                         # the decodes' keywords; score_batch takes the token sets only
+    sets.pop("grammar", None)
+
+    def report(text):
+        if gram is not None and not a.balanced:
+            print("  balanced:", "yes" if gram.check([vocab.tok_to_id.get(t, vocab.id_unk) for t in text.split()] + [vocab.id_end]) else "no")
 
     def print_alternatives(tokens, logps, entries):
         for t, (tok, lp, e) in enumerate(zip(tokens, logps, entries)):
@@ -84,38 +108,42 @@ def main(argv=None):
             out.append(res)
             continue
         if a.sample:
-            res = model.sample_batch([greyscale(img)], a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, **sets)[0]
+            res = model.sample_batch([greyscale(img)], a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, **dec)[0]
             print(path, "~>", "%d draws\tagreement %.3f" % (a.sample, res["agreement"]))
             for h in res["hypotheses"]:
                 print("  %3d x  logp %9.4f  %s" % (h["count"], h["logp"], h["text"]))
+                report(h["text"])
             out.append(res)
             continue
         if a.prefix is not None:
-            res = model.complete_batch([greyscale(img)], [a.prefix], return_scores=True, **dict(alt, **sets))
+            res = model.complete_batch([greyscale(img)], [a.prefix], return_scores=True, **dict(alt, **dec))
             hyps, scores = res[:2]
             lp, toks = scores[0][0]
             if a.scores:
                 print(path, "=>", hyps[0][0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
             else:
                 print(path, "=>", hyps[0][0])
+            report(hyps[0][0])
             if alt:
                 print_alternatives(emitted(hyps[0][0], len(toks)), toks, res[2][0][0])
             out.append(([h[0] for h in hyps], [s[0] for s in scores]) + (([x[0] for x in res[2]],) if alt else ()) if a.scores or alt else [h[0] for h in hyps])
             continue
         if a.scores or alt:
-            res = model.predict_batch([greyscale(img)], return_scores=True, **dict(alt, **sets))
+            res = model.predict_batch([greyscale(img)], return_scores=True, **dict(alt, **dec))
             hyps, scores = [h[0] for h in res[0]], res[1]
             lp, toks = scores[0][0]
             if a.scores:
                 print(path, "=>", hyps[0], "\tlogp %.4f\tgeo-mean p %.4f" % (lp, np.exp(lp / max(1, len(toks)))))
             else:
                 print(path, "=>", hyps[0])
+            report(hyps[0])
             if alt:
                 print_alternatives(emitted(hyps[0], len(toks)), toks, res[2][0][0])
             out.append((hyps, [s[0] for s in scores]) + (([x[0] for x in res[2]],) if alt else ()))
             continue
-        hyps = [h[0] for h in model.predict_batch([greyscale(img)], **sets)] if sets else model.predict(greyscale(img))
+        hyps = [h[0] for h in model.predict_batch([greyscale(img)], **dec)] if dec else model.predict(greyscale(img))
         print(path, "=>", hyps[0])
+        report(hyps[0])
         out.append(hyps)
     return out
 

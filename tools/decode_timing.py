@@ -4,7 +4,8 @@ scores), interleaved over --reps rounds, for the A/B of the scored calls.  --pre
 with an N-token forced prefix on every row (prefix=, the decode still runs max_iter + 1 steps).  --ban N: the A/B of the calls without a
 constraint and with N random tokens banned in every row (allowed= as [B, V]: a set per image).  --sample N: sampled decode with N draws per image
 (Engine.sample_decode at temperature 1, then with top_k = 50 and top_p = 0.9) against beam N of the same tree, in alternating rounds; nothing else
-runs then."""
+runs then.  --grammar: greedy, beam 5 and sample 5 under a delimiter grammar (grammar=) against the same decode with a static set, both on the
+launch-per-step kernels, in alternating rounds: the cost of the grammar kernel per step; nothing else runs then."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -50,6 +51,34 @@ if "--sample" in sys.argv:
     for (name, _), v in zip(arms, per):
         v = sorted(v)
         print("%s: %d steps, us per step median of %d %.2f (%.2f..%.2f), ratio to beam %.4f" % (name, steps, reps, v[reps // 2], v[0], v[-1], v[reps // 2] / sorted(per[0])[reps // 2]))
+    sys.exit(0)
+
+if "--grammar" in sys.argv:
+    # the cost of the grammar kernel: greedy, beam 5 and sample 5 under a delimiter grammar against the same decode with a static set (every token
+    # allowed, one row per image), both on the launch-per-step path (step_kernels forced: a grammar call never takes the persistent chain)
+    import numpy as np
+    from latex_ocr_amd.grammar import Grammar
+    cls = np.zeros(V, np.int8)
+    for q in range(1, 6):                                   # five kinds, four openers and four closers each
+        cls[40 * q:40 * q + 4], cls[40 * q + 4:40 * q + 8] = q, -q
+    gram = Grammar(cls, max_depth=32, budget=True, id_end=V - 1)
+    every = torch.ones(B, V, dtype=torch.bool)
+    for kind, n in (("greedy", 1), ("beam", 5), ("sample", 5)):
+        eng = Engine(V, dtype="bf16", beam=n, max_steps=152)
+        eng.step_kernels = 2
+        call = {"greedy": lambda **kw: eng.greedy_decode(img, V - 1, max_iter=100, **kw),
+                "beam": lambda **kw: eng.beam_decode(img, V - 1, n, max_iter=100, **kw),
+                "sample": lambda **kw: eng.sample_decode(img, V - 1, n=n, seed=1, max_iter=100, **kw)}[kind]
+        arms = [("static set", lambda: call(allowed=every)), ("grammar", lambda: call(allowed=every, grammar=gram))]
+        for _, fn in arms: fn()
+        per, steps = [[], []], [0, 0]
+        for r in range(reps):
+            for i in ((0, 1) if r % 2 == 0 else (1, 0)):
+                dt, steps[i] = timed(arms[i][1])
+                per[i].append(dt * 1e6 / steps[i])
+        a, b = sorted(per[0]), sorted(per[1])
+        print("%s %d: us per step (median of %d, min..max)  static set %.2f (%.2f..%.2f, %d steps)  grammar %.2f (%.2f..%.2f, %d steps)  difference %.2f us  ratio %.4f"
+              % (kind, n, reps, a[reps // 2], a[0], a[-1], steps[0], b[reps // 2], b[0], b[-1], steps[1], b[reps // 2] - a[reps // 2], b[reps // 2] / a[reps // 2]))
     sys.exit(0)
 
 for beam in (1, 5):
