@@ -283,6 +283,33 @@ int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hyp_block_str
 int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
                        int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
                        int32_t* row_image, void* stream);
+/* Consensus (minimum-Bayes-risk choice) among n sampled transcriptions per image, on the device, shape-free: two launches, no host synchronisation,
+ * no atomics, capturable into a graph.
+ * DRAWS: draw i of image g starts at element g * image_stride + i * draw_stride of `ids` and its tokens lie tok_stride elements apart; its sequence
+ * s_i is the first T tokens cut at the first id_end (truncate_end's rule; id_end < 0: no cut).  The ids [B, max_steps, n] that lxo_sample_decode
+ * writes are read in place with image_stride max_steps * n, draw_stride 1, tok_stride n, T = the steps run; rows [B, n, T]: T * n, T, 1.
+ * THE DEFINITION:
+ *   dist[g][i][j] = Levenshtein(s_i, s_j): int32, exact, symmetric, 0 on the diagonal.
+ *   c(i, j) = (float)dist[g][i][j] / (float)max(|s_j|, 1) with normalize = 1 -- draw j plays the reference, one f32 division as lxo_edit_distance's
+ *     cost_out -- and (float)dist[g][i][j] with normalize = 0.
+ *   w_j = weights[g][j], device f32 [B][n]; NULL: every weight is 1.  A weight that is negative or not finite counts as 0; an image whose weights
+ *     (so read) sum to 0 gets all ones.
+ *   risk[g][i] = (sum_j w_j * c(i, j)) / (sum_j w_j): f32, every product and sum rounded on its own (no fused multiply-add), both sums added in
+ *     ascending j from 0.f, one final division.
+ *   best[g] = the smallest i whose stored risk[g][i] is the minimum: an f32 comparison of the values written, ties go to the lower draw index.
+ * With NULL weights and normalize = 0 every term and every partial sum is an integer below 2^24 (n <= 64 draws of <= 1024 tokens), so the sums are
+ * exact and risk[g][i] is the correctly rounded f32 quotient (float)(sum_j dist[g][i][j]) / (float)n: exact up to that one division.  Equal draws
+ * have equal rows of dist and so equal risks, bit for bit.  The distances are integer arithmetic and every float sum has a fixed order: the same
+ * bytes in every run.
+ * OUTPUTS (device, all NOT NULL): dist_out int32 [B][n][n] -- also the hand-over between the two launches; risk_out f32 [B][n] -- it holds the
+ * draws' lengths as scratch between the launches, its content is final after the second; best_out int32 [B].
+ * B == 0 launches nothing.  T == 0 or n == 1: dist and risk all 0, best 0.
+ * -1, with the reason in lxo_last_error and no output written: a NULL ids, dist_out, risk_out or best_out; B < 0; n outside
+ * 1 .. LXO_CONSENSUS_MAX_N; T outside 0 .. LXO_EDIT_MAX_REF; a negative stride; normalize other than 0 or 1; more than 2^31 - 16 pairs
+ * B * n * (n - 1) / 2. */
+#define LXO_CONSENSUS_MAX_N 64
+int lxo_consensus(const int32_t* ids, long long image_stride, long long draw_stride, long long tok_stride, int B, int n, int T, int id_end,
+                  const float* weights, int normalize, int32_t* dist_out, float* risk_out, int32_t* best_out, void* stream);
 /* Teacher-forced scoring, after lxo_decoder_train_fwd with the same shape and formula: per-token log-probs, the model's top-1 token per
  * position and per-sequence sums; reads ws region "logits", writes only the caller's outputs (device, [B, T] / [B]).
  * logp_out f32 [B, T] (NOT NULL): log_softmax(logits of step t)[formula[b][t]] for t < lengths[b], 0 after.

@@ -171,6 +171,19 @@ extern "C" int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int 
     CHECK_LAUNCH(lxo_k_mrt_candidates(a, (hipStream_t)stream), "lxo_mrt_candidates");
     return 0;
 }
+static_assert(LXO_CONSENSUS_MAX_N == kConsensusMaxN, "include/lxo.h and csrc/seqcost.h disagree on the number of draws");
+extern "C" int lxo_consensus(const int32_t* ids, long long image_stride, long long draw_stride, long long tok_stride, int B, int n, int T, int id_end,
+                             const float* weights, int normalize, int32_t* dist_out, float* risk_out, int32_t* best_out, void* stream) {
+    if (!ids || !dist_out || !risk_out || !best_out) return fail(-1, "lxo_consensus: null ids, dist_out, risk_out or best_out");
+    if (B < 0 || image_stride < 0 || draw_stride < 0 || tok_stride < 0) return fail(-1, "lxo_consensus: B or a stride negative");
+    if (n < 1 || n > LXO_CONSENSUS_MAX_N) return fail(-1, "lxo_consensus: n outside 1 .. LXO_CONSENSUS_MAX_N");
+    if (T < 0 || T > LXO_EDIT_MAX_REF) return fail(-1, "lxo_consensus: T outside 0 .. LXO_EDIT_MAX_REF (draws longer than the kernel's column limit)");
+    if (normalize != 0 && normalize != 1) return fail(-1, "lxo_consensus: normalize must be 0 or 1");
+    if ((long long)B * n * (n - 1) / 2 > 0x7ffffff0ll) return fail(-1, "lxo_consensus: B n (n - 1) / 2 pairs exceed one launch");
+    const ConsArgs a = {ids, weights, dist_out, risk_out, best_out, image_stride, draw_stride, tok_stride, B, n, T, id_end, normalize};
+    CHECK_LAUNCH(lxo_k_consensus(a, (hipStream_t)stream), "lxo_consensus");
+    return 0;
+}
 extern "C" int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
                                 float* logp_out, int32_t* top1_out, float* seq_out, void* stream) {
     MAKE_PLAN(P, s);

@@ -1,5 +1,5 @@
 // Launchers of the sequence-cost kernels (seqcost.hip): batched Levenshtein distance over token rows, and the candidate rows of a minimum-risk
-// step built on the device from sampled ids and references.
+// step built on the device from sampled ids and references, and the minimum-risk choice among an image's draws.
 #pragma once
 #include "lxo_common.h"
 
@@ -29,3 +29,16 @@ struct CandArgs {
     int B, max_steps, n, steps, Tr, id_end, id_pad, inc;
 };
 int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st);
+
+// The consensus among the draws of an image (lxo_consensus, include/lxo.h holds the definition): draw i of image g starts at element
+// g image_stride + i draw_stride of ids, its tokens tok_stride apart, T of them, cut at the first id_end.  Two launches, no host synchronisation:
+// the distances of the B n (n - 1) / 2 unordered pairs into both halves of dist [B][n][n] (and the draws' lengths into risk, as scratch), then per
+// image the risks, the diagonal and the arg-min.  T > kEditMaxRef, n > kConsensusMaxN or more waves than a grid holds: -2.
+constexpr int kConsensusMaxN = 64;
+struct ConsArgs {
+    const int* ids; const float* weights;
+    int* dist; float* risk; int* best;
+    long long image_stride, draw_stride, tok_stride;
+    int B, n, T, id_end, normalize;
+};
+int lxo_k_consensus(const ConsArgs& a, hipStream_t st);

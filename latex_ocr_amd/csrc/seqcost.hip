@@ -1,5 +1,6 @@
 // Sequence costs on the device: the batched Levenshtein distance (lxo_edit_distance) and the candidate rows of a minimum-risk step built from
-// sampled ids (lxo_mrt_candidates).  Integer arithmetic throughout: exact, and the same in every order.
+// sampled ids (lxo_mrt_candidates).  Integer arithmetic throughout: exact, and the same in every order.  On top of the distances, the
+// minimum-risk choice among the draws of an image (lxo_consensus): all pairwise distances, the expected cost of every draw, the arg-min.
 #include "seqcost.h"
 
 namespace {
@@ -22,14 +23,14 @@ LXO_DEV int cut_len(const int* p, long long stride, int len, int id_end, int lan
 // dependency cur[j] = min(t[j], cur[j - 1] + 1) unrolls to cur[j] = j + min_{k <= j} (t[k] - k): a min-plus prefix.  So a row costs one neighbour
 // exchange (prev of the column left of the strip), a serial prefix-min over the strip and one exclusive prefix-min scan over the 64 lanes.
 // Columns beyond the reference's n tokens compute values nobody reads (a cell depends on columns to its left only).
-// m hypothesis tokens at hp (stride hts), n <= 64 CPL reference tokens at rp -> the distance, in every lane.
+// m hypothesis tokens at hp (stride hts), n <= 64 CPL reference tokens at rp (stride rts) -> the distance, in every lane.
 template <int CPL>
-LXO_DEV int edit_wave(const int* hp, long long hts, int m, const int* rp, int n, int lane) {
+LXO_DEV int edit_wave(const int* hp, long long hts, int m, const int* rp, long long rts, int n, int lane) {
     int b[CPL], prev[CPL];
 #pragma unroll
     for (int e = 0; e < CPL; ++e) {
         const int j = lane * CPL + e;
-        b[e] = j < n ? rp[j] : -1;
+        b[e] = j < n ? rp[j * rts] : -1;
         prev[e] = j + 1;
     }
     for (int i0 = 0; i0 < m; i0 += 64) {
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256) void edit_kernel(EditArgs a) {
     const int* rp = a.ref + (long long)r * a.ref_ld;
     const int m = cut_len(hp, a.ht_stride, a.hyp_len ? min(max(a.hyp_len[p], 0), a.T) : a.T, a.id_end, lane);
     const int n = cut_len(rp, 1, min(a.ref_len ? min(max(a.ref_len[r], 0), a.ref_ld) : a.ref_ld, 64 * CPL), a.id_end, lane);
-    const int d = edit_wave<CPL>(hp, a.ht_stride, m, rp, n, lane);
+    const int d = edit_wave<CPL>(hp, a.ht_stride, m, rp, 1, n, lane);
     if (lane == 0) {
         if (a.dist) a.dist[p] = d;
         if (a.cost) a.cost[p] = (float)d / (float)max(n, 1);
@@ -169,6 +170,82 @@ __global__ __launch_bounds__(256) void cand_emit_kernel(CandArgs a, const int* s
     }
 }
 
+// ---- consensus among the draws of an image (lxo_consensus) ----
+// Launch 1, one wave per unordered pair (g, i < j), image by image in the order (0,1) (0,2) .. (0,n-1) (1,2) ..: the distance of the two draws into
+// dist[g][i][j] and dist[g][j][i].  Equal draws (equal length, equal tokens) skip the DP: its answer for them is 0 as well.  The waves of the pairs
+// (0, j) leave the draws' lengths in risk_out [g][j] (as int32) for launch 2.
+LXO_DEV const int* cons_draw(const ConsArgs& a, int g, int i) { return a.ids + (long long)g * a.image_stride + (long long)i * a.draw_stride; }
+
+template <int CPL>
+__global__ __launch_bounds__(256) void cons_pairs_kernel(ConsArgs a, int per) {
+    const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= a.B * per) return;
+    const int g = w / per;
+    int q = w % per, i = 0;
+    while (q >= a.n - 1 - i) { q -= a.n - 1 - i; ++i; }
+    const int j = i + 1 + q;
+    const int* pi = cons_draw(a, g, i);
+    const int* pj = cons_draw(a, g, j);
+    const int Li = cut_len(pi, a.tok_stride, a.T, a.id_end, lane), Lj = cut_len(pj, a.tok_stride, a.T, a.id_end, lane);
+    bool same = Li == Lj;
+    for (int t0 = 0; t0 < Li && same; t0 += 64) {
+        const int t = t0 + lane;
+        same = __ballot(t < Li && pi[t * a.tok_stride] != pj[t * a.tok_stride]) == 0ull;
+    }
+    const int d = same ? 0 : edit_wave<CPL>(pi, a.tok_stride, Li, pj, a.tok_stride, Lj, lane);
+    if (lane == 0) {
+        int* row = a.dist + (long long)g * a.n * a.n;
+        row[i * a.n + j] = d;
+        row[j * a.n + i] = d;
+        if (i == 0) {
+            int* len = reinterpret_cast<int*>(a.risk) + (long long)g * a.n;
+            len[j] = Lj;
+            if (j == 1) len[0] = Li;
+        }
+    }
+}
+
+// Launch 2, one wave per image, lane i = draw i: risk[g][i] = (sum_j w_j c(i, j)) / sum_j w_j with both sums added in ascending j, products and sums
+// rounded one by one (no fused multiply-add: the value is the one the f32 operations of the definition give); then the arg-min over the values
+// written, the lower draw on ties.  The diagonal of dist is written here.
+__global__ __launch_bounds__(256) void cons_select_kernel(ConsArgs a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, g = blockIdx.x * 4 + (threadIdx.x >> 6), n = a.n;
+    if (g >= a.B) return;
+    const bool mine = lane < n;
+    float* risk = a.risk + (long long)g * n;
+    int* row = a.dist + (long long)g * n * n;
+    const int len = mine && n > 1 ? reinterpret_cast<const int*>(risk)[lane] : 0;      // (one draw: no pair left a length, and none is needed)
+    float w = 1.f;
+    if (a.weights) {
+        w = mine ? a.weights[(long long)g * n + lane] : 0.f;
+        if (!(w > 0.f) || !(w - w == 0.f)) w = 0.f;                                    // negative, NaN, infinite: 0
+        float sum = 0.f;
+        for (int j = 0; j < n; ++j) sum += __shfl(w, j);
+        if (sum == 0.f) w = 1.f;
+    }
+    float W = 0.f, acc = 0.f;
+    for (int j = 0; j < n; ++j) {
+        const float wj = __shfl(w, j);
+        const int Lj = __shfl(len, j);
+        const int d = mine && lane != j ? row[lane * n + j] : 0;
+        const float c = a.normalize ? (float)d / (float)max(Lj, 1) : (float)d;
+        W += wj;
+        acc += wj * c;
+    }
+    const float r = acc / W;
+    if (mine) { risk[lane] = r; row[lane * n + lane] = 0; }
+    float v = mine ? r : __int_as_float(0x7f800000);
+    int best = lane;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int ob = __shfl_xor(best, o);
+        if (ov < v || (ov == v && ob < best)) { v = ov; best = ob; }
+    }
+    if (lane == 0) a.best[g] = best;
+}
+
 }  // namespace
 
 #define LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, __VA_ARGS__)
@@ -195,4 +272,21 @@ int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st) {
     EditArgs e = {a.cand, nullptr, a.ref, a.ref_len, a.row_image, a.group_off + a.B, nullptr, a.cost, Tc, 0, 1, 1, Tc, a.B, a.Tr, 1,
                   a.B * (a.n + a.inc), a.id_end};
     return lxo_k_edit_distance(e, st);
+}
+
+int lxo_k_consensus(const ConsArgs& a, hipStream_t st) {
+    if (a.T > kEditMaxRef || a.n > kConsensusMaxN) return -2;
+    if (a.B == 0) return 0;
+    const long long per = (long long)a.n * (a.n - 1) / 2, waves = per * a.B;
+    if (waves > 0x7ffffff0ll) return -2;
+    if (waves) {
+        const int grid = (int)((waves + 3) / 4), p = (int)per;
+        if (a.T <= 64) LAUNCH(cons_pairs_kernel<1>, grid, a, p);
+        else if (a.T <= 128) LAUNCH(cons_pairs_kernel<2>, grid, a, p);
+        else if (a.T <= 256) LAUNCH(cons_pairs_kernel<4>, grid, a, p);
+        else if (a.T <= 512) LAUNCH(cons_pairs_kernel<8>, grid, a, p);
+        else LAUNCH(cons_pairs_kernel<16>, grid, a, p);
+    }
+    LAUNCH(cons_select_kernel, cdiv(a.B, 4), a);
+    return (int)hipGetLastError();
 }

@@ -845,6 +845,50 @@ class Engine(object):
                                             _p(dist), _p(cost), self._stream()), "edit_distance")
         return (dist.cpu().numpy(), cost.cpu().numpy()) if return_cost else dist.cpu().numpy()
 
+    def consensus(self, ids, id_end, weights=None, normalize=True, return_dist=False):
+        """The minimum-risk choice among n transcriptions per image (lxo_consensus): ids [B, T, n] token ids -- what sample_decode returns -- as a
+        host array or a device int32 tensor, whose own strides are passed through (a view such as x.permute(0, 2, 1) of rows [B, n, T] is read in
+        place).  Draw i of an image is its column cut at the first id_end (None: no cut); risk[b, i] is its expected edit distance to the image's
+        draws, sum_j w_j c(i, j) / sum_j w_j with c = distance / max(tokens of draw j, 1) (normalize) or the distance itself, and best[b] the draw of
+        least risk, the lower index on ties.  weights [B, n] (None: uniform).  -> (best int32 [B], risk f32 [B, n]) and with return_dist also the
+        distances int32 [B, n, n].  A ValueError before any launch for a wrong rank, n outside 1 .. 64, T above the kernel's limit, weights of
+        another shape, and host weights that are negative, not finite or sum to 0 in a row (on the device such an entry counts as 0 and such a row
+        as all ones)."""
+        if isinstance(ids, torch.Tensor) and ids.device == self.device and ids.dtype == torch.int32:
+            t = ids
+        else:
+            t = self._to_dev(ids, torch.int32)
+        best, risk, dist = self._consensus_device(t, id_end, weights, normalize)
+        out = (best.cpu().numpy(), risk.cpu().numpy())
+        return out + (dist.cpu().numpy(),) if return_dist else out
+
+    def _consensus_device(self, ids, id_end, weights=None, normalize=True):
+        """consensus' checks and its call on a device int32 tensor [B, T, n] of any strides: -> (best, risk, dist), left on the device"""
+        if ids.dim() != 3:
+            raise ValueError("consensus: ids must be [B, T, n], got %s" % list(ids.shape))
+        B, T, n = (int(x) for x in ids.shape)
+        if not 1 <= n <= _abi.LXO_CONSENSUS_MAX_N:
+            raise ValueError("consensus: n = %d draws per image outside 1 .. %d" % (n, _abi.LXO_CONSENSUS_MAX_N))
+        if T > _abi.LXO_EDIT_MAX_REF:
+            raise ValueError("consensus: draws of %d tokens exceed the edit-distance kernel's limit of %d" % (T, _abi.LXO_EDIT_MAX_REF))
+        w = None
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor):
+                a = np.asarray(weights, np.float64)
+                if a.shape == (B, n) and (not np.isfinite(a).all() or (a < 0).any() or (a.sum(axis=1) == 0).any()):
+                    raise ValueError("consensus: weights must be finite, >= 0 and not all 0 for an image")
+            w = self._to_dev(weights, torch.float32)
+            if tuple(w.shape) != (B, n):
+                raise ValueError("consensus: weights must be [B = %d, n = %d], got %s" % (B, n, list(w.shape)))
+        dist = torch.empty(B, n, n, dtype=torch.int32, device=self.device)
+        risk = torch.empty(B, n, dtype=torch.float32, device=self.device)
+        best = torch.empty(B, dtype=torch.int32, device=self.device)
+        if B:
+            src = ids if T else torch.zeros(1, dtype=torch.int32, device=self.device)      # (no token: a word to point at, none of it read)
+            self._ck(self.lib.lxo_consensus(_p(src), int(ids.stride(0)), int(ids.stride(2)), int(ids.stride(1)), B, n, T, -1 if id_end is None else int(id_end),
+                                            _p(w), 1 if normalize else 0, _p(dist), _p(risk), _p(best), self._stream()), "consensus")
+        return best, risk, dist
+
     def evaluate_batch(self, img, formula, lengths):
         """(sum CE, n_words) of img2seq.py:74-75 for one batch (teacher forced)."""
         self.forward(img, formula)
@@ -1341,7 +1385,7 @@ class Engine(object):
         return _abi.LxoSampleOpts(temperature, top_k, top_p, int(seed) & 0xFFFFFFFF)
 
     def sample_decode(self, img, id_end, n=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, max_iter=151, return_scores=False, return_attention=False,
-                      prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False):
+                      prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False, return_consensus=False, consensus_normalize=True):
         """n independent DRAWS of the whole sequence per image (lxo_sample_decode): ids int32 [B, T', n].  Every step draws from the model's
         distribution at `temperature`, cut to the top_k most likely tokens (0: off) and then to the smallest set of renormalised mass >= top_p
         (1: off); temperature = 0 means top_k = 1, the arg-max.  Draw (b, j) depends only on seed, b, j and the step: the same seed repeats bit for
@@ -1352,9 +1396,13 @@ class Engine(object):
         prefix / prefix_lengths / allowed: per image, as in greedy_decode.  A ValueError before any launch for what greedy_decode refuses, n outside
         1 .. min(16, V), temperature < 0 or not finite, top_k < 0, top_p outside (0, 1].
         grammar / return_depth: as in greedy_decode (lxo_sample_decode_grammar), one state per draw: the cut-offs and the draw run over the
-        step's effective set, so every draw ends balanced.  depth int32 [B, T', n] (last output)."""
+        step's effective set, so every draw ends balanced.  depth int32 [B, T', n] (last output).
+        return_consensus: the minimum-risk choice among each image's draws (consensus(), uniform weights, consensus_normalize its normalize),
+        computed on the ids where the decode left them on the device: best int32 [B] and risk f32 [B, n] are appended as the last two outputs."""
         if return_depth and grammar is None:
             raise ValueError("return_depth needs grammar=")
+        if return_consensus and int(max_iter) > _abi.LXO_EDIT_MAX_REF:
+            raise ValueError("return_consensus: max_iter = %d exceeds the edit-distance kernel's limit of %d tokens" % (int(max_iter), _abi.LXO_EDIT_MAX_REF))
         box = []
         ids, logp, logq, alpha, steps, geo = self._sample_device(img, id_end, n, temperature, top_k, top_p, seed, max_iter, return_scores, return_attention,
                                                                  prefix, prefix_lengths, allowed, grammar, box)
@@ -1366,6 +1414,8 @@ class Engine(object):
             out += [logp[:, :steps], logq[:, :steps]]
         if return_depth:
             out.append(box[0][:, :steps])
+        if return_consensus:
+            out += self._consensus_device(ids[:, :steps], id_end, None, consensus_normalize)[:2]
         out = tuple(a.cpu().numpy() for a in out)
         return out if len(out) > 1 else out[0]
 

@@ -423,21 +423,28 @@ class Img2SeqModel(BaseModel):
             alts.append([self._alt_entries(alt, b, int(emitted[b, i])) for b in range(ids.shape[0])])
         return hyps, scores, alts
 
-    def sample_batch(self, images, n, temperature=1.0, top_k=0, top_p=1.0, seed=0, banned=None, allowed=None, grammar=None):
+    def sample_batch(self, images, n, temperature=1.0, top_k=0, top_p=1.0, seed=0, banned=None, allowed=None, grammar=None, consensus=False):
         """n sampled transcriptions per image (Engine.sample_decode), folded into their DISTINCT hypotheses: -> one dict per image,
         {"hypotheses": [{"text", "count", "logp": the model's sequence log-prob (sum of the token log-probs through END), "token_logp": [...]},
         ...] sorted by count, then log-prob, both descending, "agreement": top count / n}.  A hypothesis is a draw truncated at its first END; draws
         that agree share one entry (the log-probs of its first draw).  Agreement is a confidence: n draws that all say the same are a stronger
         accept signal than the greedy path's mean token probability, and the top entry is the vote.  banned / allowed / grammar: as in predict_batch
-        (under a grammar no draw is lost to an unbalanced formula)."""
+        (under a grammar no draw is lost to an unbalanced formula).
+        consensus: the minimum-risk choice among the draws on top of the vote (Engine.sample_decode(return_consensus=True): the n draws with
+        uniform weights, so a hypothesis weighs by its count): every hypothesis gains "risk", its expected edit distance (over the length of the
+        other side) to the image's draws, and every image "consensus", the index into "hypotheses" of the one of least risk, and "expected_cost",
+        that risk -- a confidence that still tells hypotheses apart where every draw is distinct and every count 1.  Nothing else changes."""
         fd = self._get_feed_dict(images, dropout=1)
         max_iter = getattr(self._config, "max_length_formula", 150) + 1
         id_end = self._vocab.id_end
-        ids, logp, _ = self.engine.sample_decode(fd["img"], id_end, n=n, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, max_iter=max_iter,
-                                                 return_scores=True, allowed=self._token_sets(len(images), banned, allowed), **self._grammar(grammar))
+        res = self.engine.sample_decode(fd["img"], id_end, n=n, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, max_iter=max_iter,
+                                        return_scores=True, allowed=self._token_sets(len(images), banned, allowed), return_consensus=bool(consensus),
+                                        **self._grammar(grammar))
+        ids, logp = res[:2]
+        best, risk = res[3:] if consensus else (None, None)
         out = []
         for b in range(ids.shape[0]):
-            seen = {}
+            seen, entry = {}, []
             for j in range(ids.shape[2]):
                 path = ids[b, :, j]
                 end = np.flatnonzero(path == id_end)
@@ -445,12 +452,19 @@ class Img2SeqModel(BaseModel):
                 key = tuple(int(x) for x in truncate_end(path, id_end))
                 if key in seen:
                     seen[key]["count"] += 1
+                    entry.append(seen[key])
                     continue
                 lp = [float(x) for x in logp[b, :m, j]]
                 seen[key] = {"text": " ".join(self._vocab.id_to_tok[i] for i in key), "count": 1,
                              "logp": float(np.sum(np.asarray(lp, dtype=np.float64))), "token_logp": lp}
+                if consensus:
+                    seen[key]["risk"] = float(risk[b, j])
+                entry.append(seen[key])
             hyps = sorted(seen.values(), key=lambda h: (-h["count"], -h["logp"]))
             out.append({"hypotheses": hyps, "agreement": hyps[0]["count"] / float(ids.shape[2])})
+            if consensus:
+                k = [i for i, h in enumerate(hyps) if h is entry[int(best[b])]][0]
+                out[-1].update(consensus=k, expected_cost=hyps[k]["risk"])
         return out
 
     def predict(self, img):

@@ -14,6 +14,8 @@ alternatives=K: for a decode they come from a second, teacher-forced pass over t
 --ban / --allow-file, which then constrain the alternatives.  --sample N draws N transcriptions per image instead of decoding the best one
 (Img2SeqModel.sample_batch; --temperature T, --top-k K, --top-p P and --seed S shape and repeat the draws; combines with --ban /
 --allow-file): one line with the agreement (top count / N), then one line per distinct hypothesis with its count and log-prob.
+--consensus (with --sample) adds the minimum-risk choice among the draws (sample_batch(consensus=True)): the head line names the hypothesis with
+the least expected edit distance to the draws and that cost, every hypothesis line carries its risk, and a * marks the chosen one.
 --balanced decodes under the delimiter grammar of the vocabulary (latex_ocr_amd.grammar.Grammar.latex: { }, \\left / \\right, \\begin{X} / \\end{X};
 --pairs "OPEN:CLOSE ..." names the pairs instead, each side a comma-separated token list): every hypothesis closes what it opens.  It
 combines with everything but --formula.  Without the flag, where the vocabulary has delimiters, a line "  balanced: yes / no" behind each
@@ -42,6 +44,7 @@ def main(argv=None):
     ap.add_argument("--top-k", type=int, default=0, help="--sample: draw among the K most likely tokens (0: off)")
     ap.add_argument("--top-p", type=float, default=1.0, help="--sample: draw among the smallest token set of mass >= P (1: off)")
     ap.add_argument("--seed", type=int, default=0, help="--sample: the same seed repeats the draws")
+    ap.add_argument("--consensus", action="store_true", help="--sample: the hypothesis of least expected edit distance to the draws, and that cost")
     ap.add_argument("--balanced", action="store_true", help="decode under the delimiter grammar: every hypothesis closes what it opens")
     ap.add_argument("--pairs", default=None, help='delimiter pairs "OPEN:CLOSE ..." (each side comma-separated tokens) instead of those read off the vocabulary')
     ap.add_argument("images", nargs="+")
@@ -52,6 +55,8 @@ def main(argv=None):
         ap.error("--prefix completes one image and does not combine with --formula")
     if a.sample and (a.formula is not None or a.prefix is not None or a.alternatives or not 1 <= a.sample <= 16):
         ap.error("--sample takes 1 .. 16 and does not combine with --formula, --prefix or --alternatives")
+    if a.consensus and not a.sample:
+        ap.error("--consensus chooses among the draws of --sample N")
     d = a.results
     config_vocab, config_model = Config(d + "vocab.json"), Config(d + "model.json")
     vocab = Vocab(config_vocab)
@@ -108,10 +113,16 @@ def main(argv=None):
             out.append(res)
             continue
         if a.sample:
-            res = model.sample_batch([greyscale(img)], a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, **dec)[0]
+            more = {"consensus": True} if a.consensus else {}
+            res = model.sample_batch([greyscale(img)], a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, **dict(dec, **more))[0]
             print(path, "~>", "%d draws\tagreement %.3f" % (a.sample, res["agreement"]))
-            for h in res["hypotheses"]:
-                print("  %3d x  logp %9.4f  %s" % (h["count"], h["logp"], h["text"]))
+            if a.consensus:
+                print(path, "=> consensus:", res["hypotheses"][res["consensus"]]["text"], "\texpected cost %.4f" % res["expected_cost"])
+            for k, h in enumerate(res["hypotheses"]):
+                if a.consensus:
+                    print("%s %3d x  logp %9.4f  risk %.4f  %s" % ("*" if k == res["consensus"] else " ", h["count"], h["logp"], h["risk"], h["text"]))
+                else:
+                    print("  %3d x  logp %9.4f  %s" % (h["count"], h["logp"], h["text"]))
                 report(h["text"])
             out.append(res)
             continue
