@@ -21,6 +21,9 @@
 // with an XCD barrier after each.  A workgroup whose barrier does not complete within 200 ms (a chain that lost a member: fewer than
 // 32 workgroups of the grid landed on its XCD) flags an error word and stops waiting; the host checks the word after the first use
 // of this path and falls back to the launch-per-step chain (engine.py).
+// The backward chain (xdec_bwd_kernel, further down) runs the same steps in reverse; there a (step, sample) pair behind the sample's formula end
+// is recognised by its all-zero d_ctx row and streams nothing (37 % of the pairs at the benchmark's lengths).  The forward chain knows nothing of
+// lengths: its record is kept -- and tested -- at padded positions too.
 #include "xdec.h"
 #include "drop.h"
 #include "api_util.h"
@@ -1207,6 +1210,11 @@ int launch_dec_nb(const XDecDec& p, hipStream_t st) { return p.allow ? launch_de
 //   Q3  d_att_h = sum of the chunks; d_h = (d_h~ + d_att_h W_att_h^T) mask + carry; LSTM cell backward -> d_z, d_c     its 16 units
 //   Q4  [d_o | d_h] carries = d_z K[D:]^T; g_{t-1} = (d_o(logits) + d_o carry) mask tanh'                              its 32 columns
 // Resident per wave: its eighth of K_OW (2 x 2 fragments), of K_ATT_H (1) and of K_LSTM[D:] (16 fragments: 4 in registers, 12 in LDS).
+// Steps behind a sample's end (BPTT meets them first): d_o(logits) is 0 there and nothing is carried into them, so the d_ctx row Q2 receives is 512
+// exact zeros.  The kernel has no length input; the sample's workgroups see it on the row itself and stream nothing in Q2 (zeros into their d_e
+// columns, a zero d_att_h partial, no request for the next step either).  The protocol is untouched -- every poll, barrier and hand-over store of
+// a step stays, nobody's work moves to another workgroup, a chain still waits for its slowest member; what the live samples' workgroups gain is the
+// memory bandwidth the dead ones no longer take.  The forward chain computes padded positions as before (its record is compared at all positions).
 template <int ATT_U>
 LXO_DEV void attb_load(u32x4 (&xi)[ATT_U], u32x2 (&xa)[ATT_U], float (&al)[ATT_U], rsrc_t rim, rsrc_t rai, rsrc_t ral, int base, int an, int lane) {
 #pragma unroll
@@ -1351,6 +1359,9 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
         attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ralq, wave + XW * ATT_U * (rv ? nblk - 1 : 0), anq, lane);
         attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, ralq, wave + XW * ATT_U * (rv ? nblk - 2 : 1), anq, lane);
     };
+    // the stream's software pipeline across steps: a step ends with the next step's first two blocks requested (kPFB: in Q3 / Q4), EXCEPT a dead
+    // step (Q2), which requests nothing and leaves the pipeline cold; the next live step requests its own first blocks (wave-uniform: a scalar)
+    bool cold = false;
     for (int t = T - 1; t >= 0; --t) {
         dr.t = t;
         XSTAMP(T - 1 - t, 0);
@@ -1427,21 +1438,44 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
             const int tn = max(t - 1, 0);
             const rsrc_t ral = make_rsrc(p.alpha + sp * p.Rp + al_off, (unsigned)anq * 4u);
             const rsrc_t raln = make_rsrc(p.alpha + (long long)tn * B * p.Rp + al_off, (unsigned)anq * 4u);
+            // A step behind the sample's end: d_o(logits) is 0 there and so is everything BPTT carried into it, so d_ctx is 512 exact zeros, every d_e
+            // of the row is alpha (0 - 0) and the d_att_h partial a sum of zeros.  Every wave holds the whole d_ctx row: all waves of the workgroup
+            // and all workgroups of the sample decide alike.  Such a step requests and computes no block; it stores the zeros of its d_e columns
+            // (datt_img_live_kernel finds a row's live range by d != 0) and goes on to the forward values, the workgroup barrier and the partial's
+            // hand-over words (acc is still 0) like any other step: no poll, barrier or hand-over store is left out.
+            bool nz = false;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) nz = nz || dc[e] != 0.f;     // (a NaN is not a zero: a broken step streams as before)
+            // (readfirstlane: known uniform.  Left to the compiler, the loop counter below that starts from `cold` becomes a vector register, and with
+            // it every row address of the stream and the block's row tests -- measured: 14.7 us for a live step's stream against 11.9)
+            const bool dead_step = __builtin_amdgcn_readfirstlane(__ballot(nz) == 0ull ? 1 : 0) != 0;
+            if (dead_step) for (int i = tid; i < an; i += 512) de_row[i] = 0.f;
             if constexpr (kPFB == 0) {
-            for (int it = 0; it < nblk; it += 2) {
+            // A dead step walks no block (nb = 0) and requests nothing: the pipeline is cold behind it.  The first live step behind dead ones starts
+            // one trip early (it = -2), which computes nothing and requests blocks 0 and 1 of its own walk as the kernel's prologue does for
+            // t = T - 1 -- one exposed load latency per sample and launch; the loop's requests stay the only ones (a second place that writes the
+            // block registers costs a second register set: the allocator does not merge the two).
+            const int nb = dead_step ? 0 : nblk;
+            for (int it = __builtin_amdgcn_readfirstlane((cold && nb > 0) ? -2 : 0); it < nb; it += 2) {
                 const bool moreA = it + 2 < nblk, moreB = it + 3 < nblk;
-                attb_block<ATT_U, EXPD>(xiA, xaA, alA, ro.XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
-                __builtin_amdgcn_sched_barrier(0);
+                if (it >= 0) {
+                    attb_block<ATT_U, EXPD>(xiA, xaA, alA, ro.XBASE(it, rev), an, dc, ah, s, acc, de_row, lane);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, moreA ? ral : raln, moreA ? ro.XBASE(it + 2, rev) : ro.XBASE(0, rev ^ 1), anq, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 if (it + 1 < nblk) {                              // (an odd block count ends on an A half: B already holds the next step's block 1)
-                    attb_block<ATT_U, EXPD>(xiB, xaB, alB, ro.XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
-                    __builtin_amdgcn_sched_barrier(0);
+                    if (it >= 0) {
+                        attb_block<ATT_U, EXPD>(xiB, xaB, alB, ro.XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                     attb_load<ATT_U>(xiB, xaB, alB, imq, aiq, moreB ? ral : raln, moreB ? ro.XBASE(it + 3, rev) : ro.XBASE(1, rev ^ 1), anq, lane);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            } else {
+            cold = dead_step;
+            } else if (!dead_step) {
+            if (cold) { prefetch_b(t); cold = false; }          // kPFB: the first live step behind dead ones requests its own first blocks (Q3 / Q4 of a dead step request nothing)
             // the chunk ends with nothing in flight (kPFB: the next step's first blocks are requested in Q3 / Q4); peeled as in the forward chain
             int it = 0;
             for (; it + 3 < nblk; it += 2) {
@@ -1459,7 +1493,7 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
             if (rem == 3) { __builtin_amdgcn_sched_barrier(0); attb_load<ATT_U>(xiA, xaA, alA, imq, aiq, ral, ro.XBASE(it + 2, rev), anq, lane); __builtin_amdgcn_sched_barrier(0); }
             if (rem >= 2) attb_block<ATT_U, EXPD>(xiB, xaB, alB, ro.XBASE(it + 1, rev), an, dc, ah, s, acc, de_row, lane);
             if (rem == 3) attb_block<ATT_U, EXPD>(xiA, xaA, alA, ro.XBASE(it + 2, rev), an, dc, ah, s, acc, de_row, lane);
-            }
+            } else cold = true;
             // forward values of the coming phases (unconditional, clamped indices)
             fwd_values(t);
 #pragma unroll
@@ -1518,7 +1552,7 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
                 *reinterpret_cast<f32x4*>(&redc[wave][lane * 4]) = v;
             }
             __syncthreads();
-            if (kPFB == 1 && t > 0) prefetch_b(t - 1);
+            if (kPFB == 1 && t > 0 && !cold) prefetch_b(t - 1);
             if (tid < NB * 64) {
                 const int row = tid >> 6, k4 = (tid & 63) * 4;
                 f32x4 v = *reinterpret_cast<const f32x4*>(&redc[row * QS][k4]);
@@ -1582,7 +1616,7 @@ __global__ __launch_bounds__(512) void xdec_bwd_kernel(XDecBwd p) {
                     for (int i = 0; i < 4; ++i) if (NB >= 4 || i < NB) red[wave][g4 * 4 + i][nt * 16 + r16] = acc[nt][i];
             }
             __syncthreads();
-            if (kPFB == 3 && t > 0) prefetch_b(t - 1);
+            if (kPFB == 3 && t > 0 && !cold) prefetch_b(t - 1);
             if (tid < NB * 32) {
                 float v = 0.f;
 #pragma unroll
