@@ -2,7 +2,8 @@
 """Text evaluation driver with the shape of the reference's evaluate_txt.py:13-50: reload the
 configs saved in the results dir, restore the latest checkpoint, decode the test set, score.  --per-sample FILE also writes the
 teacher-forced score of every test sample's own label (Img2SeqModel.score_batch), one TSV line each -- index, tokens, sequence
-log-prob, mean token log-prob, first position where the model's top-1 differs from the label -- lowest mean first."""
+log-prob, mean token log-prob, first position where the model's top-1 differs from the label -- lowest mean first.  --on-device takes the text
+metrics from the decoded ids on the device (Img2SeqModel.score_ids) instead of re-reading the files: the same numbers, the same line."""
 import argparse
 
 from latex_ocr_amd.model.evaluation.text import score_files
@@ -16,6 +17,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--results", default="results/small/")
     ap.add_argument("--per-sample", default=None, metavar="FILE", help="write per-sample teacher-forced scores of the labels (TSV)")
+    ap.add_argument("--on-device", action="store_true", help="text metrics from the decoded ids on the device, not from the written files")
     a = ap.parse_args(argv)
     d = a.results
     config_data, config_vocab, config_model = Config(d + "data.json"), Config(d + "vocab.json"), Config(d + "model.json")
@@ -24,8 +26,12 @@ def main(argv=None):
     model.build_pred()
     (test_set,) = make_sets(config_data, vocab, names=("test",))
     config_eval = Config({"dir_answers": d + "formulas_test/", "batch_size": 20})
-    files, perplexity = model.write_prediction(config_eval, test_set)
-    scores = score_files(files[0], files[1])
+    if a.on_device:
+        files, perplexity, (refs, hyps) = model.write_prediction(config_eval, test_set, return_ids=True)
+        scores = model.score_ids(refs, hyps[0])
+    else:
+        files, perplexity = model.write_prediction(config_eval, test_set)
+        scores = score_files(files[0], files[1])
     scores["perplexity"] = perplexity
     model.logger.info("- Test Txt: " + " || ".join("{} is {:04.2f}".format(k, v) for k, v in scores.items()))
     if a.per_sample:

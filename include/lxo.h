@@ -268,6 +268,33 @@ int lxo_mrt_weights(const float* seq_logp, const float* cost, const int32_t* gro
 int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
                       const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
                       int pairs, int id_end, int32_t* dist_out, float* cost_out, void* stream);
+/* The counts an evaluation's text metrics are made of -- BLEU-4's clipped n-gram matches and totals, the lengths, the Levenshtein distance and exact
+ * match -- per pair and summed over the pairs, on the device, shape-free.  ADDRESSING, LENGTHS, THE END CUT AND THE CLAMPING of what the device holds
+ * are lxo_edit_distance's, argument for argument: the ids [B, max_steps, n] of a sampled decode are read in place, references are taken in
+ * pad_batch_formulas' layout.  Pair p has hypothesis h and reference r after the cut.
+ * stats_out int32 [pairs][LXO_TEXT_STATS] (nullable), row p:
+ *   [0 .. 3]  match_n, n = 1 .. 4: sum over the distinct n-grams g of h of min(count_h(g), count_r(g)) -- corpus BLEU's clipped matches with one reference.
+ *   [4 .. 7]  total_n = max(1, |h| - n + 1) (nltk's rule: with |h| < n the total is 1 and the matches are 0).
+ *   [8] |h|   [9] |r|   [10] Levenshtein(h, r), the value lxo_edit_distance writes   [11] 1 if h == r (equal length, equal tokens), else 0.
+ * corpus_io int64 [LXO_TEXT_CORPUS] (nullable): [0 .. 9] the column sums of stats [0 .. 9] over the pairs, [10] sum of the distances, [11] sum of
+ *   max(|h|, |r|), [12] sum of the exact matches, [13] pairs.  accumulate = 0 overwrites, accumulate = 1 adds to what is there: an evaluation runs batch
+ *   after batch into one row and copies 14 integers out at its end.  BLEU-4, the edit-distance score and exact match follow from the row alone
+ *   (model/evaluation/text.py scores_from_counts).
+ * Tokens are compared as int32 values and ANY value is a token (negative ids, an id of V as a sentinel): an n-gram is compared only where it lies inside
+ * its sequence, by position, never against padding.  Both sides are at most LXO_EDIT_MAX_REF tokens wide.
+ * THE COUNTING IDENTITY: hypothesis position i counts for order n iff k < c, with k the earlier hypothesis positions holding its n-gram and c the
+ * reference positions holding it; summed over i that is sum_g min(count_h(g), count_r(g)) exactly.  One wave per pair, both sides staged in LDS, one
+ * walk for the four orders; integer arithmetic only, no host synchronisation, capturable into a graph, the same bytes in every run.  With stats_out
+ * the corpus row is a fixed-order reduction of the rows in a second one-workgroup launch; with stats_out NULL the waves add into corpus_io with 64-bit
+ * integer atomics (behind a launch that zeroes it when accumulate = 0) -- integer sums, the same in every order.
+ * pairs == 0: no kernel runs; corpus_io is zeroed when accumulate == 0 and untouched otherwise.
+ * -1, with the reason in lxo_last_error and nothing written: stats_out and corpus_io both NULL; a NULL hyp or ref; pairs, T, G or a stride negative,
+ * hyp_block or per_ref < 1, G < 1 with pairs > 0; T outside 0 .. LXO_EDIT_MAX_REF; ref_ld outside 1 .. LXO_EDIT_MAX_REF; accumulate not 0 or 1. */
+#define LXO_TEXT_STATS  12   /* int32 per pair  */
+#define LXO_TEXT_CORPUS 14   /* int64 per corpus */
+int lxo_text_stats(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                   const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
+                   int pairs, int id_end, int32_t* stats_out, long long* corpus_io, int accumulate, void* stream);
 /* The candidate rows of a minimum-risk step, built on the device from a sampled decode: three launches, no host synchronisation.
  * ids int32 [B, max_steps, n] as lxo_sample_decode leaves them and steps = the steps it ran (0 <= steps <= max_steps, 1 <= n <= 16);
  * ref int32 [B, Tr] with ref_len [B] in pad_batch_formulas' layout (tokens, END, PAD; length = tokens + 1), 1 <= Tr <= LXO_EDIT_MAX_REF.

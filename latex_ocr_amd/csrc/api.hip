@@ -160,6 +160,23 @@ extern "C" int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hy
     CHECK_LAUNCH(lxo_k_edit_distance(a, (hipStream_t)stream), "lxo_edit_distance");
     return 0;
 }
+static_assert(LXO_TEXT_STATS == kTextStats && LXO_TEXT_CORPUS == kTextCorpus, "include/lxo.h and csrc/seqcost.h disagree on the text-metric rows");
+extern "C" int lxo_text_stats(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                              const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
+                              int pairs, int id_end, int32_t* stats_out, long long* corpus_io, int accumulate, void* stream) {
+    if (!hyp || !ref) return fail(-1, "lxo_text_stats: null hyp or ref");
+    if (!stats_out && !corpus_io) return fail(-1, "lxo_text_stats: stats_out and corpus_io are both NULL");
+    if (pairs < 0 || T < 0 || G < 0 || hyp_block_stride < 0 || hyp_row_stride < 0 || hyp_tok_stride < 0)
+        return fail(-1, "lxo_text_stats: a negative count or stride");
+    if (hyp_block < 1 || per_ref < 1 || (pairs > 0 && G < 1)) return fail(-1, "lxo_text_stats: hyp_block < 1, per_ref < 1 or no reference row");
+    if (T > LXO_EDIT_MAX_REF) return fail(-1, "lxo_text_stats: T outside 0 .. LXO_EDIT_MAX_REF (a hypothesis wider than the kernel's staging limit)");
+    if (ref_ld < 1 || ref_ld > LXO_EDIT_MAX_REF) return fail(-1, "lxo_text_stats: ref_ld outside 1 .. LXO_EDIT_MAX_REF (a reference longer than the kernel's column limit)");
+    if (accumulate != 0 && accumulate != 1) return fail(-1, "lxo_text_stats: accumulate must be 0 or 1");
+    const TextArgs a = {hyp, hyp_len, ref, ref_len, ref_of, stats_out, corpus_io, hyp_block_stride, hyp_row_stride, hyp_tok_stride,
+                        hyp_block, T, G, ref_ld, per_ref, pairs, id_end, accumulate};
+    CHECK_LAUNCH(lxo_k_text_stats(a, (hipStream_t)stream), "lxo_text_stats");
+    return 0;
+}
 extern "C" int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
                                   int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
                                   int32_t* row_image, void* stream) {

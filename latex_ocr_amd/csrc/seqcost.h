@@ -42,3 +42,16 @@ struct ConsArgs {
     int B, n, T, id_end, normalize;
 };
 int lxo_k_consensus(const ConsArgs& a, hipStream_t st);
+
+// The text metrics' counts (lxo_text_stats, include/lxo.h holds the definition): pairs addressed, cut and clamped as EditArgs', T <= kEditMaxRef as
+// well.  stats (nullable) int32 [pairs][kTextStats]; corpus (nullable) int64 [kTextCorpus], overwritten or added to (accumulate).  With stats: one
+// launch for the rows and a one-workgroup launch that sums them in a fixed order; without: the waves add their rows into corpus with 64-bit integer
+// atomics (behind a launch that zeroes it when it is overwritten).  No host synchronisation.  T or ref_ld > kEditMaxRef: -2.
+constexpr int kTextStats = 12, kTextCorpus = 14;
+struct TextArgs {
+    const int* hyp; const int* hyp_len; const int* ref; const int* ref_len; const int* ref_of;
+    int* stats; long long* corpus;
+    long long hb_stride, hr_stride, ht_stride;
+    int hyp_block, T, G, ref_ld, per_ref, pairs, id_end, accumulate;
+};
+int lxo_k_text_stats(const TextArgs& a, hipStream_t st);

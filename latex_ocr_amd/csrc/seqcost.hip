@@ -1,6 +1,8 @@
 // Sequence costs on the device: the batched Levenshtein distance (lxo_edit_distance) and the candidate rows of a minimum-risk step built from
 // sampled ids (lxo_mrt_candidates).  Integer arithmetic throughout: exact, and the same in every order.  On top of the distances, the
 // minimum-risk choice among the draws of an image (lxo_consensus): all pairwise distances, the expected cost of every draw, the arg-min.
+// And the counts an evaluation's text metrics are made of (lxo_text_stats): clipped n-gram matches, lengths, distance and exact match per pair,
+// summed over the pairs into a corpus row.
 #include "seqcost.h"
 
 namespace {
@@ -246,6 +248,136 @@ __global__ __launch_bounds__(256) void cons_select_kernel(ConsArgs a) {
     if (lane == 0) a.best[g] = best;
 }
 
+// ---- text metrics of a pair (lxo_text_stats): clipped n-gram matches for n = 1 .. 4, lengths, distance, exact match ----
+// A side's tokens are staged in LDS with token t at word t + 1, so that the walks below read four tokens per aligned 16-byte broadcast.  Words
+// behind the sequence are zero, and NO comparison reaches them: an n-gram is compared only where it lies inside its sequence, by position, so any
+// int32 value is a token.
+constexpr int kTextWords = kEditMaxRef + 12;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+
+LXO_DEV void text_stage(int* s, const int* src, long long stride, int len, int lane) {
+    for (int t = lane; t < len + 12; t += 64) s[t] = (t >= 1 && t <= len) ? src[(t - 1) * stride] : 0;
+}
+
+// Four positions j0 .. j0 + 3 of a walk: x holds the tokens j0 .. j0 + 6.  CHECK: position j counts only while bound - j >= 1, and then for every
+// order (ALL) or for the orders n <= bound - j.
+template <bool CHECK, bool ALL>
+LXO_DEV void text_group(const int (&x)[7], int j0, int bound, int t0, int t1, int t2, int t3, int (&cnt)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int room = bound - (j0 + u);
+        const bool e1 = (!CHECK || room >= 1) && x[u] == t0;
+        const bool e2 = e1 && (!CHECK || ALL || room >= 2) && x[u + 1] == t1;
+        const bool e3 = e2 && (!CHECK || ALL || room >= 3) && x[u + 2] == t2;
+        const bool e4 = e3 && (!CHECK || ALL || room >= 4) && x[u + 3] == t3;
+        cnt[0] += e1; cnt[1] += e2; cnt[2] += e3; cnt[3] += e4;
+    }
+}
+
+// The lane holds the window (t0 .. t3) of its hypothesis position; cnt[n - 1] += the positions j < steps of the staged sequence s whose window agrees
+// with it in the first n tokens.  PREFIX: s is the hypothesis itself and only j < bound (the lane's own position) count -- their n-grams lie inside
+// the hypothesis wherever the lane's does.  Otherwise s is the reference of bound tokens and order n counts at j only while j + n <= bound.  The
+// first `unchecked` positions (a multiple of 4, wave-uniform, <= steps) meet these limits in every lane and order and are compared without them.
+// The next group's tokens are read while the current group is compared.
+template <bool PREFIX>
+LXO_DEV void text_walk(const int* s, int steps, int unchecked, int bound, int t0, int t1, int t2, int t3, int (&cnt)[4]) {
+    int x[7] = {s[1], s[2], s[3], 0, 0, 0, 0};
+    i32x4 q = *reinterpret_cast<const i32x4*>(s + 4);
+    int j0 = 0;
+    for (; j0 < unchecked; j0 += 4) {
+        x[3] = q[0]; x[4] = q[1]; x[5] = q[2]; x[6] = q[3];
+        q = *reinterpret_cast<const i32x4*>(s + j0 + 8);
+        text_group<false, PREFIX>(x, j0, bound, t0, t1, t2, t3, cnt);
+        x[0] = x[4]; x[1] = x[5]; x[2] = x[6];
+    }
+    for (; j0 < steps; j0 += 4) {
+        x[3] = q[0]; x[4] = q[1]; x[5] = q[2]; x[6] = q[3];
+        q = *reinterpret_cast<const i32x4*>(s + j0 + 8);
+        text_group<true, PREFIX>(x, j0, bound, t0, t1, t2, t3, cnt);
+        x[0] = x[4]; x[1] = x[5]; x[2] = x[6];
+    }
+}
+
+// One wave per pair.  Hypothesis position i counts for order n iff the number k of EARLIER hypothesis positions with its n-gram is below the number c
+// of reference positions with it: summed over i that is sum_g min(count_h(g), count_r(g)), the clipped matches, with no table of n-grams.  Lane l of
+// each 64-position chunk owns one position and walks the hypothesis prefix and the reference once for all four orders.
+template <int CPL>
+__global__ __launch_bounds__(256) void text_stats_kernel(TextArgs a) {
+    __shared__ __attribute__((aligned(16))) int tok[4][2 * kTextWords];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave;
+    if (p >= a.pairs) return;
+    const int r = min(max(a.ref_of ? a.ref_of[p] : p / a.per_ref, 0), a.G - 1);
+    const int* hp = a.hyp + (long long)(p / a.hyp_block) * a.hb_stride + (long long)(p % a.hyp_block) * a.hr_stride;
+    const int* rp = a.ref + (long long)r * a.ref_ld;
+    // (the lengths are the same in every lane: held as scalars, the walks' loop control and position limits cost no vector work)
+    const int m = __builtin_amdgcn_readfirstlane(cut_len(hp, a.ht_stride, min(a.hyp_len ? min(max(a.hyp_len[p], 0), a.T) : a.T, kEditMaxRef), a.id_end, lane));
+    const int n = __builtin_amdgcn_readfirstlane(cut_len(rp, 1, min(a.ref_len ? min(max(a.ref_len[r], 0), a.ref_ld) : a.ref_ld, 64 * CPL), a.id_end, lane));
+    int* hs = tok[__builtin_amdgcn_readfirstlane(wave)];
+    int* rs = hs + kTextWords;
+    text_stage(hs, hp, a.ht_stride, m, lane);
+    text_stage(rs, rp, 1, n, lane);
+    __builtin_amdgcn_wave_barrier();                                    // the wave's lanes exchange through its own LDS rows (in-order LDS: no s_barrier)
+
+    int match[4] = {0, 0, 0, 0};
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const int i = i0 + lane, ic = min(i, m);
+        const int t0 = hs[ic + 1], t1 = hs[ic + 2], t2 = hs[ic + 3], t3 = hs[ic + 4];
+        int k[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
+        text_walk<true>(hs, min(i0 + 63, m - 1), i0, i, t0, t1, t2, t3, k);                     // (every j < i0 lies in front of every lane)
+        text_walk<false>(rs, n, max(n - 3, 0) / 4 * 4, n, t0, t1, t2, t3, c);                   // (groups whose last position j has j + 4 <= n)
+#pragma unroll
+        for (int o = 0; o < 4; ++o) match[o] += (int)__builtin_popcountll(__ballot(i + o < m && k[o] < c[o]));
+    }
+    bool same = m == n;
+    for (int t0 = 0; t0 < m && same; t0 += 64) {
+        const int t = min(t0 + lane, m);
+        same = __ballot(hs[t + 1] != rs[t + 1]) == 0ull;
+    }
+    const int d = edit_wave<CPL>(hp, a.ht_stride, m, rp, 1, n, lane);
+    // lane c holds value c of the row (the rows' columns, or the corpus' with max(|h|, |r|) slipped in and the pair count at the end): one store, or one
+    // atomic instruction, of the wave
+    const int row[kTextCorpus] = {match[0], match[1], match[2], match[3], max(1, m), max(1, m - 1), max(1, m - 2), max(1, m - 3), m, n, d,
+                                  a.stats ? (same ? 1 : 0) : max(m, n), same ? 1 : 0, p == 0 ? a.pairs : 0};
+    int v = 0;
+#pragma unroll
+    for (int c = 0; c < kTextCorpus; ++c) if (lane == c) v = row[c];
+    if (a.stats) {
+        if (lane < kTextStats) a.stats[(long long)p * kTextStats + lane] = v;
+    } else if (lane < kTextCorpus) {
+        // no rows to reduce: 64-bit integer adds, whose sum is the same in every order
+        atomicAdd(reinterpret_cast<unsigned long long*>(a.corpus) + lane, (unsigned long long)v);
+    }
+}
+
+// Launch 2, one workgroup: the column sums of the rows in a fixed order (thread t takes the rows t, t + 256, ..; then the wave, then the four waves),
+// written to or added into the corpus row.
+__global__ __launch_bounds__(256) void text_corpus_kernel(const int* stats, int pairs, long long* corpus, int accumulate) {
+    __shared__ long long part[4][kTextCorpus - 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long s[kTextCorpus - 1];
+#pragma unroll
+    for (int c = 0; c < kTextCorpus - 1; ++c) s[c] = 0;
+    for (int p = threadIdx.x; p < pairs; p += 256) {
+        const int* row = stats + (long long)p * kTextStats;
+#pragma unroll
+        for (int c = 0; c < 11; ++c) s[c] += row[c];
+        s[11] += max(row[8], row[9]);
+        s[12] += row[11];
+    }
+#pragma unroll
+    for (int c = 0; c < kTextCorpus - 1; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[c] += __shfl_xor(s[c], o);
+        if (lane == 0) part[wave][c] = s[c];
+    }
+    __syncthreads();
+    const int c = threadIdx.x;
+    if (c < kTextCorpus) {
+        const long long v = c == kTextCorpus - 1 ? (long long)pairs : part[0][c] + part[1][c] + part[2][c] + part[3][c];
+        corpus[c] = (accumulate ? corpus[c] : 0ll) + v;
+    }
+}
+
 }  // namespace
 
 #define LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, __VA_ARGS__)
@@ -288,5 +420,20 @@ int lxo_k_consensus(const ConsArgs& a, hipStream_t st) {
         else LAUNCH(cons_pairs_kernel<16>, grid, a, p);
     }
     LAUNCH(cons_select_kernel, cdiv(a.B, 4), a);
+    return (int)hipGetLastError();
+}
+
+int lxo_k_text_stats(const TextArgs& a, hipStream_t st) {
+    if (a.ref_ld > kEditMaxRef || a.T > kEditMaxRef) return -2;
+    // a corpus row that is overwritten without rows to reduce (no pair, or no stats: the waves add into it) is zeroed first -- the reduction over no row
+    if (a.corpus && !a.accumulate && (a.pairs == 0 || !a.stats)) LAUNCH(text_corpus_kernel, 1, (const int*)nullptr, 0, a.corpus, 0);
+    if (a.pairs == 0) return (int)hipGetLastError();
+    const int grid = cdiv(a.pairs, 4);
+    if (a.ref_ld <= 64) LAUNCH(text_stats_kernel<1>, grid, a);
+    else if (a.ref_ld <= 128) LAUNCH(text_stats_kernel<2>, grid, a);
+    else if (a.ref_ld <= 256) LAUNCH(text_stats_kernel<4>, grid, a);
+    else if (a.ref_ld <= 512) LAUNCH(text_stats_kernel<8>, grid, a);
+    else LAUNCH(text_stats_kernel<16>, grid, a);
+    if (a.stats && a.corpus) LAUNCH(text_corpus_kernel, 1, a.stats, a.pairs, a.corpus, a.accumulate);
     return (int)hipGetLastError();
 }

@@ -845,6 +845,79 @@ class Engine(object):
                                             _p(dist), _p(cost), self._stream()), "edit_distance")
         return (dist.cpu().numpy(), cost.cpu().numpy()) if return_cost else dist.cpu().numpy()
 
+    def text_stats(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None, corpus=None):
+        """The counts the text metrics are made of, per pair, on the device (lxo_text_stats): -> int32 [pairs, 12] = the clipped n-gram matches for
+        n = 1 .. 4, the totals max(1, |h| - n + 1), |h|, |r|, the Levenshtein distance and 1 for h == r (include/lxo.h holds the definition).
+        hyp [pairs, T] and ref [G, Tr] token ids, lengths, id_end and ref_index as edit_distance takes them, host arrays or device tensors; a device
+        int32 tensor is read in place through its own strides, and hyp may also be the [B, T, n] ids of sample_decode (a view such as
+        x.permute(0, 2, 1) of rows [B, n, T] included): pair b * n + j is draw j of image b.  corpus: a device int64 [14] tensor the call ADDS its
+        column sums into and leaves on the device (model/evaluation/text.py scores_from_counts reads such a row), so an evaluation accumulates
+        batch after batch and copies 14 integers out at its end.  A ValueError before any launch as edit_distance's, and for a hypothesis or
+        reference wider than the kernel's limit (LXO_EDIT_MAX_REF) or a corpus that is not a device int64 [14] tensor."""
+        stats, _ = self._text_stats_device("text_stats", hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, True, corpus, 1)
+        return stats.cpu().numpy()
+
+    def text_metrics(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None):
+        """{"BLEU-4", "ExactMatchScore", "EditDistance"} x 100 -- score_files' dict -- of the pairs of one text_stats call, from its corpus row alone:
+        one launch sequence, one copy of 14 integers, the floats of the host bleu_score / exact_match_score / edit_distance on the cut sequences."""
+        from .model.evaluation.text import scores_from_counts
+        _, corpus = self._text_stats_device("text_metrics", hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, False, None, 0)
+        return scores_from_counts(corpus.cpu().numpy())
+
+    def _text_stats_device(self, what, hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, want_stats, corpus, accumulate):
+        """text_stats' checks and its call: -> (stats int32 [pairs, 12] or None, corpus int64 [14]), both left on the device.  corpus None: a fresh row."""
+        h = hyp if isinstance(hyp, torch.Tensor) and hyp.device == self.device and hyp.dtype == torch.int32 else self._to_dev(hyp, torch.int32)
+        r = self._to_dev(ref, torch.int32)
+        if h.dim() not in (2, 3) or r.dim() != 2:
+            raise ValueError("%s: hyp must be [pairs, T] or [B, T, n] and ref [G, Tr], got %s and %s" % (what, list(h.shape), list(r.shape)))
+        T, G, Tr = int(h.shape[1]), int(r.shape[0]), int(r.shape[1])
+        if h.dim() == 3:
+            block, pairs, geom = int(h.shape[2]), int(h.shape[0]) * int(h.shape[2]), (int(h.stride(0)), int(h.stride(2)), int(h.stride(1)))
+        else:
+            block, pairs, geom = 1, int(h.shape[0]), (int(h.stride(0)), 0, int(h.stride(1)))
+        if T > _abi.LXO_EDIT_MAX_REF or Tr > _abi.LXO_EDIT_MAX_REF:
+            raise ValueError("%s: rows of %d (hypotheses) and %d (references) tokens exceed the kernel's limit of %d" % (what, T, Tr, _abi.LXO_EDIT_MAX_REF))
+        if pairs > 0 and G < 1:
+            raise ValueError("%s: %d hypotheses but no reference" % (what, pairs))
+        hl = rl = ri = None
+        if hyp_lengths is not None:
+            hl = self._to_dev(hyp_lengths, torch.int32)
+            if tuple(hl.shape) != (pairs,):
+                raise ValueError("%s: hyp_lengths must be [pairs = %d], got %s" % (what, pairs, list(hl.shape)))
+        if ref_lengths is not None:
+            rl = self._to_dev(ref_lengths, torch.int32)
+            if tuple(rl.shape) != (G,):
+                raise ValueError("%s: ref_lengths must be [G = %d], got %s" % (what, G, list(rl.shape)))
+        per_ref = 1
+        if ref_index is not None:
+            if not isinstance(ref_index, torch.Tensor):
+                a = np.asarray(ref_index)
+                if a.shape == (pairs,) and a.size and (a.min() < 0 or a.max() >= G):
+                    raise ValueError("%s: ref_index must lie in [0, G = %d), got %d .. %d" % (what, G, int(a.min()), int(a.max())))
+            ri = self._to_dev(ref_index, torch.int32)
+            if tuple(ri.shape) != (pairs,):
+                raise ValueError("%s: ref_index must be [pairs = %d], got %s" % (what, pairs, list(ri.shape)))
+        elif pairs:
+            if pairs % G:
+                raise ValueError("%s: without ref_index the %d hypotheses must be a multiple of the %d references" % (what, pairs, G))
+            per_ref = pairs // G
+        if corpus is None:
+            corpus = torch.zeros(_abi.LXO_TEXT_CORPUS, dtype=torch.int64, device=self.device)
+        elif (not isinstance(corpus, torch.Tensor) or corpus.device != self.device or corpus.dtype != torch.int64 or tuple(corpus.shape) != (_abi.LXO_TEXT_CORPUS,)
+              or not corpus.is_contiguous()):
+            raise ValueError("%s: corpus must be a contiguous int64 [%d] tensor on %s" % (what, _abi.LXO_TEXT_CORPUS, self.device))
+        stats = torch.empty(pairs, _abi.LXO_TEXT_STATS, dtype=torch.int32, device=self.device) if want_stats else None
+        if pairs == 0:                                             # nothing to count: the rows are empty, the corpus stays as it is
+            return stats, corpus
+        if T == 0:                                                 # hypotheses without a column: a word to point at, none of it read
+            h = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if Tr == 0:                                                # references without a column: every reference is empty
+            r, Tr = torch.zeros(max(G, 1), 1, dtype=torch.int32, device=self.device), 1
+            rl = torch.zeros(max(G, 1), dtype=torch.int32, device=self.device)
+        self._ck(self.lib.lxo_text_stats(_p(h), block, geom[0], geom[1], geom[2], T, _p(hl), _p(r), G, Tr, _p(rl), _p(ri), per_ref, pairs,
+                                         -1 if id_end is None else int(id_end), _p(stats), _p(corpus), int(accumulate), self._stream()), what)
+        return stats, corpus
+
     def consensus(self, ids, id_end, weights=None, normalize=True, return_dist=False):
         """The minimum-risk choice among n transcriptions per image (lxo_consensus): ids [B, T, n] token ids -- what sample_decode returns -- as a
         host array or a device int32 tensor, whose own strides are passed through (a view such as x.permute(0, 2, 1) of rows [B, n, T] is read in

@@ -95,6 +95,12 @@ def corpus_bleu(list_of_references, hypotheses, max_n=4):
                         best[g] = c
             num[n - 1] += sum(min(c, best[g]) for g, c in h.items())
             den[n - 1] += max(1, len(hyp) - n + 1)
+    return _bleu_from_counts(num, den, hyp_len, ref_len)
+
+
+def _bleu_from_counts(num, den, hyp_len, ref_len):
+    """corpus_bleu's tail: the score from the summed clipped matches and totals per order and the summed lengths"""
+    max_n = len(num)
     if num[0] == 0 or min(num) == 0 or min(den) == 0:
         return 0.0
     logp = sum(math.log(n / d) for n, d in zip(num, den)) / max_n
@@ -117,4 +123,20 @@ def score_files(path_ref, path_hyp):
         "BLEU-4": bleu_score(refs, hyps) * 100,
         "ExactMatchScore": exact_match_score(refs, hyps) * 100,
         "EditDistance": edit_distance(refs, hyps) * 100,
+    }
+
+
+def scores_from_counts(corpus):
+    """The dict of `score_files` from the 14 integers lxo_text_stats sums over a set of pairs (include/lxo.h: corpus_io) -- clipped matches and
+    totals for n = 1 .. 4, the summed hypothesis and reference lengths, the summed distances, the summed max(|h|, |r|), the exact matches and the
+    number of pairs.  The expressions are those of `corpus_bleu`'s tail, `edit_distance` and `exact_match_score` on the same integers, so the
+    floats equal theirs."""
+    c = [int(x) for x in corpus]
+    if len(c) != 14:
+        raise ValueError("scores_from_counts: 14 integers expected, got %d" % len(c))
+    tot = float(c[11])
+    return {
+        "BLEU-4": _bleu_from_counts(c[0:4], c[4:8], c[8], c[9]) * 100,
+        "ExactMatchScore": c[12] / float(max(c[13], 1)) * 100,
+        "EditDistance": (1.0 - c[10] / tot if tot else 1.0) * 100,
     }

@@ -204,11 +204,50 @@ class Img2SeqModel(BaseModel):
         return {"risk": risk, "candidates": out}
 
     def _run_evaluate(self, config, test_set):
-        """Reference: model/img2seq.py:198-213."""
-        files, perp = self.write_prediction(config, test_set)
-        scores = score_files(files[0], files[1])
+        """Reference: model/img2seq.py:198-213.  With `metrics_on_device` true in the config it is given, the text metrics come from the decoded ids
+        through score_ids (the files are written all the same): the same dict."""
+        if getattr(config, "metrics_on_device", False):
+            files, perp, (refs, hyps) = self.write_prediction(config, test_set, return_ids=True)
+            scores = self.score_ids(refs, hyps[0])
+        else:
+            files, perp = self.write_prediction(config, test_set)
+            scores = score_files(files[0], files[1])
         scores["perplexity"] = perp
         return scores
+
+    SCORE_IDS_BATCH = 256
+
+    def score_ids(self, references, hypotheses, per_sample=False):
+        """score_files' dict -- {"BLEU-4", "ExactMatchScore", "EditDistance"} x 100 -- from token ids, on the device: references and hypotheses are
+        lists of id sequences, pair by pair, each cut at the vocabulary's END.  The pairs go through Engine.text_stats in batches of SCORE_IDS_BATCH
+        with ONE accumulator on the device and one copy of its 14 integers at the end; per_sample=True also returns the int32 [N, 12] rows
+        (include/lxo.h: lxo_text_stats), -> (dict, rows).
+        The dict EQUALS score_files' on the files write_answers writes from the same ids, for a vocabulary whose token strings are distinct,
+        non-empty and free of whitespace (then equal ids are equal strings and a line splits back into its tokens).  One quirk is kept: an empty
+        sequence is written as an empty line, which score_files reads as ONE token ("".split(" ") is [""]) -- so it has length 1, and an empty
+        hypothesis equals an empty reference token for token.  An empty cut sequence is therefore mapped to the single id n_tok (one past the
+        vocabulary, equal to no token) on both sides before the call."""
+        from .evaluation.text import scores_from_counts
+        if len(references) != len(hypotheses):
+            raise ValueError("score_ids: %d references but %d hypotheses" % (len(references), len(hypotheses)))
+        id_end, empty = self._vocab.id_end, [self._vocab.n_tok]
+        eng = self.engine
+        corpus, rows = None, []                                   # (the first batch's call makes the accumulator, the others add into it)
+        for at in range(0, len(references), self.SCORE_IDS_BATCH):
+            sides = []
+            for seqs in (hypotheses[at:at + self.SCORE_IDS_BATCH], references[at:at + self.SCORE_IDS_BATCH]):
+                cut = [truncate_end([int(i) for i in s], id_end) or empty for s in seqs]
+                ln = np.array([len(c) for c in cut], np.int32)
+                a = np.zeros((len(cut), int(ln.max())), np.int32)
+                for i, c in enumerate(cut):
+                    a[i, :len(c)] = c
+                sides += [a, ln]
+            stats, corpus = eng._text_stats_device("score_ids", sides[0], sides[2], sides[1], sides[3], None, None, per_sample, corpus, 1)
+            rows.append(stats)
+        scores = scores_from_counts([0] * 14 if corpus is None else corpus.cpu().numpy())
+        if not per_sample:
+            return scores
+        return scores, (np.concatenate([r.cpu().numpy() for r in rows]) if rows else np.zeros((0, 12), np.int32))
 
     def _beam_kwargs(self):
         """The diversity-penalty arguments of one Engine.beam_decode call (decoder.py:67-68); the seed is the number of beam decodes so far."""
@@ -276,8 +315,9 @@ class Img2SeqModel(BaseModel):
         ids = self.engine.greedy_decode(img, self._vocab.id_end, max_iter=max_iter, allowed=allowed)
         return np.expand_dims(ids, axis=1)
 
-    def write_prediction(self, config, test_set):
-        """Reference: model/img2seq.py:215-254.  perplexity is NEGATED (quirk C-2)."""
+    def write_prediction(self, config, test_set, return_ids=False):
+        """Reference: model/img2seq.py:215-254.  perplexity is NEGATED (quirk C-2).  return_ids: -> (files, perplexity, (refs, hyps)) with the id
+        sequences the files were written from, hyps[i] the hypotheses of rank i."""
         k = self._config.beam_size if getattr(self._config, "decoding", "greedy") == "beam_search" else 1
         refs, hyps = [], [[] for _ in range(k)]
         n_words, ce_words = 0, 0.0
@@ -293,6 +333,8 @@ class Img2SeqModel(BaseModel):
                     hyps[i].append(pred)
         files = write_answers(refs, hyps, self._vocab.id_to_tok, config.dir_answers, self._vocab.id_end)
         perp = -np.exp(ce_words / float(n_words))
+        if return_ids:
+            return files, perp, (refs, hyps)
         return files, perp
 
     def predict_batch(self, images, return_scores=False, banned=None, allowed=None, alternatives=0, grammar=None):
