@@ -240,6 +240,21 @@ int lxo_ce_loss_fwd_bwd_dev(const lxo_shape* s, void* ws, const int32_t* formula
  * gradient of sum w CE * inv_norm. */
 int lxo_ce_loss_weighted(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
                          const float* w_tok, const float* w_row, float inv_norm, const float* norm_dev, void* stream);
+/* The label-smoothed loss (TensorFlow's softmax_cross_entropy(label_smoothing=), torch's F.cross_entropy(label_smoothing=)): the target of a live row
+ * (t < lengths[b]) with clamped target y is q_j = (1 - eps) [j == y] + eps / V over j in [0, V), and with lse the row's log-sum-exp, p its soft-max and
+ * w = w_tok[b][t] * w_row[b] (both nullable here: a NULL factor is 1, both NULL is smoothing alone)
+ *     CE = lse - x_y,   U = lse - (sum_{j < V} x_j) / V  (= -mean_j log p_j),   L = (1 - eps) * CE + eps * U,
+ *     d(logits)[t * B + b][j] = (p_j - q_j) * (w * inv_norm) for j < V;   0 in the padding columns [V, Vp) and on rows t >= lengths[b].
+ * In f32 on the device: eps_v = eps / (float)V is one division, the target column subtracts (1.f - eps) + eps_v and every other column eps_v -- with
+ * eps == 0 that is p - 1 and p - 0, so d(logits) and all four statistics are lxo_ce_loss_weighted's bit for bit, and without weights d(logits) and
+ * "loss"[0..1] are lxo_ce_loss_fwd_bwd's.  The logit sum runs over [0, V) only: what the padding columns hold is never read into a result.
+ * norm_dev (nullable, device f32 [1]): 1 / norm_dev[0] replaces inv_norm, as in lxo_ce_loss_weighted.
+ * ws region "loss" = {sum w L, live token count, sum w, sum CE (plain, unweighted)} over the live tokens -- [1] and [3] are the bytes lxo_ce_loss_weighted
+ * leaves -- through the ordered per-workgroup slots of ws region "det_part" in every mode: the same bytes in every run.  The forward chain's error
+ * word turns [0] into NaN.  The rest of the training step is linear in d(logits): lxo_train_bwd after this call leaves the gradient of sum w L * inv_norm.
+ * -1, nothing written, the reason in lxo_last_error: eps not finite or outside [0, 1); a NULL ws, formula or lengths. */
+int lxo_ce_loss_smoothed(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths, float eps,
+                         const float* w_tok, const float* w_row, float inv_norm, const float* norm_dev, void* stream);
 /* Minimum-risk weights on the device, shape-free: rows group_off[g] .. group_off[g + 1] - 1 (device int32 [G + 1], ascending, group_off[0] == 0,
  * group_off[G] <= rows) are the candidate transcriptions of image g, seq_logp their sequence log-probs (lxo_score_tokens' seq_out) and cost their costs
  * (device f32 [rows]).  Q_c = softmax_c(alpha * seq_logp_c) over the group (maximum subtracted), R_g = sum_c Q_c cost_c,

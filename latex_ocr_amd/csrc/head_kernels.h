@@ -6,9 +6,13 @@
 // sign); d(logits) of a live row is scaled by w * inv_ntok and loss_acc = {sum w CE, token count, sum w, sum CE}: four statistics per slot of `det`
 // (512 x 4 floats, else -2).  Without weights: {sum CE, token count} and the kernels of before
 struct CeWeights { const float* tok; const float* row; };
+// smooth (nullable, lxo_ce_loss_smoothed): the target of a live row is q_j = (1 - eps) [j == y] + eps / V over [0, V), eps_v = eps / (float)V.  d(logits) is
+// (p_j - q_j) * scale -- the target column subtracts (1.f - eps) + eps_v, every other eps_v -- and the row's loss (1 - eps) CE + eps (lse - sum_{j < V} x_j / V);
+// the statistics are the four, {sum w L, token count, sum w, sum CE (plain)}, with or without weights (without: w = 1.f), through `det` as above
+struct CeSmooth { float eps, eps_v; };
 int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
                   const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st,      // chain_err (nullable): error word of the persistent decoder chain; non-zero poisons the loss (NaN)
-                  const CeWeights* weights = nullptr);
+                  const CeWeights* weights = nullptr, const CeSmooth* smooth = nullptr);
 // minimum-risk weights of candidate rows grouped by image (rows group_off[g] .. group_off[g + 1] - 1, G groups): Q = softmax(alpha seq_logp) over a group,
 // R_g = sum Q cost, w_out = alpha Q (R_g - cost), q_out (nullable) = Q, risk_out (nullable) [1] = sum_g R_g added in ascending g; rows behind the last group: 0.
 // Offsets are clamped into [0, rows] on the device.  No atomics: the same bytes in every run

@@ -420,6 +420,24 @@ LXO_DEV void ce_end(float* red, float ce_sum, float n_sum, float* loss_acc, floa
 // the kernels they were -- or one CeWeights (WT): token (b, t) then weighs tok[b][t] * row[b], ONE f32 product, a NULL factor is 1, any sign
 LXO_DEV float ce_weight(const RowTok&) { return 1.f; }
 LXO_DEV float ce_weight(const RowTok& r, const CeWeights& q) { return (q.tok ? q.tok[r.o] : 1.f) * (q.row ? q.row[r.b] : 1.f); }
+// Label smoothing (lxo_ce_loss_smoothed): the pack may also END in one CeSmooth (SM), alone -- every token weighs 1.f -- or behind the CeWeights.  The
+// target of a live row is then q_j = (1 - eps) [j == y] + eps / V over [0, V): ce_target is what column j subtracts from p_j, 1.f and 0.f without it
+LXO_DEV float ce_weight(const RowTok&, const CeSmooth&) { return 1.f; }
+LXO_DEV float ce_weight(const RowTok& r, const CeWeights& q, const CeSmooth&) { return ce_weight(r, q); }
+template <typename... W> struct ce_has_smooth { static constexpr bool value = false; };
+template <typename... W> struct ce_has_smooth<CeSmooth, W...> { static constexpr bool value = true; };
+template <typename A, typename... W> struct ce_has_smooth<A, W...> { static constexpr bool value = ce_has_smooth<W...>::value; };
+LXO_DEV CeSmooth ce_smooth() { return {0.f, 0.f}; }
+LXO_DEV CeSmooth ce_smooth(const CeWeights&) { return {0.f, 0.f}; }
+LXO_DEV CeSmooth ce_smooth(const CeSmooth& s) { return s; }
+LXO_DEV CeSmooth ce_smooth(const CeWeights&, const CeSmooth& s) { return s; }
+template <bool SM>
+LXO_DEV float ce_target(bool hit, const CeSmooth& s) {
+    if constexpr (SM) return hit ? (1.f - s.eps) + s.eps_v : s.eps_v;
+    else return hit ? 1.f : 0.f;
+}
+// a live row's smoothed loss from its plain CE, its log-sum-exp and the sum of its logits over [0, V): (1 - eps) CE + eps U, U = lse - sum / V = -mean_j log p_j
+LXO_DEV float ce_smoothed(const CeSmooth& s, float ce, float lse, float xsum, int V) { return (1.f - s.eps) * ce + s.eps * (lse - xsum / (float)V); }
 // d(logits) scale of a row: inv_ntok on a live unweighted row, the single f32 product w * inv_norm on a weighted one, 0 past lengths[b]
 template <bool WT>
 LXO_DEV float ce_scale(const RowTok& r, float w, float inv_ntok) {
@@ -430,6 +448,11 @@ LXO_DEV float ce_scale(const RowTok& r, float w, float inv_ntok) {
 template <bool WT>
 LXO_DEV void ce_stats(float& ce_sum, float& n_sum, float& w_sum, float& u_sum, float w, float ce) {
     if constexpr (WT) { ce_sum += w * ce; w_sum += w; u_sum += ce; } else ce_sum += ce;
+    n_sum += 1.0f;
+}
+// ... smoothed {w L, 1, w, CE}: the row's loss l in the first, its PLAIN CE in the last
+LXO_DEV void ce_stats_smoothed(float& ce_sum, float& n_sum, float& w_sum, float& u_sum, float w, float l, float ce) {
+    ce_sum += w * l; w_sum += w; u_sum += ce;
     n_sum += 1.0f;
 }
 // ce_end for the four: always through the ordered slots, 4 per workgroup, each added as ce_end adds its two
@@ -470,15 +493,19 @@ LXO_DEV void beam_emit(int b, int k, int tid, int time, int id, int par, float v
 // ---- loss ----
 // loss of img2seq.py:68-75 + gradient; one wave per (t, b) row, rows strided over the grid, three strided passes per row
 // W = CeWeights (lxo_ce_loss_weighted): the row's scale is w * inv_norm and the statistics are the four of ce_stats; everything else is the same row
+// W ending in CeSmooth (lxo_ce_loss_smoothed): the sum of the logits over [0, V) rides the third pass, on the values it loads anyway -- a lane adds its
+// columns in ascending order, then the wave -- and ce_target stands in place of the one-hot
 template <typename CT, typename... W>
 __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
                                                      const int* __restrict__ lengths, CT* __restrict__ dlogits,
                                                      float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
                                                      const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp, W... wt) {
     constexpr bool WT = sizeof...(W) != 0;
+    constexpr bool SM = ce_has_smooth<W...>::value;
     __shared__ float red[WT ? 16 : 8];
     inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const CeSmooth sm = ce_smooth(wt...);
     float ce_sum = 0.f, n_sum = 0.f, w_sum = 0.f, u_sum = 0.f;
     for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
         const RowTok r = row_tok(row, B, T, lengths);
@@ -488,28 +515,41 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
         const float lse = strided_lse<false>(lg, lane, V, nullptr);
         const float w = ce_weight(r, wt...);
         const float scale = ce_scale<WT>(r, w, inv_ntok);
+        float xs = 0.f;
         for (int j = lane; j < Vp; j += 64) {
             float g = 0.f;
-            if (j < V) g = (expf(lg[j] - lse) - (j == tgt ? 1.f : 0.f)) * scale;
+            if (j < V) {
+                const float xj = lg[j];
+                if constexpr (SM) xs += xj;
+                g = (expf(xj - lse) - ce_target<SM>(j == tgt, sm)) * scale;
+            }
             dl[j] = from_f32<CT>(g);
         }
-        if (r.live) ce_stats<WT>(ce_sum, n_sum, w_sum, u_sum, w, lse - lg[tgt]);
+        if constexpr (SM) {
+            if (r.live) {
+                const float ce = lse - lg[tgt];
+                ce_stats_smoothed(ce_sum, n_sum, w_sum, u_sum, w, ce_smoothed(sm, ce, lse, wave_sum(xs), V), ce);
+            }
+        } else if (r.live) ce_stats<WT>(ce_sum, n_sum, w_sum, u_sum, w, lse - lg[tgt]);
     }
     if constexpr (WT) ce_end_w(red, ce_sum, n_sum, w_sum, u_sum, loss_part); else ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
 }
 
 // The same with the row held in registers (Vp <= 64 * KV): ONE pass over the logits instead of three passes of 4-byte loads, and every row
 // has its own wave from the start (the three-pass kernel: 31 us for 13 MB at the benchmark shape, a chain of dependent passes per row; this one 8).
+// Smoothing costs it one more wave reduction per row, over registers it already holds.
 template <typename CT, int KV, typename... W>
 __global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
                                                           const int* __restrict__ lengths, CT* __restrict__ dlogits,
                                                           float* __restrict__ loss_acc, float* __restrict__ loss_part, float inv_ntok, const float* __restrict__ ntok_dev,
                                                           const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp, W... wt) {
     constexpr bool WT = sizeof...(W) != 0;
+    constexpr bool SM = ce_has_smooth<W...>::value;
     constexpr bool BF = is_bf16<CT>::value;
     __shared__ float red[WT ? 16 : 8];
     inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const CeSmooth sm = ce_smooth(wt...);
     float ce_sum = 0.f, n_sum = 0.f, w_sum = 0.f, u_sum = 0.f;
     for (int row = blockIdx.x * 4 + wave; row < T * B; row += gridDim.x * 4) {
         const RowTok r = row_tok(row, B, T, lengths);
@@ -531,12 +571,21 @@ __global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restri
             for (int e = 0; e < 4; ++e) {
                 const int j = j0 + e;
                 const float pr = row_exp<BF>(x[4 * q + e] - lse);
-                g[e] = j < V ? (pr - (j == tgt ? 1.f : 0.f)) * scale : 0.f;
+                g[e] = j < V ? (pr - ce_target<SM>(j == tgt, sm)) * scale : 0.f;
             }
             if constexpr (BF) { const u32x2 pk = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])}; *reinterpret_cast<u32x2*>(dl + j0) = pk; }
             else { const f32x4 gv = {g[0], g[1], g[2], g[3]}; *reinterpret_cast<f32x4*>(dl + j0) = gv; }
         }
-        if (r.live) ce_stats<WT>(ce_sum, n_sum, w_sum, u_sum, w, lse - xt);
+        if constexpr (SM) {
+            // the sum of the logits over [0, V) only (row_load's fill of the columns behind V is for the max and the exp): KV additions in a lane, six in the wave
+            float xs = 0.f;
+#pragma unroll
+            for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xs += 4 * (lane + 64 * q) + e < V ? x[4 * q + e] : 0.f;
+            xs = wave_sum(xs);
+            if (r.live) ce_stats_smoothed(ce_sum, n_sum, w_sum, u_sum, w, ce_smoothed(sm, lse - xt, lse, xs, V), lse - xt);
+        } else if (r.live) ce_stats<WT>(ce_sum, n_sum, w_sum, u_sum, w, lse - xt);
     }
     if constexpr (WT) ce_end_w(red, ce_sum, n_sum, w_sum, u_sum, loss_part); else ce_end(red, ce_sum, n_sum, loss_acc, loss_part);
 }
@@ -1102,15 +1151,22 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
 #define BY_KV(Vp, ROWS) do { if ((Vp) <= 256) ROWS(4); else if ((Vp) <= 512) ROWS(8); else ROWS(16); } while (0)
 
 int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
-                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st, const CeWeights* weights) {
+                  const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st, const CeWeights* weights,
+                  const CeSmooth* smooth) {
     int g = cdiv(T * B, 4);
     float* part = (det.p && det.floats >= 1024) ? det.p : nullptr;      // loss_acc is zero on entry (lxo_impl_ce_loss)
-    const int nst = weights ? 4 : 2;                                    // statistics per workgroup slot
-    if (weights && !(det.p && det.floats >= 2048)) return -2;           // the four weighted statistics go through the ordered slots only
+    const bool four = weights || smooth;
+    const int nst = four ? 4 : 2;                                       // statistics per workgroup slot
+    if (four && !(det.p && det.floats >= 2048)) return -2;              // the four weighted / smoothed statistics go through the ordered slots only
     const CeWeights wt = weights ? *weights : CeWeights{};
+    const CeSmooth sm = smooth ? *smooth : CeSmooth{};
 #define CE_ARGS(CT_) logits, formula, lengths, (CT_*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp
-    // CE_WT(CT, KERNEL<...): KERNEL<...> or, with weights, KERNEL<..., CeWeights>
-#define CE_WT(CT_, ...) do { if (weights) LAUNCH((__VA_ARGS__, CeWeights>), g, CE_ARGS(CT_), wt); else LAUNCH((__VA_ARGS__>), g, CE_ARGS(CT_)); } while (0)
+    // CE_WT(CT, KERNEL<...): KERNEL<...> or, with weights, KERNEL<..., CeWeights>; with smoothing KERNEL<..., CeSmooth> and KERNEL<..., CeWeights, CeSmooth>
+#define CE_WT(CT_, ...) do { \
+        if (weights && smooth) LAUNCH((__VA_ARGS__, CeWeights, CeSmooth>), g, CE_ARGS(CT_), wt, sm); \
+        else if (smooth) LAUNCH((__VA_ARGS__, CeSmooth>), g, CE_ARGS(CT_), sm); \
+        else if (weights) LAUNCH((__VA_ARGS__, CeWeights>), g, CE_ARGS(CT_), wt); \
+        else LAUNCH((__VA_ARGS__>), g, CE_ARGS(CT_)); } while (0)
     if (Vp % 4 == 0 && Vp <= 1024 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0) {
         // a wave per row, the row in registers (one pass); the f32 parity mode keeps at most 512 workgroups (its ordered partial sums)
         if (g > (part ? 512 : 2048)) g = part ? 512 : 2048;

@@ -65,6 +65,7 @@ class Engine(object):
         self.chain_used = False
         self.chain_used_bwd = False
         self.chain_failures = 0           # steps a chain failed in (each was dropped or redone)
+        self.last_ce = None               # plain token-mean CE of the last synchronised train_step (whatever loss it optimised)
         self._nochain_shapes, self._nochain_shapes_bwd = set(), set()
         self._health_ring = None
         self._health_i = 0
@@ -407,6 +408,17 @@ class Engine(object):
             out.append(a)
         return out
 
+    @staticmethod
+    def _check_smoothing(who, label_smoothing):
+        """The label smoothing before any launch: a real number in [0, 1) -> float"""
+        try:
+            eps = float(label_smoothing)
+        except (TypeError, ValueError):
+            raise ValueError("%s: label_smoothing must be a number in [0, 1), got %r" % (who, label_smoothing))
+        if not (math.isfinite(eps) and 0.0 <= eps < 1.0 and float(np.float32(eps)) < 1.0):
+            raise ValueError("%s: label_smoothing must be a finite number in [0, 1), got %r" % (who, label_smoothing))
+        return eps
+
     def _weights_dev(self, w, dead):
         """f32 on the device, zero rows appended for the dead rows forward() added (weight 0 on a length of 0); a host array goes through pinned
         memory and an asynchronous copy, as the lengths do"""
@@ -422,12 +434,16 @@ class Engine(object):
             return t
         return t.pin_memory().to(self.device, non_blocking=True)
 
-    def loss(self, lengths, inv_ntok=None, ntok_dev=None, ntok_event=None, weights=None, row_weights=None, _padded=False):
+    def loss(self, lengths, inv_ntok=None, ntok_dev=None, ntok_event=None, weights=None, row_weights=None, _padded=False, label_smoothing=0.0):
         """Loss statistics + d(logits).  Either inv_ntok (host float) or ntok_dev (device float32 [1] = the global token count,
         e.g. from DataParallel.sum_count_async; the compute stream waits for ntok_event, the host does not).
         weights [B, T] / row_weights [B] (host arrays or device tensors, either or both): the weighted loss lxo_ce_loss_weighted -- token (b, t)
         weighs weights[b, t] * row_weights[b], of any sign; inv_ntok / ntok_dev are then its normaliser, whatever the caller chose, and the
-        statistics are the four {sum w CE, token count, sum w, sum CE}.  Without weights: {sum CE, token count}, as ever."""
+        statistics are the four {sum w CE, token count, sum w, sum CE}.  Without weights: {sum CE, token count}, as ever.
+        label_smoothing = eps in (0, 1): the smoothed loss lxo_ce_loss_smoothed -- a live row's target is (1 - eps) one-hot + eps / V over the
+        vocabulary, its loss L = (1 - eps) CE + eps (lse - mean logit) -- with or without weights; the statistics are then the four
+        {sum w L, token count, sum w, sum CE (plain)}.  0.0: the calls above, as without the argument.  Outside [0, 1): a ValueError before any launch."""
+        eps = self._check_smoothing("loss", label_smoothing)
         if weights is None and row_weights is None:
             self._bind_lengths(lengths)
             wt = wr = None
@@ -447,6 +463,11 @@ class Engine(object):
             self._ntok_dev = ntok_dev          # keep alive until the kernel has been enqueued
             if ntok_dev.is_cuda:               # allocated on the count stream, read on this one: the allocator must not hand the
                 ntok_dev.record_stream(torch.cuda.current_stream(self.device))   # block to a later upload before this kernel ran
+        if eps > 0.0:
+            self._ck(self.lib.lxo_ce_loss_smoothed(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), ctypes.c_float(eps), _p(wt), _p(wr),
+                                                   ctypes.c_float(0.0 if ntok_dev is not None else inv_ntok), _p(ntok_dev), self._stream()),
+                     "ce_loss_smoothed")
+            return self.region("loss")[:4]
         if wt is not None or wr is not None:
             self._ck(self.lib.lxo_ce_loss_weighted(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), _p(wt), _p(wr),
                                                    ctypes.c_float(0.0 if ntok_dev is not None else inv_ntok), _p(ntok_dev), self._stream()),
@@ -595,19 +616,25 @@ class Engine(object):
         self.pack()
 
     def train_step(self, img, formula, lengths, lr, clip=-1.0, dist=None, sync_loss=True, dropout=1.0, dropout_seed=None,
-                   weights=None, row_weights=None, norm=None):
+                   weights=None, row_weights=None, norm=None, label_smoothing=0.0):
         """One optimisation step of img2seq.py:_run_train's body.  Returns the batch loss
         (token mean over the global batch) or None when sync_loss is False.  dropout = config.dropout
         (keep probability, img2seq.py:166); masks are keyed by (dropout_seed or a per-engine step counter).
         weights [B, T] / row_weights [B] (host arrays or device tensors): the step minimises sum_{b,t} weights[b, t] row_weights[b] CE[b, t] / norm
         (loss()); norm = None: the global token count, as without weights (data parallel: the device-side count); norm = a float: the caller's
-        own normaliser, the GLOBAL one under dist.  Returns that weighted loss."""
+        own normaliser, the GLOBAL one under dist.  Returns that weighted loss.
+        label_smoothing in (0, 1): the step minimises the smoothed loss (loss()), weighted or not, and returns it; 0.0: the step without the argument.
+        Either way a synchronised step leaves the PLAIN token-mean CE of the batch in self.last_ce (under dist: of the global batch), what a
+        perplexity is made of."""
+        eps = self._check_smoothing("train_step", label_smoothing)
         weighted = weights is not None or row_weights is not None
         if weighted:
             weights, row_weights = self._check_weights("train_step", weights, row_weights, int(img.shape[0]), int(formula.shape[1]))
         if norm is not None and not (math.isfinite(float(norm)) and float(norm) != 0.0):
             raise ValueError("train_step: norm must be a finite non-zero number, got %r" % (norm,))
         wkw = dict(weights=weights, row_weights=row_weights) if weighted else {}
+        if eps > 0.0:
+            wkw["label_smoothing"] = eps
         drop = None
         if dropout is not None and 0.0 < float(dropout) < 1.0:
             self.drop_step = getattr(self, "drop_step", 0) + 1
@@ -649,6 +676,7 @@ class Engine(object):
                                        dropout_seed=drop[1] if drop is not None else None, norm=norm, **wkw)
             finally:
                 self._redoing = False
+        self.last_ce = float(s[3 if len(s) == 4 else 0]) / max(float(s[1]), 1.0)
         return float(s[0]) / (float(s[1]) if norm is None else float(norm))
 
     def mrt_grads(self, img, cand, cand_lengths, group_sizes, cost, alpha, dropout=None):

@@ -44,7 +44,13 @@ class Img2SeqModel(BaseModel):
                              max_steps=getattr(cfg, "max_length_formula", 150) + 2)
 
     def build_train(self, config):
-        """Reference: model/img2seq.py:34-40."""
+        """Reference: model/img2seq.py:34-40.  The training config's optional "label_smoothing" key (a number in [0, 1), default 0.0) makes every
+        cross-entropy step minimise the smoothed loss (Engine.train_step(label_smoothing=)); it does not combine with the "mrt" key."""
+        from ..engine import Engine
+        self._label_smoothing = Engine._check_smoothing("training config: \"label_smoothing\"", getattr(config, "label_smoothing", 0.0))
+        if self._label_smoothing > 0.0 and getattr(config, "mrt", None) is not None:
+            raise ValueError("training config: \"label_smoothing\" and \"mrt\" do not combine -- the minimum-risk step does not smooth its targets; "
+                             "drop one of the two keys")
         self.logger.info("Building model...")
         self._build_engine()
         self._lr_method = config.lr_method.lower()
@@ -90,6 +96,8 @@ class Img2SeqModel(BaseModel):
             raise ValueError("dropout is a keep probability and must be > 0, got {}".format(keep))
         mrt = getattr(config, "mrt", None)
         if mrt is not None:
+            if getattr(self, "_label_smoothing", 0.0) > 0.0 or getattr(config, "label_smoothing", 0.0):
+                raise ValueError("training config: \"label_smoothing\" and \"mrt\" do not combine")
             return self._run_train_mrt(config, train_set, val_set, epoch, lr_schedule, mrt, keep)
         depth = int(getattr(config, "prefetch_depth", 2))
         # steps per pass are counted once per (dataset, batch size, world): another train() call with other arguments must not reuse the count
@@ -100,6 +108,8 @@ class Img2SeqModel(BaseModel):
             nbatches = len(batches)        # steps this pass really takes (per shape bucket), what the LR schedule was scaled with
             self._dp_nbatches = (key, nbatches)   # the same set every epoch: counted once
         prog = Progbar(nbatches)
+        eps = getattr(self, "_label_smoothing", 0.0)
+        smooth = dict(label_smoothing=eps) if eps > 0.0 else {}
         if depth > 0:
             feed = Prefetcher(train_set, batch_size, self._vocab.id_pad, self._vocab.id_end, device=self.engine.device,
                               depth=depth, batches=batches)
@@ -112,8 +122,9 @@ class Img2SeqModel(BaseModel):
             it = sync_feed()
         for i, (img, formula, lengths) in enumerate(it):
             loss_eval = self.engine.train_step(img, formula, lengths, lr_schedule.lr, clip=self._clip, dist=self.dist,
-                                               dropout=keep)
-            prog.update(i + 1, [("loss", loss_eval), ("perplexity", np.exp(loss_eval)), ("lr", lr_schedule.lr)])
+                                               dropout=keep, **smooth)
+            # the loss the step optimised; the perplexity of the PLAIN cross-entropy, smoothed or not: comparable between runs
+            prog.update(i + 1, [("loss", loss_eval), ("perplexity", np.exp(self.engine.last_ce if smooth else loss_eval)), ("lr", lr_schedule.lr)])
             lr_schedule.update(batch_no=epoch * nbatches + i)
         self.logger.info("- Training: {}".format(prog.info))
         sub = "formulas_val/" if rank == 0 else "formulas_val_rank%d/" % rank    # every rank scores (keeps LR schedules equal)

@@ -43,7 +43,8 @@ class Img2SeqFunction(torch.autograd.Function):
             drop = (module.keep_prob, module._drop_seed)
         eng.forward(img, formula, dropout=drop)
         n_tok = int(np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths).sum())
-        stats = eng.loss(lengths, 1.0 / float(n_tok))                  # device [sum of CE, token count]
+        # device [sum of CE, token count]; label smoothing while training only, as dropout: [sum of L, token count, ...] (lxo_ce_loss_smoothed)
+        stats = eng.loss(lengths, 1.0 / float(n_tok), label_smoothing=module.label_smoothing if module.training else 0.0)
         ctx.module = module
         return (stats[0] / stats[1]).reshape(())
 
@@ -57,8 +58,9 @@ class Img2SeqFunction(torch.autograd.Function):
 class Img2Seq(nn.Module):
     """CNN encoder + attention LSTM decoder of the reference (model/encoder.py, model/decoder.py) as one module."""
 
-    def __init__(self, n_tok, dims=None, dtype="bf16", device="cuda:0", seed=0, keep_prob=1.0, lib=None):
+    def __init__(self, n_tok, dims=None, dtype="bf16", device="cuda:0", seed=0, keep_prob=1.0, lib=None, label_smoothing=0.0):
         super().__init__()
+        self.label_smoothing = Engine._check_smoothing("Img2Seq", label_smoothing)      # in [0, 1); used while self.training, the plain loss in eval()
         self.engine = Engine(n_tok, dims=dims, dtype=dtype, device=device, seed=seed, lib=lib)
         # the parameter shares the engine's buffer: optimizers update the engine in place
         self.flat = nn.Parameter(self.engine.params, requires_grad=True)

@@ -1,10 +1,11 @@
-"""What the weighted loss and the minimum-risk step cost, at the benchmark shape (B = 64, 128 x 512, V = 500, T = 101, bf16).
+"""What the weighted loss, label smoothing and the minimum-risk step cost, at the benchmark shape (B = 64, 128 x 512, V = 500, T = 101, bf16).
 
 1. The loss launch (Engine.loss behind one forward: the memset, the CE kernel, the ordered reduction of its statistics) without weights --
-   lxo_ce_loss_fwd_bwd, the yardstick -- and with device row_weights (lxo_ce_loss_weighted), timed by device events over --launches
-   back-to-back calls, in alternating rounds of one process; medians of --reps.
-2. Engine.mrt_step (16 images x 4 candidates = the same 64 rows) against Engine.train_step on those rows, host clock around steps that end in
-   the loss copy, the same way.
+   lxo_ce_loss_fwd_bwd, the yardstick --, with device row_weights (lxo_ce_loss_weighted), and with label_smoothing = 0.1 without weights and
+   with the row_weights (lxo_ce_loss_smoothed), timed by device events over --launches back-to-back calls, in alternating rounds of one
+   process; medians of --reps.
+2. Engine.mrt_step (16 images x 4 candidates = the same 64 rows) and Engine.train_step(label_smoothing=0.1) against Engine.train_step on those
+   rows, host clock around steps that end in the loss copy, the same way.
 Prints one line per arm: median (min..max)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,7 +40,9 @@ def report(name, v, unit, base=None):
 eng = Engine(V, dtype="bf16", seed=0)
 eng.forward(img_d, f_d)
 arms = [("loss, no weights (lxo_ce_loss_fwd_bwd)", lambda: eng.loss(l_d, 1.0 / n_tok)),
-        ("loss, row_weights (lxo_ce_loss_weighted)", lambda: eng.loss(l_d, 1.0 / n_tok, row_weights=w_row))]
+        ("loss, row_weights (lxo_ce_loss_weighted)", lambda: eng.loss(l_d, 1.0 / n_tok, row_weights=w_row)),
+        ("loss, label_smoothing 0.1 (lxo_ce_loss_smoothed)", lambda: eng.loss(l_d, 1.0 / n_tok, label_smoothing=0.1)),
+        ("loss, label_smoothing 0.1 + row_weights (lxo_ce_loss_smoothed)", lambda: eng.loss(l_d, 1.0 / n_tok, row_weights=w_row, label_smoothing=0.1))]
 
 
 def timed_launches(fn):
@@ -67,9 +70,10 @@ for (name, _), v in zip(arms, per):
 # ---- 2. mrt_step against train_step on the same 64 rows
 gs = np.full(G, B // G)
 cost = np.random.default_rng(2).uniform(0.0, 1.0, size=B).astype(np.float32)
-e_ce, e_mrt = Engine(V, dtype="bf16", seed=0), Engine(V, dtype="bf16", seed=0)
+e_ce, e_ls, e_mrt = Engine(V, dtype="bf16", seed=0), Engine(V, dtype="bf16", seed=0), Engine(V, dtype="bf16", seed=0)
 img_rep = np.ascontiguousarray(img[np.repeat(np.arange(G), gs)])
 arms = [("train_step, 64 rows", lambda: e_ce.train_step(img_rep, f, l, 1e-4)),
+        ("train_step(label_smoothing=0.1), 64 rows", lambda: e_ls.train_step(img_rep, f, l, 1e-4, label_smoothing=0.1)),
         ("mrt_step, 16 images x 4 candidates", lambda: e_mrt.mrt_step(img[:G], f, l, gs, cost, 1e-4, 0.005))]
 
 
@@ -92,4 +96,5 @@ base = None
 for (name, _), v in zip(arms, per):
     m = report(name, v, "ms per step (host arrays in, loss out)", base)
     base = m if base is None else base
-print("chains: train_step %s/%s, mrt_step %s/%s" % (e_ce.chain_used, e_ce.chain_used_bwd, e_mrt.chain_used, e_mrt.chain_used_bwd))
+print("chains: train_step %s/%s, train_step(label_smoothing) %s/%s, mrt_step %s/%s" % (e_ce.chain_used, e_ce.chain_used_bwd, e_ls.chain_used,
+                                                                                      e_ls.chain_used_bwd, e_mrt.chain_used, e_mrt.chain_used_bwd))
