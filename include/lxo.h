@@ -218,6 +218,16 @@ int lxo_set_encoder_side_stream(void* stream);
  * (attention_cell.py:58-89) under teacher forcing, logits for every step. */
 int lxo_decoder_train_fwd(const lxo_shape* s, const float* params, const void* wpack, void* ws,
                           const int32_t* formula, void* stream);
+/* The same for a caller that knows the formula lengths (device int32 [B], the array the loss calls take; the dead rows that fill a batch up carry
+ * length 0).  Where the persistent forward chain runs, a pair (t, b) with t >= lengths[b] is DEAD: its attention workgroups stream nothing.  What
+ * a dead position then holds: ws region "alpha" row (t, b) and the ctx columns of its record (ws regions "rec" / "recb", slot t + 1) are exact
+ * zeros; h, c, the gates, att_h, o and the logits are what the step computes from that zero context -- finite, and a function of this call's
+ * inputs only, never of what the workspace held before.  The loss, lxo_score_tokens and lxo_train_bwd read a dead position only to multiply it
+ * by an exact zero.  Every live position (t < lengths[b]) holds lxo_decoder_train_fwd's value bit for bit, whatever the other rows' lengths.
+ * On every other path -- the launch-per-step kernels, f32, a shape the chain does not take -- and with lengths == NULL the call IS
+ * lxo_decoder_train_fwd: every padded position is computed. */
+int lxo_decoder_train_fwd_live(const lxo_shape* s, const float* params, const void* wpack, void* ws,
+                               const int32_t* formula, const int32_t* lengths, void* stream);
 /* loss of model/img2seq.py:68-75 and d(loss)/d(logits).  inv_ntok = 1 / (number of
  * unmasked tokens in the GLOBAL batch).  ws region "loss" = {sum CE, token count}.  Target ids outside [0, V) are
  * clamped into it (< 0 -> 0, >= V -> V - 1), as lxo_score_tokens does; d(logits) is 0 in the padding columns [V, Vp). */

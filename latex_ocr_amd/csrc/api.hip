@@ -117,6 +117,13 @@ extern "C" int lxo_decoder_train_fwd(const lxo_shape* s, const float* params, co
     CHECK_LAUNCH(lxo_impl_decoder_train_fwd(P, params, wpack, ws, formula, (hipStream_t)stream), "lxo_decoder_train_fwd");
     return 0;
 }
+extern "C" int lxo_decoder_train_fwd_live(const lxo_shape* s, const float* params, const void* wpack, void* ws,
+                                          const int32_t* formula, const int32_t* lengths, void* stream) {
+    MAKE_PLAN(P, s);
+    if (s->T <= 0) return fail(-1, "T must be positive");
+    CHECK_LAUNCH(lxo_impl_decoder_train_fwd(P, params, wpack, ws, formula, (hipStream_t)stream, lengths), "lxo_decoder_train_fwd_live");
+    return 0;
+}
 extern "C" int lxo_ce_loss_fwd_bwd(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
                                    float inv_ntok, void* stream) {
     MAKE_PLAN(P, s);

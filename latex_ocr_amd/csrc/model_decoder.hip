@@ -297,8 +297,9 @@ static int fwd_setup(const Train& w, const int* formula) {
     return nt(P, false, true, false, P.ws<void>(ws, W_EMB_IN), P.Dp, P.pk(w.wp, K_LSTM_XT), P.Dp, w.zx, 4 * U, T * B, 4 * U, P.Dp,
               w.prm + P.poff[P_LSTM_B], 0, false, st);
 }
-// the whole recurrence in one launch: 8 XCD-local chains of B / 8 samples (xdec.hip).  *ran stays false where the shape does not qualify (-2)
-static int fwd_chain(const Train& w, bool* ran) {
+// the whole recurrence in one launch: 8 XCD-local chains of B / 8 samples (xdec.hip).  *ran stays false where the shape does not qualify (-2).
+// lengths (device, [B], nullable): the chain streams nothing for the steps behind a row's end (XDecFwd.lengths)
+static int fwd_chain(const Train& w, const int* lengths, bool* ran) {
     const Plan& P = w.P; void* ws = w.ws;
     RC(mirror_oh(P, ws, 0, P.s.B, w.st));
     XDecFwd x; memset(&x, 0, sizeof(x));
@@ -307,6 +308,7 @@ static int fwd_chain(const Train& w, bool* ran) {
     x.zx = w.zx; x.gates = w.gates; x.atth = w.atth; x.alpha = w.alpha;
     x.T = P.s.T; x.Rp = P.Rp;
     x.dr = P.drop(0, 0);
+    x.lengths = lengths;
     LxoTimed tm("xdec_fwd", "chain", (double)P.s.T * P.s.B * P.R * (P.s.E + P.s.C) * P.esz, w.st);
     const int rc = lxo_launch_xdec_fwd(x, P.s.U, P.s.O, P.s.C, P.s.E, w.st);
     if (rc == 0) *ran = true;
@@ -340,11 +342,12 @@ static int fwd_logits(const Train& w) {
 
 // All B rows run all T steps, padded ones included, as the reference does (decoder.py:57: dynamic_rnn without sequence_length; the padded
 // steps are masked in the loss, img2seq.py:68-71).  One stream, but for the split-K loop's second half-batch under `dual`.
-int lxo_impl_decoder_train_fwd(const Plan& P, const float* prm, const void* wp, void* ws, const int* formula, hipStream_t st) {
+// lengths (lxo_decoder_train_fwd_live; null: none): only the persistent chain reads them -- the loops compute every position as before.
+int lxo_impl_decoder_train_fwd(const Plan& P, const float* prm, const void* wp, void* ws, const int* formula, hipStream_t st, const int* lengths) {
     const Train w = train_of(P, prm, wp, ws, st);
     RC(fwd_setup(w, formula));
     bool chain = false;
-    if (w.sp.try_chain) RC(fwd_chain(w, &chain));
+    if (w.sp.try_chain) RC(fwd_chain(w, lengths, &chain));
     // no chain in this call: clear its tickets and its error word (the loss kernel and lxo_chain_guard read it; a reused workspace may hold another shape's bytes here)
     if (P.bf && !chain) HIPRC(hipMemsetAsync(chain_block(P, ws, kChainFwd), 0, kXDecSyncBytes, st));
     if (w.sp.loop == StepPath::SplitK) RC(fwd_splitk_loop(w));

@@ -28,6 +28,9 @@ struct XDecFwd {
     int T, B, R, Rp, REC, RECB;
     Drop dr;                          // dropout of h and o (thr == 0: off); dr.t is set per step
     unsigned long long* dbg;          // measurement aid (null = off): [256 workgroups][T][16] 100 MHz timestamps at the phase boundaries (tools/xdec_stamps.py)
+    const int* lengths;               // [B] formula lengths (nullable: every pair is live).  A pair (t, b) with t >= lengths[b] is DEAD: its attention
+                                      // workgroups stream nothing, its ctx and alpha row are exact zeros, the rest of its record is what the step computes
+                                      // from that zero context (lxo_decoder_train_fwd_live in include/lxo.h)
 };
 
 // 0 = launched; -2 = the shape does not qualify (the caller runs the launch-per-step chain instead)

@@ -22,8 +22,10 @@
 // 32 workgroups of the grid landed on its XCD) flags an error word and stops waiting; the host checks the word after the first use
 // of this path and falls back to the launch-per-step chain (engine.py).
 // The backward chain (xdec_bwd_kernel, further down) runs the same steps in reverse; there a (step, sample) pair behind the sample's formula end
-// is recognised by its all-zero d_ctx row and streams nothing (37 % of the pairs at the benchmark's lengths).  The forward chain knows nothing of
-// lengths: its record is kept -- and tested -- at padded positions too.
+// is recognised by its all-zero d_ctx row and streams nothing (37 % of the pairs at the benchmark's lengths).  The forward chain is told the
+// lengths where the caller has them (XDecFwd.lengths, lxo_decoder_train_fwd_live): a pair behind its row's end streams nothing in P3 either, its
+// context and alpha row are exact zeros and the rest of its record is what the step makes of that zero context.  Without lengths
+// (lxo_decoder_train_fwd) its record is kept -- and tested -- at padded positions too.
 #include "xdec.h"
 #include "drop.h"
 #include "api_util.h"
@@ -452,12 +454,13 @@ LXO_DEV void xdec_att_h(float (&ah)[4], const XChain& c, int ab, rsrc_t rll_ah, 
 
 // P3's walk over the chunk, direction rev.  Entering: block 0 in A and block 1 in B (requested at the end of the previous step's P3).  Each
 // buffer is refilled right after its block is computed -- with the block two ahead, or, at the end of the chunk, with the NEXT STEP's first two
-// blocks (its direction is the other one): they land during P4 / P1 / P2
+// blocks (its direction is the other one): they land during P4 / P1 / P2.  nwalk: ro.nblk, or 0 for a step that walks nothing (a dead pair
+// of the forward chain: no block is computed and none is requested; what the last walk asked for stays in the buffers, unread).  A scalar
 template <int ATT_U, bool EXPD>
-LXO_DEV void xdec_walk(u32x4 (&xiA)[ATT_U], u32x2 (&xaA)[ATT_U], u32x4 (&xiB)[ATT_U], u32x2 (&xaB)[ATT_U], const XRole<ATT_U>& ro, int rev,
+LXO_DEV void xdec_walk(u32x4 (&xiA)[ATT_U], u32x2 (&xaA)[ATT_U], u32x4 (&xiB)[ATT_U], u32x2 (&xaB)[ATT_U], const XRole<ATT_U>& ro, int nwalk, int rev,
                        const float (&ah)[4], const float (&bt)[4], float& m, float& l, float (&acc)[8], float* sc, int lane) {
     const int nblk = ro.nblk;
-    for (int it = 0; it < nblk; it += 2) {
+    for (int it = 0; it < nwalk; it += 2) {
         att_block<ATT_U, EXPD>(xiA, xaA, ro.XBASE(it, rev), ro.an, ah, bt, m, l, acc, sc, lane);
         __builtin_amdgcn_sched_barrier(0);
         att_load<ATT_U>(xiA, xaA, ro.imq, ro.aiq, (it + 2 < nblk) ? ro.XBASE(it + 2, rev) : ro.XBASE(0, rev ^ 1), ro.anq, lane);
@@ -528,7 +531,8 @@ LXO_DEV void xdec_o_fetch(u32x4 (&a)[4], const P& p, const XChain& c, long long 
 
 // P4: merge the chunk partials of the chain's samples into ctx -- the A tile of the o projection (actx) and, for the 16 channels this
 // workgroup owns, the record (slot sn).  Four groups of 128 threads split the NB samples; a thread holds 4 channels.
-// SM: the samples' softmax max and 1 / sum are kept too (smax, sinv: what alpha needs).  arrived: measurement only (null = off), stamped once the polled partials are there
+// SM: the samples' softmax max and 1 / sum are kept too (smax, sinv: what alpha needs), and a sample none of whose chunks reports a sum (a dead
+// pair of the forward chain: every partial is zero) merges to an exact zero context instead of 0 / 0.  arrived: measurement only (null = off), stamped once the polled partials are there
 template <int NB, bool PP, bool SM, class P>
 LXO_DEV void xdec_p4_merge(const P& p, const XChain& c, long long sn, int t, float (*wgt)[32 / NB], float* smax, float* sinv, float (*redc)[XC],
                            bf16_t (*actx)[XC + 8], unsigned long long* arrived) {
@@ -594,7 +598,8 @@ LXO_DEV void xdec_p4_merge(const P& p, const XChain& c, long long sn, int t, flo
         float ll = st_l * w;
 #pragma unroll
         for (int o = NQ / 2; o > 0; o >>= 1) ll += __shfl_xor(ll, o);
-        const float inv = 1.0f / ll;
+        float inv = 1.0f / ll;
+        if constexpr (SM) inv = ll > 0.f ? inv : 0.f;            // (a live sample's sum is >= 1: its own values are untouched)
         if (tid < NB * NQ) {
             (&wgt[0][0])[tid] = w * inv;
             if constexpr (SM) { if ((tid & (NQ - 1)) == 0) { smax[tid / NQ] = mm; sinv[tid / NQ] = inv; } }
@@ -708,7 +713,7 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
     __shared__ float cst[8][16];                                 // c state of this workgroup's 16 units (lives here for all T steps)
     __shared__ float wgt[NB][NQ], smax[NB], sinv[NB];
     __shared__ float wred[2 * XW];
-    __shared__ int s_rank, s_dead;
+    __shared__ int s_rank, s_dead, s_alen;
 
     // A forward-chain workgroup of two and more samples must allocate all 256 VGPRs per lane (granules of 8: v254 named = 256), so that
     // 8 waves x 256 fill the CU's register file and no foreign wave fits beside it: one that did would stretch this member's phases and with
@@ -732,6 +737,11 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
     if (tid < NB * 16) cst[tid >> 4][tid & 15] = p.cs[(long long)(b0 + (tid >> 4)) * XU + u0 + (tid & 15)];
 
     const XRole<ATT_U> ro = xdec_role<NB, ATT_U>(c, p.R, p.img, EXPD ? p.att_exp : p.att_img);
+    // the formula length of this workgroup's attention sample, read once per launch (no lengths: every step is live) and kept in LDS: the kernel has no
+    // scalar register to spare for a value that lives through the whole step loop (it keeps 12 .. 21 of them in VGPR lanes as it is); a uniform LDS read
+    // per step, asked for in front of the att_h poll, is hidden by that poll.  Step t is DEAD for the sample when t >= s_alen.  P3 makes the flag a
+    // scalar (readfirstlane): the walk's trip count hangs on it and must stay on the scalar ALU
+    if (tid == 0) s_alen = p.lengths ? p.lengths[ro.ab] : T;       // (read behind P1's workgroup barriers)
     Drop dr = p.dr;
     unsigned ph = 0;
     u32x4 xiA[ATT_U], xiB[ATT_U]; u32x2 xaA[ATT_U], xaB[ATT_U];
@@ -831,17 +841,21 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) pzn[q] = zr[q * XU];
             }
+            const int alen_v = s_alen;
             float ah[4];
             xdec_att_h<EXPD>(ah, c, ro.ab, rll_ah, (unsigned)(t + 1));
+            const bool live = t < __builtin_amdgcn_readfirstlane(alen_v);
             float m = -3.0e38f, l = 0.f, acc[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = 0.f;
             const int rev = t & 1;
-            if constexpr (kPF == 0) xdec_walk<ATT_U, EXPD>(xiA, xaA, xiB, xaB, ro, rev, ah, bt, m, l, acc, sc, lane);
+            // a dead pair walks no block and requests none (a row that is dead stays dead: the blocks its last live step asked for are never read);
+            // it publishes the partial (max -3e38, sum 0, context 0) with this step's tags like any other, so every poll of the step is served
+            if constexpr (kPF == 0) xdec_walk<ATT_U, EXPD>(xiA, xaA, xiB, xaB, ro, live ? ro.nblk : 0, rev, ah, bt, m, l, acc, sc, lane);
             else {
                 // the chunk ends with nothing in flight (the next step's first blocks are requested elsewhere: kPF).  Peeled so that every load is
                 // unconditional on its path (a load behind a branch makes hipcc wait vmcnt(0) at the join)
-                const int nblk = ro.nblk, an = ro.an, anq = ro.anq;
+                const int nblk = live ? ro.nblk : 0, an = ro.an, anq = ro.anq;      // (a dead pair computes nothing; these variants still request its first blocks)
                 int it = 0;
                 for (; it + 3 < nblk; it += 2) {
                     att_block<ATT_U, EXPD>(xiA, xaA, ro.XBASE(it, rev), an, ah, bt, m, l, acc, sc, lane);
@@ -875,7 +889,10 @@ __global__ __launch_bounds__(512) void xdec_fwd_kernel(XDecFwd p) {
             {
                 const float mm = smax[ro.as], inv = sinv[ro.as];
                 float* al = p.alpha + (sp + ro.ab) * p.Rp + ro.ar0;
-                for (int r = tid; r < ro.an; r += 512) al[r] = __expf(sc[r] - mm) * inv;
+                // a dead pair: exact zeros (sc holds an earlier step's scores, or nothing).  A select per element: the loop as two arms of a branch
+                // put 20 more scalars into VGPR lanes
+                const int alen_a = s_alen;
+                for (int r = tid; r < ro.an; r += 512) { const float a = __expf(sc[r] - mm) * inv; al[r] = t < alen_a ? a : 0.f; }
             }
             __syncthreads();
             xdec_o_proj<NB, 16>(a, p, c, sn, t, &dr, wow, actx, red, ll_o);
@@ -1172,7 +1189,7 @@ __global__ __launch_bounds__(512) void xdec_dec_kernel(XDecDec p) {
             float m = -3.0e38f, l = 0.f, acc[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-            xdec_walk<ATT_U, true>(xiA, xaA, xiB, xaB, ro, tg & 1, ah, bt, m, l, acc, nullptr, lane);      // (no raw scores: the decode keeps no alpha)
+            xdec_walk<ATT_U, true>(xiA, xaA, xiB, xaB, ro, ro.nblk, tg & 1, ah, bt, m, l, acc, nullptr, lane);      // (no raw scores: the decode keeps no alpha)
             xdec_p3_publish<NQ, PP>(m, l, acc, c, ro.ab, ro.aq, t, p.part, wred, redc);
         }
         if constexpr (!PP) xbar(xsync, rank, ++ph, err, &s_dead);
@@ -1214,7 +1231,8 @@ int launch_dec_nb(const XDecDec& p, hipStream_t st) { return p.allow ? launch_de
 // exact zeros.  The kernel has no length input; the sample's workgroups see it on the row itself and stream nothing in Q2 (zeros into their d_e
 // columns, a zero d_att_h partial, no request for the next step either).  The protocol is untouched -- every poll, barrier and hand-over store of
 // a step stays, nobody's work moves to another workgroup, a chain still waits for its slowest member; what the live samples' workgroups gain is the
-// memory bandwidth the dead ones no longer take.  The forward chain computes padded positions as before (its record is compared at all positions).
+// memory bandwidth the dead ones no longer take.  The forward chain leaves the same pairs silent where it is given the lengths
+// (XDecFwd.lengths); whether it did makes no difference here: the test is on d_ctx, and the forward values of a dead pair only meet exact zeros.
 template <int ATT_U>
 LXO_DEV void attb_load(u32x4 (&xi)[ATT_U], u32x2 (&xa)[ATT_U], float (&al)[ATT_U], rsrc_t rim, rsrc_t rai, rsrc_t ral, int base, int an, int lane) {
 #pragma unroll

@@ -232,10 +232,13 @@ class Engine(object):
         return slot["dev"][:n]
 
     # ---------------------------------------------------------------- steps --
-    def forward(self, img, formula, dropout=None, phase_hook=None, before_decoder=None):
+    def forward(self, img, formula, dropout=None, phase_hook=None, before_decoder=None, lengths=None):
         """Encoder + teacher-forced decoder; leaves logits in the workspace.  dropout = (keep_prob, seed)
         applies tf.nn.dropout on h and o (attention_cell.py:72,83) with this step's counter-based masks;
-        backward() regenerates the same masks from the bound shape."""
+        backward() regenerates the same masks from the bound shape.
+        lengths [B] (host array or device tensor; None: every position is computed): the formula lengths, bound here as loss() would bind them
+        (self._lengths).  The persistent forward chain then streams nothing for the steps behind a row's end (lxo_decoder_train_fwd_live): the
+        record of such a position is not the padded step's any more -- exact zeros in alpha and ctx -- and only positions t < lengths[b] may be read."""
         B, H, W = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
         T = int(formula.shape[1])
         # a batch the persistent chains do not take (the reference trains at 3, buckets and evaluates at 20: configs/training.json:6,
@@ -267,6 +270,8 @@ class Engine(object):
             self.shape.dropout_seed = int(dropout[1]) & 0x7FFFFFFF
         self._img = self._to_dev(img, torch.uint8)
         self._formula = self._to_dev(formula, torch.int32)
+        if lengths is not None:
+            self._bind_lengths(lengths)                            # (behind ensure(): the dead rows are counted on the chain batch)
         st = self._stream()
         self._bind_side()
         self._ck(self.lib.lxo_encoder_fwd(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), _p(self._img), st), "encoder_fwd")
@@ -276,13 +281,21 @@ class Engine(object):
             # data parallel: the token-count all-reduce (its own stream) must be OFF the GPU before the persistent decoder chain starts --
             # the chain wants every CU, and a collective kernel that waits for a late rank would hold some of them
             torch.cuda.current_stream(self.device).wait_event(before_decoder)
-        self._ck(self.lib.lxo_decoder_train_fwd(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), _p(self._formula), st),
-                 "decoder_train_fwd")
+        self._decoder_fwd(st, lengths is not None)
         if (not self._xdec_checked and self.dtype == _abi.LXO_BF16 and self.step_kernels == 0 and self.device.type == "cuda"
                 and (B, H, W) not in self._nochain_shapes):
             if self._check_chain():
-                self._ck(self.lib.lxo_decoder_train_fwd(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), _p(self._formula), st),
-                         "decoder_train_fwd")
+                self._decoder_fwd(st, lengths is not None)
+
+    def _decoder_fwd(self, st, live):
+        """The teacher-forced decoder on the bound shape and formula; live: with the bound lengths (self._lengths), for a caller that reads no
+        position behind a row's end"""
+        if live:
+            self._ck(self.lib.lxo_decoder_train_fwd_live(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), _p(self._formula),
+                                                         _p(self._lengths), st), "decoder_train_fwd_live")
+        else:
+            self._ck(self.lib.lxo_decoder_train_fwd(self.sref(), _p(self.params), _p(self.wpack), _p(self.ws), _p(self._formula), st),
+                     "decoder_train_fwd")
 
     def chain_status(self, backward=False):
         """(used, error) of the persistent XCD-local decoder chain (csrc/xdec.hip) in the last lxo_decoder_train_fwd (backward=True: the
@@ -434,7 +447,8 @@ class Engine(object):
             return t
         return t.pin_memory().to(self.device, non_blocking=True)
 
-    def loss(self, lengths, inv_ntok=None, ntok_dev=None, ntok_event=None, weights=None, row_weights=None, _padded=False, label_smoothing=0.0):
+    def loss(self, lengths, inv_ntok=None, ntok_dev=None, ntok_event=None, weights=None, row_weights=None, _padded=False, label_smoothing=0.0,
+             _bound=False):
         """Loss statistics + d(logits).  Either inv_ntok (host float) or ntok_dev (device float32 [1] = the global token count,
         e.g. from DataParallel.sum_count_async; the compute stream waits for ntok_event, the host does not).
         weights [B, T] / row_weights [B] (host arrays or device tensors, either or both): the weighted loss lxo_ce_loss_weighted -- token (b, t)
@@ -444,8 +458,11 @@ class Engine(object):
         vocabulary, its loss L = (1 - eps) CE + eps (lse - mean logit) -- with or without weights; the statistics are then the four
         {sum w L, token count, sum w, sum CE (plain)}.  0.0: the calls above, as without the argument.  Outside [0, 1): a ValueError before any launch."""
         eps = self._check_smoothing("loss", label_smoothing)
+        if _bound:
+            lengths = None                                         # (train_step: forward() has bound these lengths already -- no second upload)
         if weights is None and row_weights is None:
-            self._bind_lengths(lengths)
+            if lengths is not None:
+                self._bind_lengths(lengths)
             wt = wr = None
         else:
             live = int(getattr(self, "live_B", self.shape.B))
@@ -649,11 +666,11 @@ class Engine(object):
         if dist is not None and norm is None:
             # the global token count travels rank -> device -> all-reduce -> loss kernel; no host sync inside the step
             ntok, ev = dist.sum_count_async(n_local)
-            self.forward(img, formula, dropout=drop, before_decoder=ev)
-            stats = self.loss(lengths, ntok_dev=ntok, ntok_event=ev, **wkw)
+            self.forward(img, formula, dropout=drop, before_decoder=ev, lengths=lengths)
+            stats = self.loss(lengths, ntok_dev=ntok, ntok_event=ev, _bound=True, **wkw)
         else:
-            self.forward(img, formula, dropout=drop)
-            stats = self.loss(lengths, 1.0 / (float(n_local) if norm is None else float(norm)), **wkw)
+            self.forward(img, formula, dropout=drop, lengths=lengths)
+            stats = self.loss(lengths, 1.0 / (float(n_local) if norm is None else float(norm)), _bound=True, **wkw)
         self.backward(comm=dist.reduce_range_fn(self.grads) if dist is not None else None)
         if dist is not None:
             dist.finish()
@@ -1038,12 +1055,10 @@ class Engine(object):
 
     def _score_piece(self, img, formula, lengths, top1_on, k=0, al=None):
         while True:
-            self.forward(img, formula)
+            self.forward(img, formula, lengths=np.asarray(lengths, dtype=np.int32).reshape(-1))      # (scoring reads t < lengths[b] only)
             B, T = int(self.shape.B), int(self.shape.T)
             live, n = int(self.live_B), B * T
-            ln = np.zeros(B, np.int32)
-            ln[:live] = lengths                                     # the dead rows forward() appended: length 0, logp 0 / top1 -1
-            ln_dev = self._lengths_dev(ln)
+            ln_dev = self._lengths                                  # zero-filled for the dead rows forward() appended: length 0, logp 0 / top1 -1
             chain = self._chains_possible()
             # ONE device buffer and one copy to the host: logp | top1 | seq | the forward chain's sync words (chain_status's slice)
             # (with alternatives: + ids [n, k] | their logp [n, k] | rank | entropy in front of the sync words)
