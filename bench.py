@@ -9,10 +9,14 @@ decoder forward, loss, BPTT, Adam, weight re-pack [+ gradient all-reduce]) on sy
       (python -m torch.distributed.run --nproc-per-node N ..., one rank per GPU, RCCL).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
       (what the driver does) works as before: RANK / LOCAL_RANK / WORLD_SIZE come from the env.
+  python bench.py --gpus 1 --steps K --warmup W --full
+      the same headline, then everything else this script measures (rooflines, phase table, secondary, CPU baselines).
 
-Rank 0 prints ONE JSON line.  After the timed region rank 0 runs ONE more, instrumented step (HIP events
+Rank 0 prints ONE JSON line.  A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps,
+--dump-outputs, the line.  With --full rank 0 runs ONE more, instrumented step after the timed region (HIP events
 around every conv / attention launch inside the step, lxo_timing_*) from which the roofline entries are computed,
-then the secondary measurements (none of them touches `value`).  --dump-outputs DIR writes what the LAST timed step computed
+then the secondary measurements and the CPU baselines (none of them touches `value`; --no-cpu-baseline / --no-secondary / --no-pmc /
+--no-extras take parts of --full out again).  --dump-outputs DIR writes what the LAST timed step computed
 (loss, weights, gradient: dump_outputs) before any of that runs.  The inputs are seeded and the timed engine runs the bf16 mode without
 float atomics (Engine(deterministic=True); LXO_DETERMINISTIC=0 times the atomic mode instead), so every run with the same arguments
 computes the same arrays bit for bit and two builds can be compared array by array.
@@ -575,10 +579,13 @@ def main():
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--vocab", type=int, default=500)
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline timing only (profiler runs): no instrumented step, no secondary keys")
-    ap.add_argument("--no-secondary", action="store_true", help="skip configs[1] / T=151 / decode measurements")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two in-run rocprofv3 --pmc passes (HBM traffic of the roofline kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also take the instrumented step (rooflines, phase table), the secondary measurements and the CPU "
+                         "baselines; off by default: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="headline timing only, as without --full (kept for the profiler command lines that pass it)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip configs[1] / T=151 / decode measurements")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two in-run rocprofv3 --pmc passes (HBM traffic of the roofline kernels)")
     ap.add_argument("--sim", action="store_true", help="TEST ONLY: CPU tensors, gloo, the hipsim build of the kernels, tiny shapes")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last one computed (loss, weights, gradient) as DIR/<name>.npy (see dump_outputs)")
@@ -643,7 +650,7 @@ def main():
         B, H, W, V = args.batch, args.height, args.width, args.vocab
         # the ordered-reduction bf16 mode (lxo_shape.deterministic): no float atomics, so the same arguments give the same weights, gradient
         # and loss in every run (--dump-outputs); with float atomics the summation order -- and after a few Adam steps the weights -- differ
-        # from run to run.  LXO_DETERMINISTIC=0 times the atomic mode; secondary.atomic_bf16 times it beside the headline in any case.
+        # from run to run.  LXO_DETERMINISTIC=0 times the atomic mode; secondary.atomic_bf16 (--full) times it beside the headline in any case.
         eng = Engine(V, dtype=args.dtype, device=dev, seed=0, deterministic=os.environ.get("LXO_DETERMINISTIC", "1") != "0")
         imgs, forms = synthetic.make_set(B, H, W, V, 30, 101, seed=1234 + rank)
     img = torch.from_numpy(pad_batch_images(imgs)).to(dev)
@@ -725,7 +732,7 @@ def main():
             out["data_parallel"] = dict(dp_info, rank_cpu_pinning=(pinned if not args.sim else None))
         if args.sim:
             out["config"]["workload"] = "TEST ONLY (--sim): hipsim-interpreted kernels on CPU, gloo, tiny shapes"
-        if not args.sim and not args.no_extras:
+        if args.full and not args.sim and not args.no_extras:
             out["conv_roofline_fraction_e2e"] = round(GF_TRAIN_PER_IMG * (H * W / (128.0 * 512.0)) * value / world / MFMA_BF16_PEAK, 4)
             recs, phases = instrumented_step(eng, img, f_d, l, torch)
             roof = roofline_from_records(recs, ("conv_fwd", "conv_dgrad"),

@@ -13,20 +13,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_headline_dump_is_bit_identical_run_to_run(tmp_path):
-    """The second run also takes the instrumented step (roofline entries) that follows the timed region -- one more training step on
-    the same engine: its dump must still equal the --no-extras run's, i.e. be taken before that step."""
+    """The second run (--full) also takes the instrumented step (roofline entries) that follows the timed region -- one more training
+    step on the same engine: its dump must still equal the plain run's, i.e. be taken before that step."""
     dumps = []
     env = dict(os.environ)
     env.pop("LXO_DETERMINISTIC", None)
-    for run, extra in enumerate((["--no-extras"], ["--no-secondary", "--no-pmc"])):
+    for run, extra in enumerate(([], ["--full", "--no-cpu-baseline", "--no-secondary", "--no-pmc"])):
         d = str(tmp_path / ("run%d" % run))
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-                            "--no-cpu-baseline", "--dump-outputs", d] + extra,
+                            "--dump-outputs", d] + extra,
                            cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         out = json.loads([x for x in r.stdout.decode().splitlines() if x.startswith("{")][-1])
         assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["deterministic"] is True
         assert ("roofline" in out) == (run == 1)                    # the instrumented step ran in the second run only
+        if run == 0:                                                # a plain run measures the headline and nothing else
+            assert not {"ms_per_step_by_phase", "secondary", "cpu_baseline", "pmc_traffic_per_launch"} & set(out), sorted(out)
         files = out["dump_outputs"]["files"]
         assert sorted(os.listdir(d)) == files == ["grads.npy", "loss.npy", "loss_stats.npy", "params.npy"]
         assert sum(os.path.getsize(os.path.join(d, f)) for f in files) < 64e6

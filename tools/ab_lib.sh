@@ -1,5 +1,5 @@
 # A/B aid: bench.py headline + in-step conv / wgrad rooflines for the shipped library and latex_ocr_amd/liblxo_prev.so (if present)
-for rep in 1 2; do for v in "" _prev; do f=latex_ocr_amd/liblxo$v.so; [ -f $f ] || continue; LXO_LIB_PATH=$GRAFT_REPO_ROOT/$f python bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+for rep in 1 2; do for v in "" _prev; do f=latex_ocr_amd/liblxo$v.so; [ -f $f ] || continue; LXO_LIB_PATH=$PWD/$f python bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 w=d['roofline_wgrad']; c=d['roofline']
