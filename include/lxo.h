@@ -362,6 +362,56 @@ int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int n, int step
 #define LXO_CONSENSUS_MAX_N 64
 int lxo_consensus(const int32_t* ids, long long image_stride, long long draw_stride, long long tok_stride, int B, int n, int T, int id_end,
                   const float* weights, int normalize, int32_t* dist_out, float* risk_out, int32_t* best_out, void* stream);
+/* Sentence-level BLEU of pairs, on the device, shape-free: the text metric as a COST, for minimum-risk training and consensus decoding.
+ * ADDRESSING, LENGTHS, THE END CUT AND THE CLAMPING are lxo_edit_distance's (and lxo_text_stats'), argument for argument.  Pair p has hypothesis h
+ * and reference r after the cut.  THE DEFINITION:
+ *   m_n, n = 1 .. 4: the clipped matches, sum over the distinct n-grams g of h of min(count_h(g), count_r(g)); t_n = max(1, |h| - n + 1).  Both are
+ *     exactly columns 0 .. 7 of lxo_text_stats.
+ *   Smoothing (Lin and Och's add-one on the higher orders only; nltk's SmoothingFunction().method2): p_1 = m_1 / t_1, p_n = (m_n + 1) / (t_n + 1)
+ *     for n = 2, 3, 4.
+ *   Brevity penalty: BP = 1 if |h| > |r|, else exp(1 - |r| / |h|).
+ *   sBLEU = 0 if m_1 = 0 (an empty hypothesis included), else BP * exp(1/4 * sum_n ln p_n).  cost = 1 - sBLEU, in [0, 1].
+ *   EQUALITY OVERRIDE: if h == r (equal length, equal tokens; two empty sequences are equal) then sBLEU = 1.f and cost = 0.f exactly, whatever
+ *     the formula says -- smoothed, an identical 2-token pair has p_3 = p_4 = 1/2.  So a reference costs 0 against itself and equal hypotheses
+ *     cost the same bit for bit.
+ *   Arithmetic: f32, logf / expf, one division per p_n, the logs added in ascending n; model/evaluation/text.py sentence_bleu restates it in
+ *     float64 on the host.  The counts are integers and exact; the floats agree with the float64 value within 1e-5.
+ * OUTPUTS (device, at least one NOT NULL): counts_out int32 [pairs][LXO_BLEU_COUNTS] = m_1 .. m_4, t_1 .. t_4, |h|, |r|; bleu_out f32 [pairs] =
+ * sBLEU; cost_out f32 [pairs] = 1 - sBLEU.
+ * One launch, one wave per pair: both sides staged in LDS, one walk for the four orders (lxo_text_stats' counting identity), NO Levenshtein DP, an
+ * equality compare, the float tail on wave-uniform values.  No host synchronisation, capturable into a graph, the same bytes in every run.
+ * Both sides are at most LXO_EDIT_MAX_REF tokens wide.  pairs == 0 launches nothing.
+ * -1, with the reason in lxo_last_error and nothing written: the three outputs all NULL; otherwise lxo_text_stats' own cases -- a NULL hyp or ref;
+ * pairs, T, G or a stride negative; hyp_block or per_ref < 1; G < 1 with pairs > 0; T outside 0 .. LXO_EDIT_MAX_REF; ref_ld outside
+ * 1 .. LXO_EDIT_MAX_REF. */
+#define LXO_BLEU_COUNTS 10   /* int32 per pair */
+int lxo_sentence_bleu(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                      const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
+                      int pairs, int id_end, int32_t* counts_out, float* bleu_out, float* cost_out, void* stream);
+/* lxo_consensus under the cost 1 - sBLEU (lxo_sentence_bleu's definition): the draws are addressed and cut as lxo_consensus', the weights read
+ * and the risk and the arg-min formed as there; there is no `normalize`.
+ *   c(i, j) = lxo_sentence_bleu's cost of hypothesis s_i against reference s_j -- draw j plays the reference; 0.f exactly for equal draws and on
+ *     the diagonal.  The cost is NOT symmetric (t_n and BP are the hypothesis'), the clipped matches are: sum_g min(count_i(g), count_j(g)).  One
+ *     wave per UNORDERED pair counts them once and writes c(i, j) and c(j, i); equal draws are found by a compare and skip the count.
+ *   risk[g][i] = (sum_j w_j * c(i, j)) / (sum_j w_j) and best[g] exactly as lxo_consensus states them.  Equal draws have equal rows of costs --
+ *     the same integers go through the same f32 operations -- and so equal risks, bit for bit.
+ * OUTPUTS (device): match_out int32 [B][n][n][4] (nullable): the clipped matches of orders 1 .. 4, symmetric; on the diagonal a draw against itself,
+ * its own n-grams max(0, |s_i| - n + 1).  cost_out f32 [B][n][n] (NOT NULL), cost_out[g][i][j] = c(i, j) -- also the hand-over between the two
+ * launches; risk_out f32 [B][n]; best_out int32 [B] (both NOT NULL).
+ * B == 0 launches nothing.  T == 0 or n == 1: costs and risks all 0, best 0.
+ * -1, with the reason in lxo_last_error and no output written: a NULL ids, cost_out, risk_out or best_out; B < 0; n outside
+ * 1 .. LXO_CONSENSUS_MAX_N; T outside 0 .. LXO_EDIT_MAX_REF; a negative stride; more than 2^31 - 16 pairs B * n * (n - 1) / 2. */
+int lxo_consensus_bleu(const int32_t* ids, long long image_stride, long long draw_stride, long long tok_stride, int B, int n, int T, int id_end,
+                       const float* weights, int32_t* match_out, float* cost_out, float* risk_out, int32_t* best_out, void* stream);
+/* lxo_mrt_candidates with the cost chosen: cost_kind = LXO_COST_EDIT is that call bit for bit (it forwards here); with LXO_COST_BLEU the third
+ * launch is lxo_sentence_bleu's kernel and cost f32 [R] = 1 - sBLEU of the row against its image's reference -- 0 exactly for the reference's own
+ * row (the equality override) and for the dead rows.  Then the rows are a side of that kernel: steps + 1 <= LXO_EDIT_MAX_REF as well.
+ * -1: lxo_mrt_candidates' cases; a cost_kind other than the two; with LXO_COST_BLEU, steps + 1 > LXO_EDIT_MAX_REF. */
+#define LXO_COST_EDIT 0
+#define LXO_COST_BLEU 1
+int lxo_mrt_candidates_cost(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
+                            int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
+                            int32_t* row_image, int cost_kind, void* stream);
 /* Teacher-forced scoring, after lxo_decoder_train_fwd with the same shape and formula: per-token log-probs, the model's top-1 token per
  * position and per-sequence sums; reads ws region "logits", writes only the caller's outputs (device, [B, T] / [B]).
  * logp_out f32 [B, T] (NOT NULL): log_softmax(logits of step t)[formula[b][t]] for t < lengths[b], 0 after.

@@ -192,16 +192,41 @@ extern "C" int lxo_text_stats(const int32_t* hyp, int hyp_block, long long hyp_b
     CHECK_LAUNCH(lxo_k_text_stats(a, (hipStream_t)stream), "lxo_text_stats");
     return 0;
 }
-extern "C" int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
-                                  int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
-                                  int32_t* row_image, void* stream) {
+static_assert(LXO_BLEU_COUNTS == kBleuCounts, "include/lxo.h and csrc/seqcost.h disagree on the sentence-BLEU counts");
+extern "C" int lxo_sentence_bleu(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                                 const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
+                                 int pairs, int id_end, int32_t* counts_out, float* bleu_out, float* cost_out, void* stream) {
+    if (!hyp || !ref) return fail(-1, "lxo_sentence_bleu: null hyp or ref");
+    if (!counts_out && !bleu_out && !cost_out) return fail(-1, "lxo_sentence_bleu: counts_out, bleu_out and cost_out are all NULL");
+    if (pairs < 0 || T < 0 || G < 0 || hyp_block_stride < 0 || hyp_row_stride < 0 || hyp_tok_stride < 0)
+        return fail(-1, "lxo_sentence_bleu: a negative count or stride");
+    if (hyp_block < 1 || per_ref < 1 || (pairs > 0 && G < 1)) return fail(-1, "lxo_sentence_bleu: hyp_block < 1, per_ref < 1 or no reference row");
+    if (T > LXO_EDIT_MAX_REF) return fail(-1, "lxo_sentence_bleu: T outside 0 .. LXO_EDIT_MAX_REF (a hypothesis wider than the kernel's staging limit)");
+    if (ref_ld < 1 || ref_ld > LXO_EDIT_MAX_REF) return fail(-1, "lxo_sentence_bleu: ref_ld outside 1 .. LXO_EDIT_MAX_REF (a reference wider than the kernel's staging limit)");
+    const BleuArgs a = {hyp, hyp_len, ref, ref_len, ref_of, nullptr, counts_out, bleu_out, cost_out, hyp_block_stride, hyp_row_stride, hyp_tok_stride,
+                        hyp_block, T, G, ref_ld, per_ref, pairs, id_end};
+    CHECK_LAUNCH(lxo_k_sentence_bleu(a, (hipStream_t)stream), "lxo_sentence_bleu");
+    return 0;
+}
+extern "C" int lxo_mrt_candidates_cost(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
+                                       int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
+                                       int32_t* row_image, int cost_kind, void* stream) {
     if (!ids || !ref || !ref_len || !cand || !cand_len || !cost || !group_off || !row_image) return fail(-1, "lxo_mrt_candidates: a null argument");
     if (B < 0 || n < 1 || n > 16 || max_steps < 0 || steps < 0 || steps > max_steps) return fail(-1, "lxo_mrt_candidates: B < 0, n outside 1 .. 16 or steps outside [0, max_steps]");
     if (Tr < 1 || Tr > LXO_EDIT_MAX_REF) return fail(-1, "lxo_mrt_candidates: Tr outside 1 .. LXO_EDIT_MAX_REF");
     if (id_end < 0) return fail(-1, "lxo_mrt_candidates: id_end < 0");
+    if (cost_kind != LXO_COST_EDIT && cost_kind != LXO_COST_BLEU) return fail(-1, "lxo_mrt_candidates_cost: cost_kind is neither LXO_COST_EDIT nor LXO_COST_BLEU");
+    if (cost_kind == LXO_COST_BLEU && steps + 1 > LXO_EDIT_MAX_REF)
+        return fail(-1, "lxo_mrt_candidates_cost: with LXO_COST_BLEU steps + 1 must not exceed LXO_EDIT_MAX_REF (rows wider than the kernel's staging limit)");
     const CandArgs a = {ids, ref, ref_len, cand, cand_len, cost, group_off, row_image, B, max_steps, n, steps, Tr, id_end, id_pad, include_reference ? 1 : 0};
-    CHECK_LAUNCH(lxo_k_mrt_candidates(a, (hipStream_t)stream), "lxo_mrt_candidates");
+    CHECK_LAUNCH(lxo_k_mrt_candidates(a, (hipStream_t)stream, cost_kind), "lxo_mrt_candidates");
     return 0;
+}
+extern "C" int lxo_mrt_candidates(const int32_t* ids, int B, int max_steps, int n, int steps, const int32_t* ref, int Tr, const int32_t* ref_len,
+                                  int id_end, int id_pad, int include_reference, int32_t* cand, int32_t* cand_len, float* cost, int32_t* group_off,
+                                  int32_t* row_image, void* stream) {
+    return lxo_mrt_candidates_cost(ids, B, max_steps, n, steps, ref, Tr, ref_len, id_end, id_pad, include_reference, cand, cand_len, cost, group_off, row_image,
+                                   LXO_COST_EDIT, stream);
 }
 static_assert(LXO_CONSENSUS_MAX_N == kConsensusMaxN, "include/lxo.h and csrc/seqcost.h disagree on the number of draws");
 extern "C" int lxo_consensus(const int32_t* ids, long long image_stride, long long draw_stride, long long tok_stride, int B, int n, int T, int id_end,
@@ -214,6 +239,17 @@ extern "C" int lxo_consensus(const int32_t* ids, long long image_stride, long lo
     if ((long long)B * n * (n - 1) / 2 > 0x7ffffff0ll) return fail(-1, "lxo_consensus: B n (n - 1) / 2 pairs exceed one launch");
     const ConsArgs a = {ids, weights, dist_out, risk_out, best_out, image_stride, draw_stride, tok_stride, B, n, T, id_end, normalize};
     CHECK_LAUNCH(lxo_k_consensus(a, (hipStream_t)stream), "lxo_consensus");
+    return 0;
+}
+extern "C" int lxo_consensus_bleu(const int32_t* ids, long long image_stride, long long draw_stride, long long tok_stride, int B, int n, int T, int id_end,
+                                  const float* weights, int32_t* match_out, float* cost_out, float* risk_out, int32_t* best_out, void* stream) {
+    if (!ids || !cost_out || !risk_out || !best_out) return fail(-1, "lxo_consensus_bleu: null ids, cost_out, risk_out or best_out");
+    if (B < 0 || image_stride < 0 || draw_stride < 0 || tok_stride < 0) return fail(-1, "lxo_consensus_bleu: B or a stride negative");
+    if (n < 1 || n > LXO_CONSENSUS_MAX_N) return fail(-1, "lxo_consensus_bleu: n outside 1 .. LXO_CONSENSUS_MAX_N");
+    if (T < 0 || T > LXO_EDIT_MAX_REF) return fail(-1, "lxo_consensus_bleu: T outside 0 .. LXO_EDIT_MAX_REF (draws wider than the kernel's staging limit)");
+    if ((long long)B * n * (n - 1) / 2 > 0x7ffffff0ll) return fail(-1, "lxo_consensus_bleu: B n (n - 1) / 2 pairs exceed one launch");
+    const ConsBleuArgs a = {ids, weights, match_out, cost_out, risk_out, best_out, image_stride, draw_stride, tok_stride, B, n, T, id_end};
+    CHECK_LAUNCH(lxo_k_consensus_bleu(a, (hipStream_t)stream), "lxo_consensus_bleu");
     return 0;
 }
 extern "C" int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,

@@ -1,5 +1,6 @@
 // Launchers of the sequence-cost kernels (seqcost.hip): batched Levenshtein distance over token rows, and the candidate rows of a minimum-risk
-// step built on the device from sampled ids and references, and the minimum-risk choice among an image's draws.
+// step built on the device from sampled ids and references, and the minimum-risk choice among an image's draws; the text metrics' counts and the
+// sentence-level BLEU built on them, as a score and as the cost of the candidates and of the consensus.
 #pragma once
 #include "lxo_common.h"
 
@@ -28,7 +29,8 @@ struct CandArgs {
     int* cand; int* cand_len; float* cost; int* group_off; int* row_image;
     int B, max_steps, n, steps, Tr, id_end, id_pad, inc;
 };
-int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st);
+// cost_kind 0: the edit-distance cost through lxo_k_edit_distance; 1: 1 - sentence BLEU through lxo_k_sentence_bleu (then steps + 1 <= kEditMaxRef too)
+int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st, int cost_kind = 0);
 
 // The consensus among the draws of an image (lxo_consensus, include/lxo.h holds the definition): draw i of image g starts at element
 // g image_stride + i draw_stride of ids, its tokens tok_stride apart, T of them, cut at the first id_end.  Two launches, no host synchronisation:
@@ -55,3 +57,26 @@ struct TextArgs {
     int hyp_block, T, G, ref_ld, per_ref, pairs, id_end, accumulate;
 };
 int lxo_k_text_stats(const TextArgs& a, hipStream_t st);
+
+// Sentence-level BLEU of pairs (lxo_sentence_bleu, include/lxo.h holds the definition): pairs addressed, cut and clamped as TextArgs'.  counts (nullable)
+// int32 [pairs][kBleuCounts], bleu (nullable) and cost (nullable) f32 [pairs]; live as EditArgs': pairs p >= live[0] read nothing and cost 0.  One launch,
+// one wave per pair, no Levenshtein DP, no host synchronisation.  T or ref_ld > kEditMaxRef: -2.
+constexpr int kBleuCounts = 10;
+struct BleuArgs {
+    const int* hyp; const int* hyp_len; const int* ref; const int* ref_len; const int* ref_of; const int* live;
+    int* counts; float* bleu; float* cost;
+    long long hb_stride, hr_stride, ht_stride;
+    int hyp_block, T, G, ref_ld, per_ref, pairs, id_end;
+};
+int lxo_k_sentence_bleu(const BleuArgs& a, hipStream_t st);
+
+// The consensus under the cost 1 - sentence BLEU (lxo_consensus_bleu): draws addressed as ConsArgs'.  Two launches: one wave per unordered pair counts the
+// clipped matches once and writes both directions of cost [B][n][n] (and of match (nullable) int32 [B][n][n][4]), then per image the risks, the
+// diagonal and the arg-min.  The limits and -2 of lxo_k_consensus.
+struct ConsBleuArgs {
+    const int* ids; const float* weights;
+    int* match; float* cost; float* risk; int* best;
+    long long image_stride, draw_stride, tok_stride;
+    int B, n, T, id_end;
+};
+int lxo_k_consensus_bleu(const ConsBleuArgs& a, hipStream_t st);

@@ -2,7 +2,8 @@
 // sampled ids (lxo_mrt_candidates).  Integer arithmetic throughout: exact, and the same in every order.  On top of the distances, the
 // minimum-risk choice among the draws of an image (lxo_consensus): all pairwise distances, the expected cost of every draw, the arg-min.
 // And the counts an evaluation's text metrics are made of (lxo_text_stats): clipped n-gram matches, lengths, distance and exact match per pair,
-// summed over the pairs into a corpus row.
+// summed over the pairs into a corpus row.  And that metric as a cost: the sentence-level BLEU of a pair (lxo_sentence_bleu), the consensus under
+// 1 - sBLEU (lxo_consensus_bleu) and the candidate rows costed with it (lxo_mrt_candidates_cost); their float tails are f32 in one fixed order.
 #include "seqcost.h"
 
 namespace {
@@ -177,6 +178,9 @@ __global__ __launch_bounds__(256) void cand_emit_kernel(CandArgs a, const int* s
 // dist[g][i][j] and dist[g][j][i].  Equal draws (equal length, equal tokens) skip the DP: its answer for them is 0 as well.  The waves of the pairs
 // (0, j) leave the draws' lengths in risk_out [g][j] (as int32) for launch 2.
 LXO_DEV const int* cons_draw(const ConsArgs& a, int g, int i) { return a.ids + (long long)g * a.image_stride + (long long)i * a.draw_stride; }
+LXO_DEV const int* cons_draw(const int* ids, long long image_stride, long long draw_stride, int g, int i) {
+    return ids + (long long)g * image_stride + (long long)i * draw_stride;
+}
 
 template <int CPL>
 __global__ __launch_bounds__(256) void cons_pairs_kernel(ConsArgs a, int per) {
@@ -378,6 +382,185 @@ __global__ __launch_bounds__(256) void text_corpus_kernel(const int* stats, int 
     }
 }
 
+// ---- sentence-level BLEU of a pair (lxo_sentence_bleu), and as the cost of a consensus (lxo_consensus_bleu) ----
+// The steps of text_stats_kernel and cons_select_kernel that the kernels below share, as functions.  (Those two kernels keep the steps in their own
+// bodies: calling the functions there moved a few of their instructions, and their code objects stay what they were.)
+// The clipped matches of a staged pair, match[n - 1] += sum_g min(count_h(g), count_r(g)) for the orders n = 1 .. 4 -- text_stats_kernel's counting identity, lane l
+// of each 64-position chunk owning one hypothesis position -- and whether the two staged sequences are equal (equal length, equal tokens).
+LXO_DEV void text_matches(const int* hs, int m, const int* rs, int n, int lane, int (&match)[4]) {
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const int i = i0 + lane, ic = min(i, m);
+        const int t0 = hs[ic + 1], t1 = hs[ic + 2], t2 = hs[ic + 3], t3 = hs[ic + 4];
+        int k[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
+        text_walk<true>(hs, min(i0 + 63, m - 1), i0, i, t0, t1, t2, t3, k);                     // (every j < i0 lies in front of every lane)
+        text_walk<false>(rs, n, max(n - 3, 0) / 4 * 4, n, t0, t1, t2, t3, c);                   // (groups whose last position j has j + 4 <= n)
+#pragma unroll
+        for (int o = 0; o < 4; ++o) match[o] += (int)__builtin_popcountll(__ballot(i + o < m && k[o] < c[o]));
+    }
+}
+LXO_DEV bool text_same(const int* hs, int m, const int* rs, int n, int lane) {
+    bool same = m == n;
+    for (int t0 = 0; t0 < m && same; t0 += 64) {
+        const int t = min(t0 + lane, m);
+        same = __ballot(hs[t + 1] != rs[t + 1]) == 0ull;
+    }
+    return same;
+}
+
+// The weight of lane i's draw as the select kernels read it: negative, NaN or infinite counts as 0, a row that sums to 0 as all ones (NULL: ones).
+LXO_DEV float cons_weight(const float* weights, int g, int n, int lane, bool mine) {
+    float w = 1.f;
+    if (weights) {
+        w = mine ? weights[(long long)g * n + lane] : 0.f;
+        if (!(w > 0.f) || !(w - w == 0.f)) w = 0.f;                                    // negative, NaN, infinite: 0
+        float sum = 0.f;
+        for (int j = 0; j < n; ++j) sum += __shfl(w, j);
+        if (sum == 0.f) w = 1.f;
+    }
+    return w;
+}
+// The lane of the smallest r among the lanes that hold a draw, the lower lane on ties; in every lane.
+LXO_DEV int cons_argmin(float r, bool mine, int lane) {
+    float v = mine ? r : __int_as_float(0x7f800000);
+    int best = lane;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int ob = __shfl_xor(best, o);
+        if (ov < v || (ov == v && ob < best)) { v = ov; best = ob; }
+    }
+    return best;
+}
+
+// The score of include/lxo.h from the clipped matches of a hypothesis of m tokens against a reference of n: add-one smoothing on the orders 2 .. 4,
+// the brevity penalty, 1 for an equal pair and 0 without a common unigram.  Lane-uniform values in, f32 throughout, one division per order.
+LXO_DEV float sbleu(const int (&match)[4], int m, int n, bool same) {
+#pragma clang fp contract(off)
+    if (same) return 1.f;
+    if (match[0] == 0) return 0.f;                                      // (an empty hypothesis included: below, m >= 1)
+    float s = logf((float)match[0] / (float)m);
+#pragma unroll
+    for (int o = 1; o < 4; ++o) s += logf((float)(match[o] + 1) / (float)(max(1, m - o) + 1));
+    const float bp = m > n ? 1.f : expf(1.f - (float)n / (float)m);
+    return bp * expf(0.25f * s);
+}
+
+// One wave per pair, as text_stats_kernel without the DP: both sides staged, one walk for the four orders, the ballot compare, the float tail.
+__global__ __launch_bounds__(256) void bleu_pairs_kernel(BleuArgs a) {
+    __shared__ __attribute__((aligned(16))) int tok[4][2 * kTextWords];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave;
+    if (p >= a.pairs) return;
+    if (a.live && p >= a.live[0]) {                                     // a dead candidate row: nothing read, no cost
+        if (lane < kBleuCounts && a.counts) a.counts[(long long)p * kBleuCounts + lane] = 0;
+        if (lane == 0) { if (a.bleu) a.bleu[p] = 1.f; if (a.cost) a.cost[p] = 0.f; }
+        return;
+    }
+    const int r = min(max(a.ref_of ? a.ref_of[p] : p / a.per_ref, 0), a.G - 1);
+    const int* hp = a.hyp + (long long)(p / a.hyp_block) * a.hb_stride + (long long)(p % a.hyp_block) * a.hr_stride;
+    const int* rp = a.ref + (long long)r * a.ref_ld;
+    const int m = __builtin_amdgcn_readfirstlane(cut_len(hp, a.ht_stride, min(a.hyp_len ? min(max(a.hyp_len[p], 0), a.T) : a.T, kEditMaxRef), a.id_end, lane));
+    const int n = __builtin_amdgcn_readfirstlane(cut_len(rp, 1, min(a.ref_len ? min(max(a.ref_len[r], 0), a.ref_ld) : a.ref_ld, kEditMaxRef), a.id_end, lane));
+    int* hs = tok[__builtin_amdgcn_readfirstlane(wave)];
+    int* rs = hs + kTextWords;
+    text_stage(hs, hp, a.ht_stride, m, lane);
+    text_stage(rs, rp, 1, n, lane);
+    __builtin_amdgcn_wave_barrier();
+
+    int match[4] = {0, 0, 0, 0};
+    const bool same = text_same(hs, m, rs, n, lane);
+    if (same) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) match[o] = max(0, m - o);           // every n-gram of h against itself
+    } else {
+        text_matches(hs, m, rs, n, lane, match);
+    }
+    const float b = sbleu(match, m, n, same);
+    if (a.counts) {
+        const int row[kBleuCounts] = {match[0], match[1], match[2], match[3], max(1, m), max(1, m - 1), max(1, m - 2), max(1, m - 3), m, n};
+        int v = 0;
+#pragma unroll
+        for (int c = 0; c < kBleuCounts; ++c) if (lane == c) v = row[c];
+        if (lane < kBleuCounts) a.counts[(long long)p * kBleuCounts + lane] = v;
+    }
+    if (lane == 0) { if (a.bleu) a.bleu[p] = b; if (a.cost) a.cost[p] = 1.f - b; }
+}
+
+// Consensus, launch 1: one wave per unordered pair (g, i < j), enumerated as cons_pairs_kernel does.  The clipped matches are symmetric in the two draws,
+// so one count serves c(i, j) -- draw j the reference -- and c(j, i); only the totals and the brevity penalty change sides.  Equal draws skip the walk.
+// The waves of the pairs (0, j) write the diagonal of match_out (a draw against itself: its own n-grams).
+__global__ __launch_bounds__(256) void cons_bleu_pairs_kernel(ConsBleuArgs a, int per) {
+    __shared__ __attribute__((aligned(16))) int tok[4][2 * kTextWords];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = blockIdx.x * 4 + wave;
+    if (w >= a.B * per) return;
+    const int g = w / per;
+    int q = w % per, i = 0;
+    while (q >= a.n - 1 - i) { q -= a.n - 1 - i; ++i; }
+    const int j = i + 1 + q;
+    const int* pi = cons_draw(a.ids, a.image_stride, a.draw_stride, g, i);
+    const int* pj = cons_draw(a.ids, a.image_stride, a.draw_stride, g, j);
+    const int Li = __builtin_amdgcn_readfirstlane(cut_len(pi, a.tok_stride, min(a.T, kEditMaxRef), a.id_end, lane));
+    const int Lj = __builtin_amdgcn_readfirstlane(cut_len(pj, a.tok_stride, min(a.T, kEditMaxRef), a.id_end, lane));
+    int* si = tok[__builtin_amdgcn_readfirstlane(wave)];
+    int* sj = si + kTextWords;
+    text_stage(si, pi, a.tok_stride, Li, lane);
+    text_stage(sj, pj, a.tok_stride, Lj, lane);
+    __builtin_amdgcn_wave_barrier();
+
+    int match[4] = {0, 0, 0, 0};
+    const bool same = text_same(si, Li, sj, Lj, lane);
+    if (same) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) match[o] = max(0, Li - o);
+    } else {
+        text_matches(si, Li, sj, Lj, lane, match);
+    }
+    const float cij = 1.f - sbleu(match, Li, Lj, same), cji = 1.f - sbleu(match, Lj, Li, same);
+    const long long n = a.n;
+    if (lane == 0) {
+        float* row = a.cost + g * n * n;
+        row[i * n + j] = cij;
+        row[j * n + i] = cji;
+    }
+    if (a.match && lane < 4) {
+        int v = 0;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) if (lane == o) v = match[o];
+        int* row = a.match + g * n * n * 4;
+        row[(i * n + j) * 4 + lane] = v;
+        row[(j * n + i) * 4 + lane] = v;
+        if (i == 0) {
+            row[(j * n + j) * 4 + lane] = max(0, Lj - lane);
+            if (j == 1) row[lane] = max(0, Li - lane);
+        }
+    }
+}
+
+// Consensus, launch 2: cons_select_kernel on the f32 cost matrix -- the same weights, ascending-j sums without fused multiply-add, arg-min and ties; the
+// diagonal of the costs is written here (and with one draw, which no pair wave saw, the diagonal of match_out).
+__global__ __launch_bounds__(256) void cons_bleu_select_kernel(ConsBleuArgs a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, g = blockIdx.x * 4 + (threadIdx.x >> 6), n = a.n;
+    if (g >= a.B) return;
+    const bool mine = lane < n;
+    float* row = a.cost + (long long)g * n * n;
+    if (n == 1 && a.match) {
+        const int L = cut_len(cons_draw(a.ids, a.image_stride, a.draw_stride, g, 0), a.tok_stride, min(a.T, kEditMaxRef), a.id_end, lane);
+        if (lane < 4) a.match[(long long)g * 4 + lane] = max(0, L - lane);
+    }
+    const float w = cons_weight(a.weights, g, n, lane, mine);
+    float W = 0.f, acc = 0.f;
+    for (int j = 0; j < n; ++j) {
+        const float wj = __shfl(w, j);
+        const float c = mine && lane != j ? row[lane * n + j] : 0.f;
+        W += wj;
+        acc += wj * c;
+    }
+    const float r = acc / W;
+    if (mine) { a.risk[(long long)g * n + lane] = r; row[lane * n + lane] = 0.f; }
+    const int best = cons_argmin(r, mine, lane);
+    if (lane == 0) a.best[g] = best;
+}
+
 }  // namespace
 
 #define LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, __VA_ARGS__)
@@ -394,8 +577,15 @@ int lxo_k_edit_distance(const EditArgs& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st) {
-    if (a.Tr > kEditMaxRef) return -2;
+int lxo_k_sentence_bleu(const BleuArgs& a, hipStream_t st) {
+    if (a.ref_ld > kEditMaxRef || a.T > kEditMaxRef) return -2;
+    if (a.pairs == 0) return 0;
+    LAUNCH(bleu_pairs_kernel, cdiv(a.pairs, 4), a);
+    return (int)hipGetLastError();
+}
+
+int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st, int cost_kind) {
+    if (a.Tr > kEditMaxRef || (cost_kind && a.steps + 1 > kEditMaxRef)) return -2;
     if (a.B == 0) return (int)hipMemsetAsync(a.group_off, 0, sizeof(int), st);
     int* slot = reinterpret_cast<int*>(a.cost);
     LAUNCH(cand_analyse_kernel, a.B, a, slot);
@@ -403,7 +593,10 @@ int lxo_k_mrt_candidates(const CandArgs& a, hipStream_t st) {
     const int Tc = a.steps + 1 > a.Tr ? a.steps + 1 : a.Tr;
     EditArgs e = {a.cand, nullptr, a.ref, a.ref_len, a.row_image, a.group_off + a.B, nullptr, a.cost, Tc, 0, 1, 1, Tc, a.B, a.Tr, 1,
                   a.B * (a.n + a.inc), a.id_end};
-    return lxo_k_edit_distance(e, st);
+    if (!cost_kind) return lxo_k_edit_distance(e, st);
+    const BleuArgs b = {e.hyp, e.hyp_len, e.ref, e.ref_len, e.ref_of, e.live, nullptr, nullptr, e.cost, e.hb_stride, e.hr_stride, e.ht_stride,
+                        e.hyp_block, e.T, e.G, e.ref_ld, e.per_ref, e.pairs, e.id_end};
+    return lxo_k_sentence_bleu(b, st);
 }
 
 int lxo_k_consensus(const ConsArgs& a, hipStream_t st) {
@@ -420,6 +613,16 @@ int lxo_k_consensus(const ConsArgs& a, hipStream_t st) {
         else LAUNCH(cons_pairs_kernel<16>, grid, a, p);
     }
     LAUNCH(cons_select_kernel, cdiv(a.B, 4), a);
+    return (int)hipGetLastError();
+}
+
+int lxo_k_consensus_bleu(const ConsBleuArgs& a, hipStream_t st) {
+    if (a.T > kEditMaxRef || a.n > kConsensusMaxN) return -2;
+    if (a.B == 0) return 0;
+    const long long per = (long long)a.n * (a.n - 1) / 2, waves = per * a.B;
+    if (waves > 0x7ffffff0ll) return -2;
+    if (waves) LAUNCH(cons_bleu_pairs_kernel, (int)((waves + 3) / 4), a, (int)per);
+    LAUNCH(cons_bleu_select_kernel, cdiv(a.B, 4), a);
     return (int)hipGetLastError();
 }
 

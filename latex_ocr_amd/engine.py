@@ -25,6 +25,13 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _cost_kind(what, cost):
+    """the cost of a minimum-risk step or a consensus: "edit" (the edit distance) or "bleu" (1 - sentence BLEU) -> include/lxo.h's LXO_COST_*"""
+    if not isinstance(cost, str) or cost not in ("edit", "bleu"):
+        raise ValueError("%s: cost must be \"edit\" or \"bleu\", got %r" % (what, cost))
+    return _abi.LXO_COST_BLEU if cost == "bleu" else _abi.LXO_COST_EDIT
+
+
 # include/lxo.h: LXO_XDEC_BLOCK_BYTES (csrc/xdec.h: kXDecBlockBytes) -- ws region "xdec_sync" holds one such block per chain (forward, then
 # backward): 4 KB of flag lines, tickets and the error word (word LXO_XDEC_ERR_WORD) + 384 KB of hand-over words (tests/test_abi.py keeps
 # the definitions together)
@@ -781,7 +788,7 @@ class Engine(object):
         return float(h[0]) / int(img.shape[0]), h[1:].copy()
 
     def mrt_sample_step(self, img, ref, ref_lengths, id_end, id_pad, lr, alpha, n=5, temperature=1.0, top_k=0, top_p=1.0, seed=0, include_reference=True,
-                        max_iter=151, clip=-1.0, dropout=1.0):
+                        max_iter=151, clip=-1.0, dropout=1.0, cost="edit"):
         """One minimum-risk training step from pixels, the candidates never leaving the device: the sampled decode (sample_decode's draws at the same
         arguments, its ids kept on the device), lxo_mrt_candidates (each image's reference -- include_reference -- and its distinct draws as padded rows
         with their edit-distance costs, as Img2SeqModel.mrt_batch builds them on the host, in the same order), ONE index_select of the images by the
@@ -793,7 +800,12 @@ class Engine(object):
         "cand_lengths" [rows], "group_sizes" [B], "cost" f32 [rows], "q" f32 [rows].
         The host sees the decode loop's step count (as in every decode) and makes one copy at the end; because of that count the call cannot be
         captured into a graph.  A step a chain failed in is redone on the same device candidates, not on a fresh draw.  Single process: there is no
-        data-parallel form."""
+        data-parallel form.
+        cost = "bleu": the rows cost 1 - sentence BLEU against their image's reference (lxo_mrt_candidates_cost with LXO_COST_BLEU; sentence_bleu's
+        definition) in place of the edit distance; the reference's own row still costs 0 exactly.  Then max_iter is bounded by the kernel's width."""
+        kind = _cost_kind("mrt_sample_step", cost)
+        if kind == _abi.LXO_COST_BLEU and int(max_iter) > _abi.LXO_EDIT_MAX_REF - 1:
+            raise ValueError("mrt_sample_step: cost = \"bleu\" takes rows of at most %d tokens, max_iter = %d" % (_abi.LXO_EDIT_MAX_REF - 1, int(max_iter)))
         B = int(img.shape[0])
         ref_d, rl_d = self._to_dev(ref, torch.int32), self._to_dev(ref_lengths, torch.int32).reshape(-1)
         if ref_d.dim() != 2 or int(ref_d.shape[0]) != B or int(rl_d.shape[0]) != B or int(ref_d.shape[1]) < 1:
@@ -820,9 +832,12 @@ class Engine(object):
         cbuf = torch.empty(R * Tc + 3 * R + B + 1, dtype=torch.int32, device=self.device)
         o = np.cumsum([0, R * Tc, R, R, B + 1, R])
         cand, cand_len, cost, group_off, row_image = [cbuf[o[i]:o[i + 1]] for i in range(5)]
-        self._ck(self.lib.lxo_mrt_candidates(_p(ids), B, int(ids.shape[1]), n, steps, _p(ref_d), Tr, _p(rl_d), int(id_end), int(id_pad), inc,
-                                             _p(cand), _p(cand_len), _p(cost.view(torch.float32)), _p(group_off), _p(row_image), self._stream()),
-                 "mrt_candidates")
+        cargs = (_p(ids), B, int(ids.shape[1]), n, steps, _p(ref_d), Tr, _p(rl_d), int(id_end), int(id_pad), inc,
+                 _p(cand), _p(cand_len), _p(cost.view(torch.float32)), _p(group_off), _p(row_image))
+        if kind == _abi.LXO_COST_EDIT:
+            self._ck(self.lib.lxo_mrt_candidates(*(cargs + (self._stream(),))), "mrt_candidates")
+        else:
+            self._ck(self.lib.lxo_mrt_candidates_cost(*(cargs + (kind, self._stream()))), "mrt_candidates")
         rows_img = img_d.index_select(0, row_image.to(torch.int64))
         redone = False
         while True:
@@ -909,8 +924,9 @@ class Engine(object):
         _, corpus = self._text_stats_device("text_metrics", hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, False, None, 0)
         return scores_from_counts(corpus.cpu().numpy())
 
-    def _text_stats_device(self, what, hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, want_stats, corpus, accumulate):
-        """text_stats' checks and its call: -> (stats int32 [pairs, 12] or None, corpus int64 [14]), both left on the device.  corpus None: a fresh row."""
+    def _pair_args(self, what, hyp, ref, hyp_lengths, ref_lengths, ref_index):
+        """The pairs of text_stats / sentence_bleu on the device, checked: -> (h, block, geom, T, hl, r, G, Tr, rl, ri, per_ref, pairs), the arguments
+        of lxo_text_stats' addressing in its order (sides without a column not yet replaced: _pair_fill)."""
         h = hyp if isinstance(hyp, torch.Tensor) and hyp.device == self.device and hyp.dtype == torch.int32 else self._to_dev(hyp, torch.int32)
         r = self._to_dev(ref, torch.int32)
         if h.dim() not in (2, 3) or r.dim() != 2:
@@ -946,6 +962,20 @@ class Engine(object):
             if pairs % G:
                 raise ValueError("%s: without ref_index the %d hypotheses must be a multiple of the %d references" % (what, pairs, G))
             per_ref = pairs // G
+        return h, block, geom, T, hl, r, G, Tr, rl, ri, per_ref, pairs
+
+    def _pair_fill(self, h, T, r, G, Tr, rl):
+        """a side without a column gets a word to point at: -> (h, r, Tr, rl)"""
+        if T == 0:                                                 # hypotheses without a column: a word to point at, none of it read
+            h = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if Tr == 0:                                                # references without a column: every reference is empty
+            r, Tr = torch.zeros(max(G, 1), 1, dtype=torch.int32, device=self.device), 1
+            rl = torch.zeros(max(G, 1), dtype=torch.int32, device=self.device)
+        return h, r, Tr, rl
+
+    def _text_stats_device(self, what, hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, want_stats, corpus, accumulate):
+        """text_stats' checks and its call: -> (stats int32 [pairs, 12] or None, corpus int64 [14]), both left on the device.  corpus None: a fresh row."""
+        h, block, geom, T, hl, r, G, Tr, rl, ri, per_ref, pairs = self._pair_args(what, hyp, ref, hyp_lengths, ref_lengths, ref_index)
         if corpus is None:
             corpus = torch.zeros(_abi.LXO_TEXT_CORPUS, dtype=torch.int64, device=self.device)
         elif (not isinstance(corpus, torch.Tensor) or corpus.device != self.device or corpus.dtype != torch.int64 or tuple(corpus.shape) != (_abi.LXO_TEXT_CORPUS,)
@@ -954,16 +984,27 @@ class Engine(object):
         stats = torch.empty(pairs, _abi.LXO_TEXT_STATS, dtype=torch.int32, device=self.device) if want_stats else None
         if pairs == 0:                                             # nothing to count: the rows are empty, the corpus stays as it is
             return stats, corpus
-        if T == 0:                                                 # hypotheses without a column: a word to point at, none of it read
-            h = torch.zeros(1, dtype=torch.int32, device=self.device)
-        if Tr == 0:                                                # references without a column: every reference is empty
-            r, Tr = torch.zeros(max(G, 1), 1, dtype=torch.int32, device=self.device), 1
-            rl = torch.zeros(max(G, 1), dtype=torch.int32, device=self.device)
+        h, r, Tr, rl = self._pair_fill(h, T, r, G, Tr, rl)
         self._ck(self.lib.lxo_text_stats(_p(h), block, geom[0], geom[1], geom[2], T, _p(hl), _p(r), G, Tr, _p(rl), _p(ri), per_ref, pairs,
                                          -1 if id_end is None else int(id_end), _p(stats), _p(corpus), int(accumulate), self._stream()), what)
         return stats, corpus
 
-    def consensus(self, ids, id_end, weights=None, normalize=True, return_dist=False):
+    def sentence_bleu(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None, return_counts=False):
+        """Sentence-level BLEU-4 per pair on the device (lxo_sentence_bleu; include/lxo.h holds the definition: add-one smoothing on the orders
+        2 .. 4, 1 exactly for an equal pair, 0 without a common unigram): -> f32 [pairs], and with return_counts also int32 [pairs, 10] = the
+        clipped matches and the totals for n = 1 .. 4, |h|, |r| -- columns 0 .. 9 of text_stats.  hyp, ref, the lengths, id_end and ref_index as
+        text_stats takes them: host arrays, device tensors, strided views and the [B, T, n] ids of sample_decode read in place.  The cost of
+        mrt_sample_step(cost="bleu") and consensus(cost="bleu") is 1 - this.  A ValueError before any launch as text_stats'."""
+        h, block, geom, T, hl, r, G, Tr, rl, ri, per_ref, pairs = self._pair_args("sentence_bleu", hyp, ref, hyp_lengths, ref_lengths, ref_index)
+        bleu = torch.empty(pairs, dtype=torch.float32, device=self.device)
+        counts = torch.empty(pairs, _abi.LXO_BLEU_COUNTS, dtype=torch.int32, device=self.device) if return_counts else None
+        if pairs:
+            h, r, Tr, rl = self._pair_fill(h, T, r, G, Tr, rl)
+            self._ck(self.lib.lxo_sentence_bleu(_p(h), block, geom[0], geom[1], geom[2], T, _p(hl), _p(r), G, Tr, _p(rl), _p(ri), per_ref, pairs,
+                                                -1 if id_end is None else int(id_end), _p(counts), _p(bleu), None, self._stream()), "sentence_bleu")
+        return (bleu.cpu().numpy(), counts.cpu().numpy()) if return_counts else bleu.cpu().numpy()
+
+    def consensus(self, ids, id_end, weights=None, normalize=True, return_dist=False, cost="edit"):
         """The minimum-risk choice among n transcriptions per image (lxo_consensus): ids [B, T, n] token ids -- what sample_decode returns -- as a
         host array or a device int32 tensor, whose own strides are passed through (a view such as x.permute(0, 2, 1) of rows [B, n, T] is read in
         place).  Draw i of an image is its column cut at the first id_end (None: no cut); risk[b, i] is its expected edit distance to the image's
@@ -971,17 +1012,24 @@ class Engine(object):
         least risk, the lower index on ties.  weights [B, n] (None: uniform).  -> (best int32 [B], risk f32 [B, n]) and with return_dist also the
         distances int32 [B, n, n].  A ValueError before any launch for a wrong rank, n outside 1 .. 64, T above the kernel's limit, weights of
         another shape, and host weights that are negative, not finite or sum to 0 in a row (on the device such an entry counts as 0 and such a row
-        as all ones)."""
+        as all ones).
+        cost = "bleu": the cost of a pair is 1 - sentence BLEU of draw i against draw j as the reference (lxo_consensus_bleu; sentence_bleu's
+        definition), there is no normalisation -- normalize must be left at its default -- and return_dist returns the f32 cost matrix [B, n, n],
+        cost[b, i, j] = c(i, j).  Any other cost than "edit" or "bleu" is a ValueError."""
+        _cost_kind("consensus", cost)
+        if cost == "bleu" and normalize is not True:
+            raise ValueError("consensus: cost = \"bleu\" has no normalisation; leave normalize at its default")
         if isinstance(ids, torch.Tensor) and ids.device == self.device and ids.dtype == torch.int32:
             t = ids
         else:
             t = self._to_dev(ids, torch.int32)
-        best, risk, dist = self._consensus_device(t, id_end, weights, normalize)
+        best, risk, dist = self._consensus_device(t, id_end, weights, normalize, cost)
         out = (best.cpu().numpy(), risk.cpu().numpy())
         return out + (dist.cpu().numpy(),) if return_dist else out
 
-    def _consensus_device(self, ids, id_end, weights=None, normalize=True):
-        """consensus' checks and its call on a device int32 tensor [B, T, n] of any strides: -> (best, risk, dist), left on the device"""
+    def _consensus_device(self, ids, id_end, weights=None, normalize=True, cost="edit"):
+        """consensus' checks and its call on a device int32 tensor [B, T, n] of any strides: -> (best, risk, dist), left on the device; with
+        cost = "bleu" dist is the f32 cost matrix"""
         if ids.dim() != 3:
             raise ValueError("consensus: ids must be [B, T, n], got %s" % list(ids.shape))
         B, T, n = (int(x) for x in ids.shape)
@@ -998,11 +1046,14 @@ class Engine(object):
             w = self._to_dev(weights, torch.float32)
             if tuple(w.shape) != (B, n):
                 raise ValueError("consensus: weights must be [B = %d, n = %d], got %s" % (B, n, list(w.shape)))
-        dist = torch.empty(B, n, n, dtype=torch.int32, device=self.device)
+        dist = torch.empty(B, n, n, dtype=torch.float32 if cost == "bleu" else torch.int32, device=self.device)
         risk = torch.empty(B, n, dtype=torch.float32, device=self.device)
         best = torch.empty(B, dtype=torch.int32, device=self.device)
-        if B:
-            src = ids if T else torch.zeros(1, dtype=torch.int32, device=self.device)      # (no token: a word to point at, none of it read)
+        src = ids if T else torch.zeros(1, dtype=torch.int32, device=self.device)          # (no token: a word to point at, none of it read)
+        if B and cost == "bleu":
+            self._ck(self.lib.lxo_consensus_bleu(_p(src), int(ids.stride(0)), int(ids.stride(2)), int(ids.stride(1)), B, n, T, -1 if id_end is None else int(id_end),
+                                                 _p(w), None, _p(dist), _p(risk), _p(best), self._stream()), "consensus")
+        elif B:
             self._ck(self.lib.lxo_consensus(_p(src), int(ids.stride(0)), int(ids.stride(2)), int(ids.stride(1)), B, n, T, -1 if id_end is None else int(id_end),
                                             _p(w), 1 if normalize else 0, _p(dist), _p(risk), _p(best), self._stream()), "consensus")
         return best, risk, dist
@@ -1501,7 +1552,7 @@ class Engine(object):
         return _abi.LxoSampleOpts(temperature, top_k, top_p, int(seed) & 0xFFFFFFFF)
 
     def sample_decode(self, img, id_end, n=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, max_iter=151, return_scores=False, return_attention=False,
-                      prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False, return_consensus=False, consensus_normalize=True):
+                      prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False, return_consensus=False, consensus_normalize=True, consensus_cost="edit"):
         """n independent DRAWS of the whole sequence per image (lxo_sample_decode): ids int32 [B, T', n].  Every step draws from the model's
         distribution at `temperature`, cut to the top_k most likely tokens (0: off) and then to the smallest set of renormalised mass >= top_p
         (1: off); temperature = 0 means top_k = 1, the arg-max.  Draw (b, j) depends only on seed, b, j and the step: the same seed repeats bit for
@@ -1514,9 +1565,13 @@ class Engine(object):
         grammar / return_depth: as in greedy_decode (lxo_sample_decode_grammar), one state per draw: the cut-offs and the draw run over the
         step's effective set, so every draw ends balanced.  depth int32 [B, T', n] (last output).
         return_consensus: the minimum-risk choice among each image's draws (consensus(), uniform weights, consensus_normalize its normalize),
-        computed on the ids where the decode left them on the device: best int32 [B] and risk f32 [B, n] are appended as the last two outputs."""
+        computed on the ids where the decode left them on the device: best int32 [B] and risk f32 [B, n] are appended as the last two outputs.
+        consensus_cost: consensus()'s cost, "edit" or "bleu" (with "bleu" consensus_normalize must be left at its default)."""
         if return_depth and grammar is None:
             raise ValueError("return_depth needs grammar=")
+        _cost_kind("sample_decode: consensus_cost", consensus_cost)
+        if consensus_cost == "bleu" and consensus_normalize is not True:
+            raise ValueError("sample_decode: consensus_cost = \"bleu\" has no normalisation; leave consensus_normalize at its default")
         if return_consensus and int(max_iter) > _abi.LXO_EDIT_MAX_REF:
             raise ValueError("return_consensus: max_iter = %d exceeds the edit-distance kernel's limit of %d tokens" % (int(max_iter), _abi.LXO_EDIT_MAX_REF))
         box = []
@@ -1531,7 +1586,7 @@ class Engine(object):
         if return_depth:
             out.append(box[0][:, :steps])
         if return_consensus:
-            out += self._consensus_device(ids[:, :steps], id_end, None, consensus_normalize)[:2]
+            out += self._consensus_device(ids[:, :steps], id_end, None, consensus_normalize, consensus_cost)[:2]
         out = tuple(a.cpu().numpy() for a in out)
         return out if len(out) > 1 else out[0]
 

@@ -114,6 +114,32 @@ def bleu_score(references, hypotheses, max_n=4):
     return corpus_bleu([[ref] for ref in references], hypotheses, max_n)
 
 
+def sentence_bleu(hyp, ref):
+    """Sentence-level BLEU-4 of one hypothesis against one reference, the definition of include/lxo.h (lxo_sentence_bleu) in Python floats: clipped
+    matches m_n and totals t_n = max(1, |h| - n + 1) for n = 1 .. 4; add-one smoothing on the higher orders only (Lin and Och; nltk's
+    SmoothingFunction().method2): p_1 = m_1 / t_1, p_n = (m_n + 1) / (t_n + 1); brevity penalty 1 for |h| > |r|, else exp(1 - |r| / |h|);
+    0 without a common unigram (an empty hypothesis included); and 1 exactly for hyp == ref, whatever the smoothed formula says (two empty
+    sequences included), so that a reference costs 0 against itself."""
+    hyp, ref = [x for x in hyp], [x for x in ref]
+    if hyp == ref:
+        return 1.0
+    m = []
+    for n in range(1, 5):
+        R = _ngrams(ref, n)
+        m.append(sum(min(c, R[g]) for g, c in _ngrams(hyp, n).items()))
+    if m[0] == 0:
+        return 0.0
+    t = [max(1, len(hyp) - n + 1) for n in range(1, 5)]
+    logp = math.log(m[0] / float(t[0])) + sum(math.log((m[k] + 1) / float(t[k] + 1)) for k in (1, 2, 3))
+    bp = 1.0 if len(hyp) > len(ref) else math.exp(1 - len(ref) / float(len(hyp)))
+    return bp * math.exp(logp / 4)
+
+
+def sentence_bleu_cost(hyp, ref):
+    """1 - sentence_bleu(hyp, ref): the cost in [0, 1] that minimum-risk training and the consensus decode take with cost = "bleu"."""
+    return 1.0 - sentence_bleu(hyp, ref)
+
+
 def score_files(path_ref, path_hyp):
     """Reference: evaluation/text.py:12-38 (tokens split on single spaces)."""
     refs = [r.split(" ") for _, r in load_formulas(path_ref).items()]

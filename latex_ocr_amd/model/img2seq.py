@@ -8,7 +8,7 @@ uint8 [H,W,1] arrays and lists of int lists; the facade owns padding.
 import numpy as np
 
 from .base import BaseModel
-from .evaluation.text import levenshtein, score_files, truncate_end, write_answers
+from .evaluation.text import levenshtein, score_files, sentence_bleu_cost, truncate_end, write_answers
 from .params import dims_from_config
 from .utils.general import Config, Progbar, minibatches
 from .utils.image import pad_batch_images
@@ -51,6 +51,9 @@ class Img2SeqModel(BaseModel):
         if self._label_smoothing > 0.0 and getattr(config, "mrt", None) is not None:
             raise ValueError("training config: \"label_smoothing\" and \"mrt\" do not combine -- the minimum-risk step does not smooth its targets; "
                              "drop one of the two keys")
+        mrt = getattr(config, "mrt", None)
+        if mrt is not None:                                      # the cost of the minimum-risk step is refused here, not at the first batch
+            self._check_cost("training config: \"mrt\": \"cost\"", mrt.get("cost", "edit") if isinstance(mrt, dict) else getattr(mrt, "cost", "edit"))
         self.logger.info("Building model...")
         self._build_engine()
         self._lr_method = config.lr_method.lower()
@@ -138,11 +141,18 @@ class Img2SeqModel(BaseModel):
         lr_schedule.update(score=score)
         return score
 
-    MRT_KEYS = ("n", "alpha", "temperature", "top_k", "top_p", "on_device")
+    MRT_KEYS = ("n", "alpha", "temperature", "top_k", "top_p", "on_device", "cost")
+
+    @staticmethod
+    def _check_cost(what, cost):
+        """the cost a minimum-risk step or a consensus optimises: "edit" (the edit distance) or "bleu" (1 - sentence BLEU, evaluation/text.py)"""
+        if not isinstance(cost, str) or cost not in ("edit", "bleu"):
+            raise ValueError("%s must be \"edit\" or \"bleu\", got %r" % (what, cost))
+        return cost
 
     def _run_train_mrt(self, config, train_set, val_set, epoch, lr_schedule, mrt, keep):
-        """One epoch of minimum-risk training: the training config's optional "mrt": {"n", "alpha", "temperature", "top_k", "top_p", "on_device"} key
-        makes every batch one mrt_batch instead of one cross-entropy step; the sampling seed is the step counter.  Single process; the feed is the
+        """One epoch of minimum-risk training: the training config's optional "mrt": {"n", "alpha", "temperature", "top_k", "top_p", "on_device",
+        "cost"} key makes every batch one mrt_batch instead of one cross-entropy step; the sampling seed is the step counter.  Single process; the feed is the
         synchronous one (the candidates are built from the batch's own formulas: on the host, or with "on_device": true by Engine.mrt_sample_step).
         The epoch ends as _run_train's does."""
         if self.dist is not None:
@@ -165,7 +175,7 @@ class Img2SeqModel(BaseModel):
         return scores["perplexity"]
 
     def mrt_batch(self, images, formulas, lr, n=5, alpha=0.005, temperature=1.0, top_k=0, top_p=1.0, seed=0, include_reference=True, dropout=1,
-                  on_device=False):
+                  on_device=False, cost="edit"):
         """One minimum-risk training step on a batch (Engine.mrt_step): the model draws n transcriptions per image (Engine.sample_decode with
         temperature / top_k / top_p / seed); an image's candidates are its DISTINCT draws, each cut at its first END, and -- include_reference --
         its reference formula; a candidate costs levenshtein(candidate, reference) / max(len(reference), 1) (evaluation/text.py, the edit distance
@@ -173,9 +183,12 @@ class Img2SeqModel(BaseModel):
         candidates.  formulas: token-id lists or space-separated token strings, as score_batch takes them.
         on_device: the same candidates, costs and step through Engine.mrt_sample_step -- the draws are cut, compared and costed by device kernels and
         never visit the host; the default builds them here, as ever.
+        cost = "bleu": a candidate costs 1 - sentence BLEU against the reference (evaluation/text.py sentence_bleu_cost on the host path,
+        lxo_mrt_candidates_cost on the device path; the two agree within 1e-5) in place of the edit distance.
         -> {"risk": the mean expected cost before the update, "candidates": per image [{"text", "q": its probability among the candidates, "cost"}]}"""
         if len(images) != len(formulas):
             raise ValueError("mrt_batch: %d images but %d formulas" % (len(images), len(formulas)))
+        self._check_cost("mrt_batch: cost", cost)
         prepro = self._vocab.form_prepro
         refs = [tuple(prepro(f)) if isinstance(f, str) else tuple(int(x) for x in f) for f in formulas]
         id_end = self._vocab.id_end
@@ -186,7 +199,7 @@ class Img2SeqModel(BaseModel):
             risk, info = self.engine.mrt_sample_step(img, f, ln, id_end, self._vocab.id_pad, lr, alpha, n=n, temperature=temperature, top_k=top_k, top_p=top_p,
                                                      seed=seed, include_reference=include_reference,
                                                      max_iter=getattr(self._config, "max_length_formula", 150) + 1, clip=getattr(self, "_clip", -1),
-                                                     dropout=dropout)
+                                                     dropout=dropout, **({} if cost == "edit" else {"cost": cost}))
             out, at = [], 0
             for m in info["group_sizes"]:
                 out.append([{"text": " ".join(tok[int(i)] for i in info["cand"][r, :info["cand_lengths"][r] - 1]), "q": float(info["q"][r]),
@@ -204,7 +217,7 @@ class Img2SeqModel(BaseModel):
                     mine.append(c)
             cands += mine
             sizes.append(len(mine))
-            costs += [levenshtein(c, ref) / float(max(len(ref), 1)) for c in mine]
+            costs += [sentence_bleu_cost(c, ref) if cost == "bleu" else levenshtein(c, ref) / float(max(len(ref), 1)) for c in mine]
         f, ln = pad_batch_formulas([list(c) for c in cands], self._vocab.id_pad, id_end)
         risk, q = self.engine.mrt_step(img, f, ln, np.asarray(sizes), np.asarray(costs, np.float32), lr, alpha,
                                        clip=getattr(self, "_clip", -1), dropout=dropout)
@@ -476,7 +489,8 @@ class Img2SeqModel(BaseModel):
             alts.append([self._alt_entries(alt, b, int(emitted[b, i])) for b in range(ids.shape[0])])
         return hyps, scores, alts
 
-    def sample_batch(self, images, n, temperature=1.0, top_k=0, top_p=1.0, seed=0, banned=None, allowed=None, grammar=None, consensus=False):
+    def sample_batch(self, images, n, temperature=1.0, top_k=0, top_p=1.0, seed=0, banned=None, allowed=None, grammar=None, consensus=False,
+                     consensus_cost="edit"):
         """n sampled transcriptions per image (Engine.sample_decode), folded into their DISTINCT hypotheses: -> one dict per image,
         {"hypotheses": [{"text", "count", "logp": the model's sequence log-prob (sum of the token log-probs through END), "token_logp": [...]},
         ...] sorted by count, then log-prob, both descending, "agreement": top count / n}.  A hypothesis is a draw truncated at its first END; draws
@@ -486,13 +500,15 @@ class Img2SeqModel(BaseModel):
         consensus: the minimum-risk choice among the draws on top of the vote (Engine.sample_decode(return_consensus=True): the n draws with
         uniform weights, so a hypothesis weighs by its count): every hypothesis gains "risk", its expected edit distance (over the length of the
         other side) to the image's draws, and every image "consensus", the index into "hypotheses" of the one of least risk, and "expected_cost",
-        that risk -- a confidence that still tells hypotheses apart where every draw is distinct and every count 1.  Nothing else changes."""
+        that risk -- a confidence that still tells hypotheses apart where every draw is distinct and every count 1.  Nothing else changes.
+        consensus_cost = "bleu": the risk is the expected 1 - sentence BLEU against the image's draws (Engine.consensus(cost="bleu"))."""
+        self._check_cost("sample_batch: consensus_cost", consensus_cost)
         fd = self._get_feed_dict(images, dropout=1)
         max_iter = getattr(self._config, "max_length_formula", 150) + 1
         id_end = self._vocab.id_end
         res = self.engine.sample_decode(fd["img"], id_end, n=n, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, max_iter=max_iter,
                                         return_scores=True, allowed=self._token_sets(len(images), banned, allowed), return_consensus=bool(consensus),
-                                        **self._grammar(grammar))
+                                        **dict(self._grammar(grammar), **({} if consensus_cost == "edit" else {"consensus_cost": consensus_cost})))
         ids, logp = res[:2]
         best, risk = res[3:] if consensus else (None, None)
         out = []

@@ -15,7 +15,7 @@ alternatives=K: for a decode they come from a second, teacher-forced pass over t
 (Img2SeqModel.sample_batch; --temperature T, --top-k K, --top-p P and --seed S shape and repeat the draws; combines with --ban /
 --allow-file): one line with the agreement (top count / N), then one line per distinct hypothesis with its count and log-prob.
 --consensus (with --sample) adds the minimum-risk choice among the draws (sample_batch(consensus=True)): the head line names the hypothesis with
-the least expected edit distance to the draws and that cost, every hypothesis line carries its risk, and a * marks the chosen one.
+the least expected edit distance to the draws and that cost, every hypothesis line carries its risk, and a * marks the chosen one; --consensus-cost bleu (only with --sample N --consensus) makes that cost 1 - sentence BLEU.
 --balanced decodes under the delimiter grammar of the vocabulary (latex_ocr_amd.grammar.Grammar.latex: { }, \\left / \\right, \\begin{X} / \\end{X};
 --pairs "OPEN:CLOSE ..." names the pairs instead, each side a comma-separated token list): every hypothesis closes what it opens.  It
 combines with everything but --formula.  Without the flag, where the vocabulary has delimiters, a line "  balanced: yes / no" behind each
@@ -45,6 +45,8 @@ def main(argv=None):
     ap.add_argument("--top-p", type=float, default=1.0, help="--sample: draw among the smallest token set of mass >= P (1: off)")
     ap.add_argument("--seed", type=int, default=0, help="--sample: the same seed repeats the draws")
     ap.add_argument("--consensus", action="store_true", help="--sample: the hypothesis of least expected edit distance to the draws, and that cost")
+    ap.add_argument("--consensus-cost", choices=("edit", "bleu"), default=None,
+                    help="--sample N --consensus: the cost the consensus minimises, the edit distance (default) or 1 - sentence BLEU")
     ap.add_argument("--balanced", action="store_true", help="decode under the delimiter grammar: every hypothesis closes what it opens")
     ap.add_argument("--pairs", default=None, help='delimiter pairs "OPEN:CLOSE ..." (each side comma-separated tokens) instead of those read off the vocabulary')
     ap.add_argument("images", nargs="+")
@@ -57,6 +59,8 @@ def main(argv=None):
         ap.error("--sample takes 1 .. 16 and does not combine with --formula, --prefix or --alternatives")
     if a.consensus and not a.sample:
         ap.error("--consensus chooses among the draws of --sample N")
+    if a.consensus_cost is not None and not (a.sample and a.consensus):
+        ap.error("--consensus-cost names the cost of --sample N --consensus")
     d = a.results
     config_vocab, config_model = Config(d + "vocab.json"), Config(d + "model.json")
     vocab = Vocab(config_vocab)
@@ -114,6 +118,8 @@ def main(argv=None):
             continue
         if a.sample:
             more = {"consensus": True} if a.consensus else {}
+            if a.consensus_cost not in (None, "edit"):
+                more["consensus_cost"] = a.consensus_cost
             res = model.sample_batch([greyscale(img)], a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, **dict(dec, **more))[0]
             print(path, "~>", "%d draws\tagreement %.3f" % (a.sample, res["agreement"]))
             if a.consensus:
