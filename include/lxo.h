@@ -39,17 +39,35 @@ int lxo_shape_size(void);
  * ("transposed", TF [in,out] -> [out,in]) weight copy in the compute dtype.
  * dt: compute dtype; a_f32/c_f32: A / C are float even when dt == LXO_BF16.
  * Replaces tf.layers.dense / tf.matmul call sites (attention_mechanism.py:43,79;
- * attention_cell.py:82-84). */
+ * attention_cell.py:82-84).
+ * Operand contract (the kernels load whole 16-byte pieces of a row and do not check):
+ *  - K > 0 and K % 32 == 0 (else -2); M <= 0 or N <= 0 is an empty call (0, nothing written).
+ *  - every row of A and Bp starts on a 16-byte boundary: A and Bp 16-byte aligned, lda % 8 == 0 and ldb % 8 == 0 (% 4 where
+ *    the row is float); lda, ldb >= K.  Only columns 0..K of rows 0..M (0..N) are read.
+ *  - C [M][ldc] in the compute dtype (float with c_f32), ldc >= N, no alignment; only columns 0..N of rows 0..M are written.
+ *    accumulate != 0 adds the previous C (read in C's own type) to the result; it is defined for act == 0.
+ *  - small != 0 (the recurrent steps' M <= 64 shapes): with dt == LXO_BF16 it takes float A and float C only (else -3);
+ *    K % 256 == 0 and lda % 4 == 0 select the split-K skinny kernel, whose float A rows need 16-byte alignment only. */
 int lxo_gemm_nt(int dt, int a_f32, int c_f32, int small, const void* A, const void* Bp, void* C,
                 int M, int N, int K, int lda, int ldb, int ldc, const float* bias, int act,
                 float alpha, int accumulate, void* stream);
 
-/* C[I,J] += sum_m A[m,I] * B[m,J] (f32 output, atomics across nsplit row ranges). */
+/* C[I,J] += sum_m A[m,I] * B[m,J] (f32 output, atomics across nsplit row ranges).
+ * Operand contract:
+ *  - atomic != 0 adds into C; atomic == 0 stores the product over C and needs nsplit == 1 (else -2).  dt == LXO_F32 always uses one
+ *    row range (a reproducible sum), whatever nsplit says.  I, J or M <= 0 is an empty call (0, nothing written).
+ *  - the kernels read whole 8-column chunks of a row: lda >= round8(I) and ldb >= round8(J) (round8(x) = (x + 7) / 8 * 8), and the
+ *    columns I..round8(I) of A and J..round8(J) of B must be readable memory; their values never reach C.
+ *  - every row of A and B starts on a 16-byte boundary: A and B 16-byte aligned, lda % 8 == 0 and ldb % 8 == 0 (% 4 where the operand
+ *    is float).  Only rows 0..M are read; C [I][ldc] float, ldc >= J, only columns 0..J of rows 0..I are written. */
 int lxo_gemm_tn(int dt, int a_f32, int b_f32, const void* A, const void* B, float* C,
                 int M, int I, int J, int lda, int ldb, int ldc, int nsplit, int atomic, void* stream);
 
 /* split-K partial products of a skinny GEMM (the recurrent steps): slab[ks][M][ldc] = A[:, ks*128:+128] *
- * Bp[:, same]^T for ks < K/128, A float [M][lda], Bp compute dtype [N][ldb]; the consumer adds the slabs. */
+ * Bp[:, same]^T for ks < K/128, A float [M][lda], Bp compute dtype [N][ldb]; the consumer adds the slabs.
+ * Operand contract: K > 0, K % 128 == 0 and lda % 4 == 0 (else -2); M <= 0 or N <= 0 is an empty call (0, nothing written); rows of
+ * A and Bp on 16-byte boundaries (A, Bp 16-byte aligned, ldb % 8 == 0, % 4 for float Bp); slab_stride >= M * ldc, ldc >= N; only
+ * columns 0..N of rows 0..M of each slab are written (plain stores over whatever was there). */
 int lxo_gemm_slab(int dt, const void* A, const void* Bp, float* slab, int M, int N, int K, int lda, int ldb, int ldc,
                   long long slab_stride, void* stream);
 

@@ -749,7 +749,8 @@ int lxo_launch_gemm_tn(int dt, int a_f32, int b_f32, const GemmTN& p, hipStream_
 }
 
 int lxo_launch_gemm_slab(int dt, const GemmNT& p, float* slab, long long slab_stride, hipStream_t s) {
-    if (p.K % 128 != 0 || p.lda % 4 != 0) return -2;
+    if (p.K % 128 != 0 || p.K <= 0 || p.lda % 4 != 0) return -2;
+    if (p.M <= 0 || p.N <= 0) return 0;          // nothing to write (a grid of 0 workgroups is a launch error, not an empty launch)
     dim3 grid(cdiv(p.N, 64), p.K / 128, cdiv(p.M, 64));
     if (dt == LXO_F32) hipLaunchKernelGGL((gemm_slab_kernel<float>), grid, dim3(256), 0, s, p, slab, slab_stride);
     else hipLaunchKernelGGL((gemm_slab_kernel<bf16_t>), grid, dim3(256), 0, s, p, slab, slab_stride);
