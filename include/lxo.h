@@ -338,6 +338,43 @@ int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hyp_block_str
 int lxo_text_stats(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
                    const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
                    int pairs, int id_end, int32_t* stats_out, long long* corpus_io, int accumulate, void* stream);
+/* The edit alignment of pairs, on the device, shape-free: WHERE a hypothesis differs from its reference -- substitution, insertion and deletion
+ * counts, the token-to-token maps of both sides and the confusion pairs -- from the Levenshtein table lxo_edit_distance fills, with its path kept.
+ * ADDRESSING, LENGTHS, THE END CUT AND THE CLAMPING are lxo_edit_distance's (and lxo_text_stats'), argument for argument: the ids [B, max_steps, n] of
+ * a sampled decode are read in place, references are taken in pad_batch_formulas' layout.  Pair p has hypothesis h (m tokens) and reference r
+ * (n tokens) after the cut; both sides are at most LXO_EDIT_MAX_REF tokens wide and ANY int32 value is a token.
+ * THE DEFINITION: D[i][j] is the Levenshtein table of h[0 .. i) against r[0 .. j) (D[i][0] = i, D[0][j] = j).  The canonical alignment is the path
+ * walked back from (i, j) = (m, n) until (0, 0), taking at every cell the FIRST rule that applies:
+ *   1. i > 0, j > 0 and D[i][j] == D[i-1][j-1] + (h[i-1] != r[j-1]): a diagonal step -- a MATCH if the tokens are equal, else a SUBSTITUTION; i--, j--.
+ *   2. else i > 0 and D[i][j] == D[i-1][j] + 1: an INSERTION (h[i-1] is a token the reference does not have); i--.
+ *   3. else: a DELETION (r[j-1] is a token the hypothesis lacks); j--.
+ * The rule is local -- a cell's step follows from the cell, its three predecessors and one token compare -- so it is decided while the table is filled.
+ * OUTPUTS (device; each nullable, not all NULL):
+ *   hyp_align int32 [pairs][T]: position i < m: the reference position it is aligned with (match or substitution), -1 for an insertion; i >= m: -2.
+ *   ref_align int32 [pairs][ref_ld]: position j < n: the hypothesis position it is aligned with, -1 for a deletion; j >= n: -2.
+ *   counts_out int32 [pairs][LXO_ALIGN_COUNTS]: matches M, substitutions S, insertions I, deletions D, |h|, |r|.  S + I + D is the value
+ *     lxo_edit_distance writes for the pair; M + S + I = |h|; M + S + D = |r|.
+ *   corpus_io int64 [LXO_ALIGN_CORPUS]: [0 .. 5] the column sums of the six counts, [6] the pairs, [7] the alignment steps left out of the
+ *     confusion matrix (below; 0 without one).  accumulate = 0 overwrites, accumulate = 1 adds to what is there -- lxo_text_stats' semantics.
+ *   confusion_io int64 [(V + 1) * (V + 1)], V >= 1 an argument: entry [a][b] counts the alignment steps with reference token a and hypothesis token b;
+ *     the index V stands for "no token": an insertion of b goes to [V][b], a deletion of a to [a][V]; matches go on the diagonal, so a row gives a
+ *     token's recall; [V][V] is never written.  A step with a token outside [0, V) is counted in the counts but not entered, and counted in
+ *     corpus_io[7].  The same accumulate governs it (0: the matrix is zeroed first).
+ * The waves add into corpus_io and confusion_io with 64-bit integer atomics: integer sums, the same in every order.
+ * SCRATCH: device memory of lxo_edit_align_scratch_bytes(pairs, T, ref_ld) bytes -- at most pairs * T * 256: per row of the table one dword per lane
+ * of the pair's wave, a strip's 2-bit steps -- passed as scratch / scratch_bytes; its content after the call means nothing.
+ * One launch, one wave per pair (behind one that zeroes what is overwritten); no host synchronisation, capturable into a graph, the same bytes in
+ * every run.  pairs == 0: no pair kernel runs; corpus_io and confusion_io are zeroed when accumulate == 0 and untouched otherwise.
+ * -1, with the reason in lxo_last_error and nothing written: all five outputs NULL; confusion_io with V < 1; scratch NULL or scratch_bytes below the
+ * size function's value when pairs > 0 and T > 0; accumulate not 0 or 1; otherwise lxo_text_stats' own cases -- a NULL hyp or ref; pairs, T, G or a
+ * stride negative; hyp_block or per_ref < 1; G < 1 with pairs > 0; T outside 0 .. LXO_EDIT_MAX_REF; ref_ld outside 1 .. LXO_EDIT_MAX_REF. */
+#define LXO_ALIGN_COUNTS 6   /* int32 per pair  */
+#define LXO_ALIGN_CORPUS 8   /* int64 per corpus */
+size_t lxo_edit_align_scratch_bytes(int pairs, int T, int ref_ld);
+int lxo_edit_align(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                   const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
+                   int pairs, int id_end, int32_t* hyp_align, int32_t* ref_align, int32_t* counts_out, long long* corpus_io, long long* confusion_io,
+                   int V, int accumulate, void* scratch, size_t scratch_bytes, void* stream);
 /* The candidate rows of a minimum-risk step, built on the device from a sampled decode: three launches, no host synchronisation.
  * ids int32 [B, max_steps, n] as lxo_sample_decode leaves them and steps = the steps it ran (0 <= steps <= max_steps, 1 <= n <= 16);
  * ref int32 [B, Tr] with ref_len [B] in pad_batch_formulas' layout (tokens, END, PAD; length = tokens + 1), 1 <= Tr <= LXO_EDIT_MAX_REF.

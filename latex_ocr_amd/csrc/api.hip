@@ -192,6 +192,28 @@ extern "C" int lxo_text_stats(const int32_t* hyp, int hyp_block, long long hyp_b
     CHECK_LAUNCH(lxo_k_text_stats(a, (hipStream_t)stream), "lxo_text_stats");
     return 0;
 }
+static_assert(LXO_ALIGN_COUNTS == kAlignCounts && LXO_ALIGN_CORPUS == kAlignCorpus, "include/lxo.h and csrc/seqcost.h disagree on the alignment rows");
+extern "C" size_t lxo_edit_align_scratch_bytes(int pairs, int T, int ref_ld) { return lxo_k_edit_align_scratch_bytes(pairs, T, ref_ld); }
+extern "C" int lxo_edit_align(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
+                              const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
+                              int pairs, int id_end, int32_t* hyp_align, int32_t* ref_align, int32_t* counts_out, long long* corpus_io,
+                              long long* confusion_io, int V, int accumulate, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!hyp || !ref) return fail(-1, "lxo_edit_align: null hyp or ref");
+    if (!hyp_align && !ref_align && !counts_out && !corpus_io && !confusion_io) return fail(-1, "lxo_edit_align: the five outputs are all NULL");
+    if (pairs < 0 || T < 0 || G < 0 || hyp_block_stride < 0 || hyp_row_stride < 0 || hyp_tok_stride < 0)
+        return fail(-1, "lxo_edit_align: a negative count or stride");
+    if (hyp_block < 1 || per_ref < 1 || (pairs > 0 && G < 1)) return fail(-1, "lxo_edit_align: hyp_block < 1, per_ref < 1 or no reference row");
+    if (T > LXO_EDIT_MAX_REF) return fail(-1, "lxo_edit_align: T outside 0 .. LXO_EDIT_MAX_REF (a hypothesis wider than the kernel's staging limit)");
+    if (ref_ld < 1 || ref_ld > LXO_EDIT_MAX_REF) return fail(-1, "lxo_edit_align: ref_ld outside 1 .. LXO_EDIT_MAX_REF (a reference longer than the kernel's column limit)");
+    if (accumulate != 0 && accumulate != 1) return fail(-1, "lxo_edit_align: accumulate must be 0 or 1");
+    if (confusion_io && V < 1) return fail(-1, "lxo_edit_align: a confusion matrix needs V >= 1");
+    if (pairs > 0 && T > 0 && (!scratch || scratch_bytes < lxo_k_edit_align_scratch_bytes(pairs, T, ref_ld)))
+        return fail(-1, "lxo_edit_align: scratch is NULL or smaller than lxo_edit_align_scratch_bytes");
+    const AlignArgs a = {hyp, hyp_len, ref, ref_len, ref_of, hyp_align, ref_align, counts_out, corpus_io, confusion_io, static_cast<unsigned*>(scratch),
+                         hyp_block_stride, hyp_row_stride, hyp_tok_stride, hyp_block, T, G, ref_ld, per_ref, pairs, id_end, confusion_io ? V : 1, accumulate};
+    CHECK_LAUNCH(lxo_k_edit_align(a, (hipStream_t)stream), "lxo_edit_align");
+    return 0;
+}
 static_assert(LXO_BLEU_COUNTS == kBleuCounts, "include/lxo.h and csrc/seqcost.h disagree on the sentence-BLEU counts");
 extern "C" int lxo_sentence_bleu(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
                                  const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,

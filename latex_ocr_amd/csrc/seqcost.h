@@ -80,3 +80,22 @@ struct ConsBleuArgs {
     int B, n, T, id_end;
 };
 int lxo_k_consensus_bleu(const ConsBleuArgs& a, hipStream_t st);
+
+// The edit alignment of pairs (lxo_edit_align, include/lxo.h holds the definition and the path rule): pairs addressed, cut and clamped as TextArgs'.
+// hyp_align (nullable) int32 [pairs][T], ref_align (nullable) int32 [pairs][ref_ld], counts (nullable) int32 [pairs][kAlignCounts]; corpus (nullable)
+// int64 [kAlignCorpus] and confusion (nullable) int64 [(V + 1)(V + 1)], overwritten (zeroed by a launch in front) or added to (accumulate) with 64-bit
+// integer atomics.  steps: the scratch, one dword per lane per row of the table -- pair p's row i (1 .. m) at dword (p T + i - 1) 64 + lane, the 2-bit
+// steps of the lane's strip of columns, column e of the strip in bits 2e, 2e + 1 (0 diagonal, 1 insertion, 2 deletion).  One wave per pair, no host
+// synchronisation.  T or ref_ld > kEditMaxRef: -2.
+constexpr int kAlignCounts = 6, kAlignCorpus = 8;
+struct AlignArgs {
+    const int* hyp; const int* hyp_len; const int* ref; const int* ref_len; const int* ref_of;
+    int* hyp_align; int* ref_align; int* counts; long long* corpus; long long* confusion; unsigned* steps;
+    long long hb_stride, hr_stride, ht_stride;
+    int hyp_block, T, G, ref_ld, per_ref, pairs, id_end, V, accumulate;
+};
+inline size_t lxo_k_edit_align_scratch_bytes(int pairs, int T, int ref_ld) {
+    (void)ref_ld;
+    return pairs > 0 && T > 0 ? (size_t)pairs * (size_t)T * 256u : 0;
+}
+int lxo_k_edit_align(const AlignArgs& a, hipStream_t st);

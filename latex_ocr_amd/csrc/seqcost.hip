@@ -4,6 +4,7 @@
 // And the counts an evaluation's text metrics are made of (lxo_text_stats): clipped n-gram matches, lengths, distance and exact match per pair,
 // summed over the pairs into a corpus row.  And that metric as a cost: the sentence-level BLEU of a pair (lxo_sentence_bleu), the consensus under
 // 1 - sBLEU (lxo_consensus_bleu) and the candidate rows costed with it (lxo_mrt_candidates_cost); their float tails are f32 in one fixed order.
+// And the path through the Levenshtein table (lxo_edit_align): substitution, insertion and deletion counts, the token maps of both sides, confusion pairs.
 #include "seqcost.h"
 
 namespace {
@@ -561,6 +562,177 @@ __global__ __launch_bounds__(256) void cons_bleu_select_kernel(ConsBleuArgs a) {
     if (lane == 0) a.best[g] = best;
 }
 
+// ---- edit alignment of a pair (lxo_edit_align): the path through the table edit_wave fills ----
+// The forward phase is edit_wave's row step with the path kept: once a row's values are final a lane holds, for every cell (i, j) of its strip, the cell
+// (cur), the cell above (prev) and the cell above-left (prev of the column to the left) -- what the path rule of include/lxo.h reads: 0 a diagonal step
+// if cur == above-left + (x != b), else 1 an insertion if cur == above + 1, else 2 a deletion.  The 2-bit steps of the strip, column e in bits 2e, 2e + 1,
+// are one dword of the lane; the 64 dwords of row i (1 .. m) are stored as one coalesced row at steps[(i - 1) 64 + lane].  Row 0 and column 0 are implied
+// (deletions and insertions).  (A template of its own beside edit_wave: the kernels built on edit_wave keep their instructions.)
+template <int CPL>
+LXO_DEV void align_forward(const int* hp, long long hts, int m, const int* rp, int n, int lane, unsigned* steps) {
+    int b[CPL], prev[CPL];
+#pragma unroll
+    for (int e = 0; e < CPL; ++e) {
+        const int j = lane * CPL + e;
+        b[e] = j < n ? rp[j] : -1;
+        prev[e] = j + 1;
+    }
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const int xi = hp[(i0 + lane < m ? i0 + lane : i0) * hts];
+        const int cnt = min(64, m - i0);
+        for (int k = 0; k < cnt; ++k) {
+            const int x = __shfl(xi, k), i = i0 + k + 1;
+            int left = __shfl_up(prev[CPL - 1], 1);
+            if (lane == 0) left = i - 1;
+            int s[CPL], run = 0x3fffffff;
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) {
+                const int diag = e ? prev[e - 1] : left;
+                const int t = min(prev[e] + 1, diag + (x != b[e] ? 1 : 0));
+                run = min(run, t - (lane * CPL + e + 1));
+                s[e] = run;
+            }
+            int v = lane == 0 ? min(run, i) : run;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(v, d);
+                if (lane >= d) v = min(v, o);
+            }
+            int ex = __shfl_up(v, 1);
+            if (lane == 0) ex = i;
+            unsigned w = 0;
+            int diag = left;
+#pragma unroll
+            for (int e = 0; e < CPL; ++e) {
+                const int cur = lane * CPL + e + 1 + min(s[e], ex);
+                const unsigned step = cur == diag + (x != b[e] ? 1 : 0) ? 0u : (cur == prev[e] + 1 ? 1u : 2u);
+                w |= step << (2 * e);
+                diag = prev[e];
+                prev[e] = cur;
+            }
+            steps[(long long)(i - 1) * 64 + lane] = w;
+        }
+    }
+}
+
+constexpr int kAlignAhead = 8;      // step rows the backtrace loads in one go, a second set in flight behind them
+
+// The rows i, i - 1, .. of the steps, the lane's own dword of each (row numbers below 1 repeat row 1: loaded, never walked)
+LXO_DEV void align_rows(unsigned (&w)[kAlignAhead], const unsigned* steps, int i, int lane) {
+#pragma unroll
+    for (int u = 0; u < kAlignAhead; ++u) w[u] = steps[(long long)(max(i - u, 1) - 1) * 64 + lane];
+}
+
+// One wave per pair.  (a) align_forward.  (b) The walk back from (m, n): the path is serial in (i, j), but the row it reads next is not path-dependent --
+// a row is left by exactly one diagonal or insertion step -- so the rows are loaded kAlignAhead at a time, the next set while the current one is walked,
+// and within a row the run of deletions left of j is resolved on the wave: every lane masks its strip to the columns <= j, a ballot finds the last lane
+// with a step that is no deletion and one shuffle fetches its column and kind.  i and j stay wave-uniform scalars; a row costs no dependent load.  Both
+// maps are staged in LDS as int16 with the defaults an unvisited position has (-1: inserted / deleted, -2: behind the sequence), so the walk stores the
+// diagonal steps only.  (c) The maps go out coalesced, one lane per position enters its step in the confusion matrix, the counts are reduced over the wave.
+template <int CPL>
+__global__ __launch_bounds__(256) void align_kernel(AlignArgs a) {
+    __shared__ short map[4][2 * kEditMaxRef];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = blockIdx.x * 4 + wave;
+    if (p >= a.pairs) return;
+    const int r = min(max(a.ref_of ? a.ref_of[p] : p / a.per_ref, 0), a.G - 1);
+    const int* hp = a.hyp + (long long)(p / a.hyp_block) * a.hb_stride + (long long)(p % a.hyp_block) * a.hr_stride;
+    const int* rp = a.ref + (long long)r * a.ref_ld;
+    const int m = __builtin_amdgcn_readfirstlane(cut_len(hp, a.ht_stride, min(a.hyp_len ? min(max(a.hyp_len[p], 0), a.T) : a.T, kEditMaxRef), a.id_end, lane));
+    const int n = __builtin_amdgcn_readfirstlane(cut_len(rp, 1, min(a.ref_len ? min(max(a.ref_len[r], 0), a.ref_ld) : a.ref_ld, 64 * CPL), a.id_end, lane));
+    short* ha = map[__builtin_amdgcn_readfirstlane(wave)];
+    short* ra = ha + kEditMaxRef;
+    for (int t = lane; t < kEditMaxRef; t += 64) { ha[t] = t < m ? -1 : -2; ra[t] = t < n ? -1 : -2; }
+    __builtin_amdgcn_wave_barrier();
+
+    if (m > 0 && n > 0) {
+        unsigned* steps = a.steps + (long long)p * a.T * 64;
+        align_forward<CPL>(hp, a.ht_stride, m, rp, n, lane, steps);
+        // The step rows are read back by the wave that stored them, every lane the dwords it wrote itself: nothing crosses lanes through memory.  The
+        // stores must have left the wave before the first load of the walk is issued: wait for the outstanding vector-memory operations (vmcnt(0)).
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        int i = m, j = n;
+        unsigned w[kAlignAhead], ahead[kAlignAhead];
+        align_rows(w, steps, i, lane);
+        while (i > 0 && j > 0) {
+            align_rows(ahead, steps, i - kAlignAhead, lane);
+#pragma unroll
+            for (int u = 0; u < kAlignAhead; ++u) {
+                if (i <= 0 || j <= 0) break;
+                const int k = min(max(j - lane * CPL, 0), CPL);                          // columns of the strip at or left of j
+                const unsigned keep = k >= 16 ? 0xffffffffu : (1u << (2 * k)) - 1u;
+                const unsigned stay = ~(w[u] >> 1) & 0x55555555u & keep;                 // bit 2e: column e leaves the row (a diagonal step or an insertion)
+                const unsigned long long any = __ballot(stay != 0u);
+                if (!any) { j = 0; break; }                                              // deletions down to column 0; the rows above are insertions: the defaults
+                const int L = 63 - (int)__builtin_clzll(any);
+                const int e = (31 - (int)__builtin_clz(stay | 1u)) >> 1;
+                const int got = __builtin_amdgcn_readfirstlane(__shfl((int)((e << 2) | ((w[u] >> (2 * e)) & 3u)), L));
+                const int jj = L * CPL + (got >> 2) + 1;                                 // the columns jj + 1 .. j are deleted: the defaults
+                if ((got & 3) == 0) {
+                    if (lane == 0) { ha[i - 1] = (short)(jj - 1); ra[jj - 1] = (short)(i - 1); }
+                    j = jj - 1;
+                } else {
+                    j = jj;
+                }
+                --i;
+            }
+#pragma unroll
+            for (int u = 0; u < kAlignAhead; ++u) w[u] = ahead[u];
+        }
+    }
+    __builtin_amdgcn_wave_barrier();                                    // lane 0's LDS stores, read by every lane below (in-order LDS: no s_barrier)
+
+    const int V = a.V;
+    const long long ld = (long long)V + 1;
+    unsigned long long* conf = reinterpret_cast<unsigned long long*>(a.confusion);
+    int cM = 0, cS = 0, cI = 0, cD = 0, out = 0;
+    for (int t0 = 0; t0 < a.T; t0 += 64) {
+        const int t = t0 + lane;
+        if (t >= a.T) break;
+        const int v = ha[t];
+        if (a.hyp_align) a.hyp_align[(long long)p * a.T + t] = v;
+        if (t >= m) continue;
+        const int hb = hp[t * a.ht_stride], rb = v >= 0 ? rp[v] : 0;
+        if (v < 0) ++cI; else if (hb == rb) ++cM; else ++cS;
+        if (conf) {
+            if (hb >= 0 && hb < V && rb >= 0 && rb < V) atomicAdd(conf + (v >= 0 ? rb : V) * ld + hb, 1ull);
+            else ++out;
+        }
+    }
+    for (int t0 = 0; t0 < a.ref_ld; t0 += 64) {
+        const int t = t0 + lane;
+        if (t >= a.ref_ld) break;
+        const int v = ra[t];
+        if (a.ref_align) a.ref_align[(long long)p * a.ref_ld + t] = v;
+        if (t >= n || v >= 0) continue;
+        ++cD;
+        if (conf) {
+            const int rb = rp[t];
+            if (rb >= 0 && rb < V) atomicAdd(conf + rb * ld + V, 1ull);
+            else ++out;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cM += __shfl_xor(cM, o); cS += __shfl_xor(cS, o); cI += __shfl_xor(cI, o); cD += __shfl_xor(cD, o); out += __shfl_xor(out, o);
+    }
+    // lane c holds value c of the row (the counts, then the pair count and the steps left out of the matrix): one store and one atomic instruction of the wave
+    const int row[kAlignCorpus] = {cM, cS, cI, cD, m, n, p == 0 ? a.pairs : 0, out};
+    int v = 0;
+#pragma unroll
+    for (int c = 0; c < kAlignCorpus; ++c) if (lane == c) v = row[c];
+    if (a.counts && lane < kAlignCounts) a.counts[(long long)p * kAlignCounts + lane] = v;
+    // 64-bit integer adds, whose sum is the same in every order
+    if (a.corpus && lane < kAlignCorpus) atomicAdd(reinterpret_cast<unsigned long long*>(a.corpus) + lane, (unsigned long long)v);
+}
+
+// What a call overwrites is zeroed by a launch in front of the pair waves, which add into it: the corpus row by the first threads, the matrix grid-stride.
+__global__ __launch_bounds__(256) void align_zero_kernel(long long* corpus, long long* confusion, long long cells) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (corpus && t < kAlignCorpus) corpus[t] = 0;
+    if (confusion)
+        for (long long c = t; c < cells; c += (long long)gridDim.x * 256) confusion[c] = 0;
+}
+
 }  // namespace
 
 #define LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, __VA_ARGS__)
@@ -574,6 +746,23 @@ int lxo_k_edit_distance(const EditArgs& a, hipStream_t st) {
     else if (a.ref_ld <= 256) LAUNCH(edit_kernel<4>, grid, a);
     else if (a.ref_ld <= 512) LAUNCH(edit_kernel<8>, grid, a);
     else LAUNCH(edit_kernel<16>, grid, a);
+    return (int)hipGetLastError();
+}
+
+int lxo_k_edit_align(const AlignArgs& a, hipStream_t st) {
+    if (a.ref_ld > kEditMaxRef || a.T > kEditMaxRef) return -2;
+    // what is overwritten is zeroed first: the waves add into it (a launch, as lxo_k_text_stats zeroes its row)
+    if (!a.accumulate && (a.corpus || a.confusion)) {
+        const long long cells = a.confusion ? ((long long)a.V + 1) * ((long long)a.V + 1) : 0;
+        LAUNCH(align_zero_kernel, (int)min(max((cells + 255) / 256, 1ll), 1024ll), a.corpus, a.confusion, cells);
+    }
+    if (a.pairs == 0) return (int)hipGetLastError();
+    const int grid = cdiv(a.pairs, 4);
+    if (a.ref_ld <= 64) LAUNCH(align_kernel<1>, grid, a);
+    else if (a.ref_ld <= 128) LAUNCH(align_kernel<2>, grid, a);
+    else if (a.ref_ld <= 256) LAUNCH(align_kernel<4>, grid, a);
+    else if (a.ref_ld <= 512) LAUNCH(align_kernel<8>, grid, a);
+    else LAUNCH(align_kernel<16>, grid, a);
     return (int)hipGetLastError();
 }
 

@@ -19,6 +19,7 @@ from .model import params as PP
 
 # Engine.score(alternatives=k): per position the k best token ids and their log-probs, the given token's rank and the step's entropy
 Alternatives = namedtuple("Alternatives", ["ids", "logp", "rank", "entropy"])
+Alignment = namedtuple("Alignment", ["hyp_align", "ref_align", "counts", "corpus", "confusion"])
 
 
 def _p(t):
@@ -988,6 +989,58 @@ class Engine(object):
         self._ck(self.lib.lxo_text_stats(_p(h), block, geom[0], geom[1], geom[2], T, _p(hl), _p(r), G, Tr, _p(rl), _p(ri), per_ref, pairs,
                                          -1 if id_end is None else int(id_end), _p(stats), _p(corpus), int(accumulate), self._stream()), what)
         return stats, corpus
+
+    def edit_align(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None, corpus=None, confusion=None, return_maps=True):
+        """The edit alignment of every pair on the device (lxo_edit_align; include/lxo.h holds the definition and the path rule): WHERE a hypothesis
+        differs from its reference.  -> Alignment(hyp_align, ref_align, counts, corpus, confusion): hyp_align int32 [pairs, T] = per hypothesis
+        position the reference position it is aligned with, -1 for an inserted token, -2 behind the sequence; ref_align int32 [pairs, Tr] likewise
+        with -1 for a deleted token (both None with return_maps=False); counts int32 [pairs, 6] = matches, substitutions, insertions, deletions,
+        |h|, |r| -- host arrays.  hyp, ref, the lengths, id_end and ref_index as text_stats takes them: host arrays, device tensors, strided views
+        and the [B, T, n] ids of sample_decode read in place.
+        corpus: a device int64 [8] tensor the call ADDS into (the column sums of the counts, the pairs, the steps left out of the matrix), or True
+        for a fresh one; confusion: a device int64 [V + 1, V + 1] tensor the call adds its alignment steps into -- [a][b] = reference token a
+        against hypothesis token b, index V = no token -- or True for a fresh one over this engine's vocabulary.  Both come back in the result,
+        left on the device (None when not asked for): an evaluation accumulates batch after batch and copies once
+        (model/evaluation/text.py error_report reads them).  A ValueError before any launch as text_stats', and for a corpus or confusion of another
+        kind."""
+        ha, ra, counts, corpus, confusion = self._edit_align_device("edit_align", hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, return_maps, True,
+                                                                    corpus, confusion)
+        host = lambda t: None if t is None else t.cpu().numpy()
+        return Alignment(host(ha), host(ra), host(counts), corpus, confusion)
+
+    def _edit_align_device(self, what, hyp, ref, hyp_lengths, ref_lengths, id_end, ref_index, want_maps, want_counts, corpus, confusion):
+        """edit_align's checks and its call: -> (hyp_align, ref_align, counts, corpus, confusion), all left on the device, None where not asked for.
+        corpus / confusion: None, True (a fresh zeroed tensor) or the tensor to add into.  The scratch is one cached tensor that grows."""
+        h, block, geom, T, hl, r, G, Tr, rl, ri, per_ref, pairs = self._pair_args(what, hyp, ref, hyp_lengths, ref_lengths, ref_index)
+        if corpus is True:
+            corpus = torch.zeros(_abi.LXO_ALIGN_CORPUS, dtype=torch.int64, device=self.device)
+        elif corpus is not None and (not isinstance(corpus, torch.Tensor) or corpus.device != self.device or corpus.dtype != torch.int64
+                                     or tuple(corpus.shape) != (_abi.LXO_ALIGN_CORPUS,) or not corpus.is_contiguous()):
+            raise ValueError("%s: corpus must be True or a contiguous int64 [%d] tensor on %s" % (what, _abi.LXO_ALIGN_CORPUS, self.device))
+        if confusion is True:
+            confusion = torch.zeros(self.n_tok + 1, self.n_tok + 1, dtype=torch.int64, device=self.device)
+        elif confusion is not None and (not isinstance(confusion, torch.Tensor) or confusion.device != self.device or confusion.dtype != torch.int64
+                                        or confusion.dim() != 2 or confusion.shape[0] != confusion.shape[1] or confusion.shape[0] < 2
+                                        or not confusion.is_contiguous()):
+            raise ValueError("%s: confusion must be True or a contiguous square int64 [V + 1, V + 1] tensor on %s, V >= 1" % (what, self.device))
+        ha = torch.empty(pairs, T, dtype=torch.int32, device=self.device) if want_maps else None
+        ra = torch.empty(pairs, Tr, dtype=torch.int32, device=self.device) if want_maps else None
+        counts = torch.empty(pairs, _abi.LXO_ALIGN_COUNTS, dtype=torch.int32, device=self.device) if want_counts or (corpus is None and confusion is None) else None
+        if pairs == 0:                                             # nothing to align: the rows are empty, the sums stay as they are
+            return ha, ra, counts, corpus, confusion
+        if Tr == 0 and ra is not None:                             # (the call below sees references of one unread column)
+            ra_call = torch.empty(pairs, 1, dtype=torch.int32, device=self.device)
+        else:
+            ra_call = ra
+        h, r, Tr, rl = self._pair_fill(h, T, r, G, Tr, rl)
+        need = int(self.lib.lxo_edit_align_scratch_bytes(pairs, T, Tr))
+        if getattr(self, "_align_scratch", None) is None or self._align_scratch.numel() < need:
+            self._align_scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        self._ck(self.lib.lxo_edit_align(_p(h), block, geom[0], geom[1], geom[2], T, _p(hl), _p(r), G, Tr, _p(rl), _p(ri), per_ref, pairs,
+                                         -1 if id_end is None else int(id_end), _p(ha) if T else None, _p(ra_call), _p(counts), _p(corpus), _p(confusion),
+                                         int(confusion.shape[0]) - 1 if confusion is not None else 1, 1, _p(self._align_scratch), self._align_scratch.numel(),
+                                         self._stream()), what)
+        return ha, ra, counts, corpus, confusion
 
     def sentence_bleu(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None, return_counts=False):
         """Sentence-level BLEU-4 per pair on the device (lxo_sentence_bleu; include/lxo.h holds the definition: add-one smoothing on the orders

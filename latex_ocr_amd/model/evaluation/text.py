@@ -166,3 +166,88 @@ def scores_from_counts(corpus):
         "ExactMatchScore": c[12] / float(max(c[13], 1)) * 100,
         "EditDistance": (1.0 - c[10] / tot if tot else 1.0) * 100,
     }
+
+
+def align(hyp, ref):
+    """The canonical edit alignment of one hypothesis against one reference, the definition of include/lxo.h (lxo_edit_align) in plain Python -- the
+    product's host path, as sentence_bleu is for its kernel.  D[i][j] is the Levenshtein table; the path is walked back from (len(hyp), len(ref)),
+    at every cell the FIRST rule that applies: a diagonal step (match or substitution) if D[i][j] == D[i-1][j-1] + (h != r), else an insertion
+    (a hypothesis token the reference lacks) if D[i][j] == D[i-1][j] + 1, else a deletion.  The rule is local, so the steps are noted row by row
+    while the table is filled and only they are kept.
+    -> (hyp_align, ref_align, counts): per hypothesis position the reference position it is aligned with or -1 (inserted), per reference position
+    the hypothesis position or -1 (deleted), and [matches, substitutions, insertions, deletions, len(hyp), len(ref)]."""
+    h, r = [x for x in hyp], [x for x in ref]
+    m, n = len(h), len(r)
+    prev = list(range(n + 1))
+    steps = []
+    for i in range(1, m + 1):
+        cur, row, x = [i] + [0] * n, [1] * (n + 1), h[i - 1]
+        for j in range(1, n + 1):
+            d = prev[j - 1] + (0 if x == r[j - 1] else 1)
+            cur[j] = min(d, prev[j] + 1, cur[j - 1] + 1)
+            row[j] = 0 if cur[j] == d else (1 if cur[j] == prev[j] + 1 else 2)
+        steps.append(row)
+        prev = cur
+    ha, ra = [-1] * m, [-1] * n
+    counts = [0, 0, 0, 0, m, n]
+    i, j = m, n
+    while i > 0 and j > 0:
+        s = steps[i - 1][j]
+        if s == 0:
+            counts[0 if h[i - 1] == r[j - 1] else 1] += 1
+            ha[i - 1], ra[j - 1] = j - 1, i - 1
+            i, j = i - 1, j - 1
+        elif s == 1:
+            i -= 1
+        else:
+            j -= 1
+    counts[2], counts[3] = ha.count(-1), ra.count(-1)
+    return ha, ra, counts
+
+
+def error_report(corpus, confusion, rev_vocab, top=20):
+    """The error breakdown of a set of pairs from what lxo_edit_align sums over them (include/lxo.h): corpus, its 8 integers -- matches,
+    substitutions, insertions, deletions, hypothesis tokens, reference tokens, pairs, steps left out of the matrix -- and confusion, its
+    (V + 1) x (V + 1) matrix, [a][b] = steps with reference token a and hypothesis token b, index V = no token.  rev_vocab maps an id to its
+    token (a dict or a list; an id it lacks is shown as its number).  -> a dict:
+      matches, substitutions, insertions, deletions, hyp_tokens, ref_tokens, pairs, left_out: the integers;
+      SubRate, InsRate, DelRate: percent of the reference tokens (0.0 without any);
+      confusions: the `top` largest off-diagonal [a][b] with a, b < V, as (ref_token, hyp_token, count);
+      deleted / inserted: the `top` largest of column V / row V, as (token, count);
+      recall: per reference token seen at least once, diagonal over row sum, the `top` lowest, as (token, recall, seen).
+    Entries that are 0 are not listed, and ties in every ranking go to the lower ids (reference id first), so the report is one fixed object."""
+    c = [int(x) for x in corpus]
+    if len(c) != 8:
+        raise ValueError("error_report: 8 integers expected in corpus, got %d" % len(c))
+    flat = [int(x) for x in (confusion.reshape(-1) if hasattr(confusion, "reshape") else confusion)]
+    V = int(round(math.sqrt(len(flat)))) - 1
+    if V < 1 or (V + 1) * (V + 1) != len(flat):
+        raise ValueError("error_report: confusion must hold (V + 1)^2 integers with V >= 1, got %d" % len(flat))
+    C = [flat[a * (V + 1):(a + 1) * (V + 1)] for a in range(V + 1)]
+    name = (lambda i: rev_vocab.get(i, str(i))) if hasattr(rev_vocab, "get") else (lambda i: rev_vocab[i] if 0 <= i < len(rev_vocab) else str(i))
+    rate = lambda x: 100.0 * x / float(c[5]) if c[5] else 0.0
+    pairs = sorted(((-C[a][b], a, b) for a in range(V) for b in range(V) if a != b and C[a][b]))[:top]
+    deleted = sorted(((-C[a][V], a) for a in range(V) if C[a][V]))[:top]
+    inserted = sorted(((-C[V][b], b) for b in range(V) if C[V][b]))[:top]
+    seen = [(C[a][a] / float(sum(C[a])), a, sum(C[a])) for a in range(V) if sum(C[a])]
+    return {
+        "matches": c[0], "substitutions": c[1], "insertions": c[2], "deletions": c[3], "hyp_tokens": c[4], "ref_tokens": c[5], "pairs": c[6], "left_out": c[7],
+        "SubRate": rate(c[1]), "InsRate": rate(c[2]), "DelRate": rate(c[3]),
+        "confusions": [(name(a), name(b), -k) for k, a, b in pairs],
+        "deleted": [(name(a), -k) for k, a in deleted],
+        "inserted": [(name(b), -k) for k, b in inserted],
+        "recall": [(name(a), q, s) for q, a, s in sorted(seen)[:top]],
+    }
+
+
+def format_error_report(report):
+    """error_report's dict as the text evaluate_txt.py --errors writes"""
+    out = ["pairs %d  reference tokens %d  hypothesis tokens %d" % (report["pairs"], report["ref_tokens"], report["hyp_tokens"]),
+           "matches %d  substitutions %d  insertions %d  deletions %d  (left out of the matrix: %d)"
+           % (report["matches"], report["substitutions"], report["insertions"], report["deletions"], report["left_out"]),
+           "SubRate %.2f  InsRate %.2f  DelRate %.2f" % (report["SubRate"], report["InsRate"], report["DelRate"]), "", "confusions (reference -> hypothesis, count)"]
+    out += ["  %s -> %s  %d" % x for x in report["confusions"]]
+    out += ["", "deleted (reference tokens the hypotheses lack)"] + ["  %s  %d" % x for x in report["deleted"]]
+    out += ["", "inserted (hypothesis tokens the references lack)"] + ["  %s  %d" % x for x in report["inserted"]]
+    out += ["", "lowest recall (token, recall, occurrences)"] + ["  %s  %.4f  %d" % x for x in report["recall"]]
+    return "\n".join(out) + "\n"

@@ -273,6 +273,48 @@ class Img2SeqModel(BaseModel):
             return scores
         return scores, (np.concatenate([r.cpu().numpy() for r in rows]) if rows else np.zeros((0, 12), np.int32))
 
+    def error_analysis(self, references, hypotheses, per_sample=False, top=20):
+        """The error breakdown of hypotheses against references, on the device: substitution, insertion and deletion counts and rates, the most
+        frequent confusions, the tokens most often dropped and inserted, the tokens of lowest recall -- evaluation/text.py error_report's dict.
+        references and hypotheses are lists of id sequences, pair by pair, each cut at the vocabulary's END.  The pairs go through
+        Engine.edit_align (include/lxo.h: lxo_edit_align holds the alignment's definition) in batches of SCORE_IDS_BATCH into ONE corpus row and
+        ONE confusion matrix on the device, copied once at the end.  per_sample=True: -> (dict, counts, hyp_maps, ref_maps) with counts int32
+        [N, 6] = matches, substitutions, insertions, deletions, |h|, |r| and the two maps as lists of lists: per hypothesis position the reference
+        position it is aligned with or -1 (inserted), per reference position the hypothesis position or -1 (deleted).
+        score_ids' empty-line quirk does NOT apply here: an empty sequence is empty -- it aligns with nothing, and every token of the other side is
+        an insertion or a deletion."""
+        from .evaluation.text import error_report
+        if len(references) != len(hypotheses):
+            raise ValueError("error_analysis: %d references but %d hypotheses" % (len(references), len(hypotheses)))
+        id_end, V = self._vocab.id_end, self._vocab.n_tok
+        eng = self.engine
+        corpus = confusion = True                                  # (the first batch's call makes the two accumulators, the others add into them)
+        rows, hmaps, rmaps = [], [], []
+        for at in range(0, len(references), self.SCORE_IDS_BATCH):
+            sides = []
+            for seqs in (hypotheses[at:at + self.SCORE_IDS_BATCH], references[at:at + self.SCORE_IDS_BATCH]):
+                cut = [truncate_end([int(i) for i in s], id_end) for s in seqs]
+                ln = np.array([len(c) for c in cut], np.int32)
+                a = np.zeros((len(cut), max(int(ln.max()), 1)), np.int32)
+                for i, c in enumerate(cut):
+                    a[i, :len(c)] = c
+                sides += [a, ln]
+            ha, ra, counts, corpus, confusion = eng._edit_align_device("error_analysis", sides[0], sides[2], sides[1], sides[3], None, None, per_sample,
+                                                                       per_sample, corpus, confusion)
+            if per_sample:
+                rows.append(counts)
+                hmaps.append((ha, sides[1]))
+                rmaps.append((ra, sides[3]))
+        if corpus is True:                                         # no pair
+            report = error_report([0] * 8, [0] * ((V + 1) * (V + 1)), self._vocab.id_to_tok, top)
+        else:
+            report = error_report(corpus.cpu().numpy(), confusion.cpu().numpy(), self._vocab.id_to_tok, top)
+        if not per_sample:
+            return report
+        cut_rows = lambda maps: [[int(x) for x in row[:n]] for t, ln in maps for row, n in zip(t.cpu().numpy(), ln)]
+        counts = np.concatenate([r.cpu().numpy() for r in rows]) if rows else np.zeros((0, 6), np.int32)
+        return report, counts, cut_rows(hmaps), cut_rows(rmaps)
+
     def _beam_kwargs(self):
         """The diversity-penalty arguments of one Engine.beam_decode call (decoder.py:67-68); the seed is the number of beam decodes so far."""
         cfg = self._config
