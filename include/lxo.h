@@ -283,6 +283,28 @@ int lxo_ce_loss_weighted(const lxo_shape* s, void* ws, const int32_t* formula, c
  * -1, nothing written, the reason in lxo_last_error: eps not finite or outside [0, 1); a NULL ws, formula or lengths. */
 int lxo_ce_loss_smoothed(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths, float eps,
                          const float* w_tok, const float* w_row, float inv_norm, const float* norm_dev, void* stream);
+/* Soft targets (knowledge distillation from a teacher's top-k per position): the target of a live row is a sparse distribution the caller supplies,
+ * mixed into lxo_ce_loss_smoothed's.  soft_ids int32 [B, T, k] and soft_p f32 [B, T, k] on the device -- lxo_score_alternatives' layout, B the shape's --
+ * with 1 <= k <= 16; the slots of row (b, t) are read only where t < lengths[b].  eps, w_tok, w_row, inv_norm and norm_dev are lxo_ce_loss_smoothed's,
+ * lambda lies in [0, 1].  Per live row, with y the clamped target, lse the log-sum-exp, p the soft-max, U = lse - (sum_{j < V} x_j) / V and CE = lse - x_y:
+ *     slot i counts iff 0 <= soft_ids[i] < V; its mass is m_i = soft_p[i] when it counts, else 0 (the device does not check masses);
+ *     Sigma = sum_i m_i, added in ascending i in f32;   rest = max(0, 1 - Sigma), the mass the top-k leaves out, spread uniformly over [0, V);
+ *     tau_j = sum_{i: ids_i == j} m_i + rest / V   (slots that name the same token add up, in ascending i);
+ *     lambda_r = 0 when Sigma == 0 (no counting slot: the row has no teacher and is lxo_ce_loss_smoothed's row), else lambda;
+ *     q_j = (1 - lambda_r) [(1 - eps) [j == y] + eps / V] + lambda_r tau_j;   S = sum_j q_j = (1 - lambda_r) + lambda_r (Sigma + rest)  (1 unless the masses exceed 1);
+ *     L = (1 - lambda_r) [(1 - eps) CE + eps U] + lambda_r [sum_i m_i (lse - x_{ids_i}) + rest U]   (the cross-entropy of q against p: the KL divergence
+ *         plus the teacher's entropy, a constant);
+ *     d(logits)[t * B + b][j] = (S p_j - q_j) * (w * inv_norm) for j < V;   0 in [V, Vp) and on rows t >= lengths[b].
+ * ws region "loss" = {sum w L, live token count, sum w, sum CE (plain, unweighted)} through the ordered slots of "det_part" in every mode: the same bytes in
+ * every run; [1] and [3] are the bytes lxo_ce_loss_weighted leaves for the same weights.  The forward chain's error word turns [0] into NaN.
+ * IDENTITIES: a row whose slots are all -1 carries lxo_ce_loss_smoothed's d(logits) bytes (with eps == 0: lxo_ce_loss_weighted's), and with every row
+ * like that the four statistics are its bytes too; lambda == 0 IS the lxo_ce_loss_smoothed call.  A live row's sum_j d(logits)_j is 0 up to rounding.
+ * -1, nothing written, the reason in lxo_last_error: a NULL ws, formula, lengths, soft_ids or soft_p; k outside 1 .. 16; eps not finite or outside
+ * [0, 1); lambda not finite or outside [0, 1].
+ * Not here: a temperature on the student's logits, renormalising the top-k instead of spreading the rest, a confidence penalty. */
+int lxo_ce_loss_soft(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,
+                     float eps, float lambda, int k, const int32_t* soft_ids, const float* soft_p,
+                     const float* w_tok, const float* w_row, float inv_norm, const float* norm_dev, void* stream);
 /* Minimum-risk weights on the device, shape-free: rows group_off[g] .. group_off[g + 1] - 1 (device int32 [G + 1], ascending, group_off[0] == 0,
  * group_off[G] <= rows) are the candidate transcriptions of image g, seq_logp their sequence log-probs (lxo_score_tokens' seq_out) and cost their costs
  * (device f32 [rows]).  Q_c = softmax_c(alpha * seq_logp_c) over the group (maximum subtracted), R_g = sum_c Q_c cost_c,

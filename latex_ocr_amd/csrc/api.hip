@@ -152,6 +152,19 @@ extern "C" int lxo_ce_loss_smoothed(const lxo_shape* s, void* ws, const int32_t*
     CHECK_LAUNCH(lxo_impl_ce_loss(P, ws, formula, lengths, inv_norm, norm_dev, (hipStream_t)stream, w_tok, w_row, &eps), "lxo_ce_loss_smoothed");
     return 0;
 }
+extern "C" int lxo_ce_loss_soft(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths, float eps, float lambda, int k,
+                                const int32_t* soft_ids, const float* soft_p, const float* w_tok, const float* w_row, float inv_norm, const float* norm_dev,
+                                void* stream) {
+    MAKE_PLAN(P, s);
+    if (!ws || !formula || !lengths) return fail(-1, "lxo_ce_loss_soft: null ws, formula or lengths");
+    if (!soft_ids || !soft_p) return fail(-1, "lxo_ce_loss_soft: null soft_ids or soft_p");
+    if (k < 1 || k > 16) return fail(-1, "lxo_ce_loss_soft: k outside 1 .. 16");
+    if (!(eps - eps == 0.f) || !(eps >= 0.f && eps < 1.f)) return fail(-1, "lxo_ce_loss_soft: eps is not a finite number in [0, 1)");
+    if (!(lambda - lambda == 0.f) || !(lambda >= 0.f && lambda <= 1.f)) return fail(-1, "lxo_ce_loss_soft: lambda is not a finite number in [0, 1]");
+    const CeSoft soft = {soft_ids, soft_p, k, lambda};
+    CHECK_LAUNCH(lxo_impl_ce_loss(P, ws, formula, lengths, inv_norm, norm_dev, (hipStream_t)stream, w_tok, w_row, &eps, &soft), "lxo_ce_loss_soft");
+    return 0;
+}
 extern "C" int lxo_mrt_weights(const float* seq_logp, const float* cost, const int32_t* group_off, int G, int rows, float alpha,
                                float* w_out, float* q_out, float* risk_out, void* stream) {
     if (!w_out || !seq_logp || !cost || !group_off) return fail(-1, "lxo_mrt_weights: null w_out, seq_logp, cost or group_off");

@@ -10,9 +10,14 @@ struct CeWeights { const float* tok; const float* row; };
 // (p_j - q_j) * scale -- the target column subtracts (1.f - eps) + eps_v, every other eps_v -- and the row's loss (1 - eps) CE + eps (lse - sum_{j < V} x_j / V);
 // the statistics are the four, {sum w L, token count, sum w, sum CE (plain)}, with or without weights (without: w = 1.f), through `det` as above
 struct CeSmooth { float eps, eps_v; };
+// soft (nullable, lxo_ce_loss_soft; include/lxo.h holds the definition): device ids / p [B][T][k], 1 <= k <= 16 (else -2), lxo_k_score_alt's layout -- slot i of a
+// live row counts iff 0 <= ids[i] < V and then carries the mass p[i]; Sigma = their sum in ascending i, rest = max(0, 1 - Sigma) is spread over [0, V),
+// tau_j = sum_{ids_i == j} p_i (ascending i) + rest / V, and the row's target is (1 - lambda) * (the smoothed target) + lambda * tau; a row with Sigma == 0 has no
+// teacher and is lxo_ce_loss_smoothed's row.  d(logits) is (S p_j - q_j) * scale with S = sum_j q_j.  Needs `smooth` (eps may be 0); the four statistics as above
+struct CeSoft { const int* ids; const float* p; int k; float lambda; };
 int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
                   const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st,      // chain_err (nullable): error word of the persistent decoder chain; non-zero poisons the loss (NaN)
-                  const CeWeights* weights = nullptr, const CeSmooth* smooth = nullptr);
+                  const CeWeights* weights = nullptr, const CeSmooth* smooth = nullptr, const CeSoft* soft = nullptr);
 // minimum-risk weights of candidate rows grouped by image (rows group_off[g] .. group_off[g + 1] - 1, G groups): Q = softmax(alpha seq_logp) over a group,
 // R_g = sum Q cost, w_out = alpha Q (R_g - cost), q_out (nullable) = Q, risk_out (nullable) [1] = sum_g R_g added in ascending g; rows behind the last group: 0.
 // Offsets are clamped into [0, rows] on the device.  No atomics: the same bytes in every run

@@ -438,6 +438,81 @@ LXO_DEV float ce_target(bool hit, const CeSmooth& s) {
 }
 // a live row's smoothed loss from its plain CE, its log-sum-exp and the sum of its logits over [0, V): (1 - eps) CE + eps U, U = lse - sum / V = -mean_j log p_j
 LXO_DEV float ce_smoothed(const CeSmooth& s, float ce, float lse, float xsum, int V) { return (1.f - s.eps) * ce + s.eps * (lse - xsum / (float)V); }
+// Soft targets (lxo_ce_loss_soft): behind the CeSmooth the pack may END in one CeSoft (SF).  The row steps it adds:
+//   ce_soft_row   lanes 0 .. k - 1 load their slot (a slot that does not count: id -1, mass 0.f) and its logit, the way xt = lg[tgt] is loaded; Sigma and
+//                 sum_i m_i (lse - x_i) are added in ascending i from wave-uniform reads of the slot lanes; a row past lengths[b] reads no slot
+//   ce_soft_tau   a column's teacher mass before rest / V: the counting slots that name it, in ascending i -- no read-modify-write of the stored row, no
+//                 atomics, so slots that share an id are as deterministic as any other
+//   ce_soft_grad  S p_j - q_j, q_j = (1 - lambda_r) * ce_target + lambda_r * (tau_j + rest / V)
+// A row with lambda_r = 0 (Sigma == 0: no teacher) takes none of the last two: the kernels send it, wave-uniformly, through the smoothed row's own
+// statements, so its d(logits) and statistics are lxo_ce_loss_smoothed's bytes whatever the compiler contracts into an fma on either path
+LXO_DEV float ce_weight(const RowTok&, const CeSmooth&, const CeSoft&) { return 1.f; }
+LXO_DEV float ce_weight(const RowTok& r, const CeWeights& q, const CeSmooth&, const CeSoft&) { return ce_weight(r, q); }
+LXO_DEV CeSmooth ce_smooth(const CeSmooth& s, const CeSoft&) { return s; }
+LXO_DEV CeSmooth ce_smooth(const CeWeights&, const CeSmooth& s, const CeSoft&) { return s; }
+template <typename... W> struct ce_has_soft { static constexpr bool value = false; };
+template <> struct ce_has_soft<CeSoft> { static constexpr bool value = true; };
+template <typename A, typename... W> struct ce_has_soft<A, W...> { static constexpr bool value = ce_has_soft<W...>::value; };
+template <typename... W> LXO_DEV CeSoft ce_soft(const W&...) { return {nullptr, nullptr, 0, 0.f}; }
+LXO_DEV CeSoft ce_soft(const CeSmooth&, const CeSoft& f) { return f; }
+LXO_DEV CeSoft ce_soft(const CeWeights&, const CeSmooth&, const CeSoft& f) { return f; }
+// lane i's value in every lane, i wave-uniform: a v_readlane into a scalar register, no LDS crossbar round trip
+#ifdef LXO_HIPSIM
+LXO_DEV int wave_bcast(int v, int i) { return __shfl(v, i); }
+#else
+LXO_DEV int wave_bcast(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
+#endif
+LXO_DEV float wave_bcast(float v, int i) { return __int_as_float(wave_bcast(__float_as_int(v), i)); }
+struct SoftRow {
+    int id; float m;                        // lane i < k: slot i
+    float lam, keep, S, rest, rest_v, dot;  // wave-uniform: lambda_r, 1 - lambda_r, sum_j q_j, rest, rest / V, sum_i m_i (lse - x_i)
+};
+LXO_DEV SoftRow ce_soft_row(const CeSoft& f, const RowTok& r, const float* lg, int lane, int V, float lse) {
+    SoftRow s;
+    s.id = -1; s.m = 0.f;
+    float c = 0.f;
+    if (r.live && lane < f.k) {
+        const long long o = r.o * f.k + lane;
+        const int v = f.ids[o];
+        if (v >= 0 && v < V) { s.id = v; s.m = f.p[o]; c = s.m * (lse - lg[v]); }
+    }
+    float sigma = 0.f;
+    s.dot = 0.f;
+    for (int i = 0; i < f.k; ++i) { sigma += wave_bcast(s.m, i); s.dot += wave_bcast(c, i); }
+    s.rest = fmaxf(0.f, 1.f - sigma);
+    s.rest_v = s.rest / (float)V;
+    s.lam = sigma == 0.f ? 0.f : f.lambda;
+    s.keep = 1.f - s.lam;
+    s.S = s.keep + s.lam * (sigma + s.rest);
+    return s;
+}
+LXO_DEV float ce_soft_tau(const SoftRow& s, int k, int j) {
+    float t = 0.f;
+    for (int i = 0; i < k; ++i) {
+        const int id_i = wave_bcast(s.id, i);
+        const float m_i = wave_bcast(s.m, i);
+        t += id_i == j ? m_i : 0.f;
+    }
+    return t;
+}
+// ... of the four columns j0 .. j0 + 3 of a register row's quarter q, j0 = 4 (lane + 64 q): a slot's quarter is id >> 8, wave-uniform -- a quarter no slot
+// names costs a scalar compare per slot, and a slot costs its compare-select-adds in one quarter only
+LXO_DEV void ce_soft_tau4(const SoftRow& s, int k, int q, int j0, float (&t)[4]) {
+    t[0] = t[1] = t[2] = t[3] = 0.f;
+    for (int i = 0; i < k; ++i) {
+        const int id_i = wave_bcast(s.id, i);
+        const float m_i = wave_bcast(s.m, i);
+        if ((id_i >> 8) != q) continue;
+        const int d = id_i - j0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] += d == e ? m_i : 0.f;
+    }
+}
+LXO_DEV float ce_soft_grad(const SoftRow& s, float pr, float hard, float tau) { return s.S * pr - (s.keep * hard + s.lam * (tau + s.rest_v)); }
+// a live row's soft loss from its smoothed loss: (1 - lambda_r) L_smoothed + lambda_r (sum_i m_i (lse - x_i) + rest U)
+LXO_DEV float ce_soft_loss(const SoftRow& s, float l_smoothed, float lse, float xsum, int V) {
+    return s.keep * l_smoothed + s.lam * (s.dot + s.rest * (lse - xsum / (float)V));
+}
 // d(logits) scale of a row: inv_ntok on a live unweighted row, the single f32 product w * inv_norm on a weighted one, 0 past lengths[b]
 template <bool WT>
 LXO_DEV float ce_scale(const RowTok& r, float w, float inv_ntok) {
@@ -495,6 +570,7 @@ LXO_DEV void beam_emit(int b, int k, int tid, int time, int id, int par, float v
 // W = CeWeights (lxo_ce_loss_weighted): the row's scale is w * inv_norm and the statistics are the four of ce_stats; everything else is the same row
 // W ending in CeSmooth (lxo_ce_loss_smoothed): the sum of the logits over [0, V) rides the third pass, on the values it loads anyway -- a lane adds its
 // columns in ascending order, then the wave -- and ce_target stands in place of the one-hot
+// W ending in CeSoft (lxo_ce_loss_soft): the row takes its own branch below -- the instantiations without one are, statement for statement, what they were
 template <typename CT, typename... W>
 __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ logits, const int* __restrict__ formula,
                                                      const int* __restrict__ lengths, CT* __restrict__ dlogits,
@@ -502,6 +578,7 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
                                                      const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp, W... wt) {
     constexpr bool WT = sizeof...(W) != 0;
     constexpr bool SM = ce_has_smooth<W...>::value;
+    constexpr bool SF = ce_has_soft<W...>::value;
     __shared__ float red[WT ? 16 : 8];
     inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -515,6 +592,31 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
         const float lse = strided_lse<false>(lg, lane, V, nullptr);
         const float w = ce_weight(r, wt...);
         const float scale = ce_scale<WT>(r, w, inv_ntok);
+        if constexpr (SF) {
+            // the soft row: the smoothed row's steps, the teacher's mass in every column's target.  The column loop is wave-uniform (the slot reads are)
+            const CeSoft sf = ce_soft(wt...);
+            const SoftRow sr = ce_soft_row(sf, r, lg, lane, V, lse);
+            if (sr.lam != 0.f) {                                   // (no teacher: the smoothed row below, statement for statement -- its bytes)
+                float xs = 0.f;
+                for (int jb = 0; jb < Vp; jb += 64) {
+                    const int j = jb + lane;
+                    const float tau = ce_soft_tau(sr, sf.k, j);
+                    float g = 0.f;
+                    if (j < V) {
+                        const float xj = lg[j];
+                        xs += xj;
+                        g = ce_soft_grad(sr, expf(xj - lse), ce_target<true>(j == tgt, sm), tau) * scale;
+                    }
+                    if (j < Vp) dl[j] = from_f32<CT>(g);
+                }
+                xs = wave_sum(xs);
+                if (r.live) {
+                    const float ce = lse - lg[tgt];
+                    ce_stats_smoothed(ce_sum, n_sum, w_sum, u_sum, w, ce_soft_loss(sr, ce_smoothed(sm, ce, lse, xs, V), lse, xs, V), ce);
+                }
+                continue;
+            }
+        }
         float xs = 0.f;
         for (int j = lane; j < Vp; j += 64) {
             float g = 0.f;
@@ -545,6 +647,7 @@ __global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restri
                                                           const unsigned* __restrict__ chain_err, int B, int T, int V, int Vp, W... wt) {
     constexpr bool WT = sizeof...(W) != 0;
     constexpr bool SM = ce_has_smooth<W...>::value;
+    constexpr bool SF = ce_has_soft<W...>::value;
     constexpr bool BF = is_bf16<CT>::value;
     __shared__ float red[WT ? 16 : 8];
     inv_ntok = ce_begin(chain_err, loss_acc, ntok_dev, inv_ntok);
@@ -562,6 +665,37 @@ __global__ __launch_bounds__(256) void ce_loss_rows_kernel(const float* __restri
         const float lse = row_lse<BF, KV>(x);
         const float w = ce_weight(r, wt...);
         const float scale = ce_scale<WT>(r, w, inv_ntok);
+        if constexpr (SF) {
+            // the soft row: the smoothed row's steps, the teacher's mass in every column's target; still one packed store per four columns
+            const CeSoft sf = ce_soft(wt...);
+            const SoftRow sr = ce_soft_row(sf, r, lg, lane, V, lse);
+            if (sr.lam != 0.f) {                                   // (no teacher: the smoothed row below, statement for statement -- its bytes)
+#pragma unroll
+                for (int q = 0; q < KV / 4; ++q) {
+                    const int j0 = 4 * (lane + 64 * q);
+                    float tau[4];
+                    ce_soft_tau4(sr, sf.k, q, j0, tau);
+                    if (j0 >= Vp) continue;
+                    float g[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int j = j0 + e;
+                        const float pr = row_exp<BF>(x[4 * q + e] - lse);
+                        g[e] = j < V ? ce_soft_grad(sr, pr, ce_target<true>(j == tgt, sm), tau[e]) * scale : 0.f;
+                    }
+                    if constexpr (BF) { const u32x2 pk = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])}; *reinterpret_cast<u32x2*>(dl + j0) = pk; }
+                    else { const f32x4 gv = {g[0], g[1], g[2], g[3]}; *reinterpret_cast<f32x4*>(dl + j0) = gv; }
+                }
+                float xs = 0.f;
+#pragma unroll
+                for (int q = 0; q < KV / 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xs += 4 * (lane + 64 * q) + e < V ? x[4 * q + e] : 0.f;
+                xs = wave_sum(xs);
+                if (r.live) ce_stats_smoothed(ce_sum, n_sum, w_sum, u_sum, w, ce_soft_loss(sr, ce_smoothed(sm, lse - xt, lse, xs, V), lse, xs, V), lse - xt);
+                continue;
+            }
+        }
 #pragma unroll
         for (int q = 0; q < KV / 4; ++q) {
             const int j0 = 4 * (lane + 64 * q);
@@ -1152,7 +1286,7 @@ __global__ __launch_bounds__(BS_TH) void beam_step_fast_kernel(const float* __re
 
 int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* lengths, void* dlogits, float* loss_acc, float inv_ntok,
                   const float* ntok_dev, const unsigned* chain_err, int B, int T, int V, int Vp, DetScratch det, hipStream_t st, const CeWeights* weights,
-                  const CeSmooth* smooth) {
+                  const CeSmooth* smooth, const CeSoft* soft) {
     int g = cdiv(T * B, 4);
     float* part = (det.p && det.floats >= 1024) ? det.p : nullptr;      // loss_acc is zero on entry (lxo_impl_ce_loss)
     const bool four = weights || smooth;
@@ -1160,10 +1294,15 @@ int lxo_k_ce_loss(int dt, const float* logits, const int* formula, const int* le
     if (four && !(det.p && det.floats >= 2048)) return -2;              // the four weighted / smoothed statistics go through the ordered slots only
     const CeWeights wt = weights ? *weights : CeWeights{};
     const CeSmooth sm = smooth ? *smooth : CeSmooth{};
+    if (soft && (!smooth || soft->k < 1 || soft->k > 16)) return -2;    // soft targets ride behind a CeSmooth (eps may be 0), their k is lxo_k_score_alt's
+    const CeSoft sf = soft ? *soft : CeSoft{};
 #define CE_ARGS(CT_) logits, formula, lengths, (CT_*)dlogits, loss_acc, part, inv_ntok, ntok_dev, chain_err, B, T, V, Vp
-    // CE_WT(CT, KERNEL<...): KERNEL<...> or, with weights, KERNEL<..., CeWeights>; with smoothing KERNEL<..., CeSmooth> and KERNEL<..., CeWeights, CeSmooth>
+    // CE_WT(CT, KERNEL<...): KERNEL<...> or, with weights, KERNEL<..., CeWeights>; with smoothing KERNEL<..., CeSmooth> and KERNEL<..., CeWeights, CeSmooth>;
+    // with soft targets a CeSoft behind either of the last two
 #define CE_WT(CT_, ...) do { \
-        if (weights && smooth) LAUNCH((__VA_ARGS__, CeWeights, CeSmooth>), g, CE_ARGS(CT_), wt, sm); \
+        if (weights && soft) LAUNCH((__VA_ARGS__, CeWeights, CeSmooth, CeSoft>), g, CE_ARGS(CT_), wt, sm, sf); \
+        else if (soft) LAUNCH((__VA_ARGS__, CeSmooth, CeSoft>), g, CE_ARGS(CT_), sm, sf); \
+        else if (weights && smooth) LAUNCH((__VA_ARGS__, CeWeights, CeSmooth>), g, CE_ARGS(CT_), wt, sm); \
         else if (smooth) LAUNCH((__VA_ARGS__, CeSmooth>), g, CE_ARGS(CT_), sm); \
         else if (weights) LAUNCH((__VA_ARGS__, CeWeights>), g, CE_ARGS(CT_), wt); \
         else LAUNCH((__VA_ARGS__>), g, CE_ARGS(CT_)); } while (0)

@@ -4,6 +4,7 @@
 struct DecPrefix;                     // head_kernels.h
 struct DecAllow;
 struct DecSample;
+struct CeSoft;
 const char* lxo_ws_name(int id);
 int lxo_impl_pack_weights(const Plan& P, const float* prm, void* wp, hipStream_t st);
 int lxo_impl_encoder_fwd(const Plan& P, const float* prm, const void* wp, void* ws, const uint8_t* img, hipStream_t st);
@@ -11,7 +12,8 @@ int lxo_impl_encoder_bwd(const Plan& P, const float* prm, const void* wp, void* 
                          int last_layer, int first_layer, hipStream_t st, void* const* ready = nullptr);
 int lxo_impl_decoder_train_fwd(const Plan& P, const float* prm, const void* wp, void* ws, const int* formula, hipStream_t st, const int* lengths = nullptr);
 int lxo_impl_ce_loss(const Plan& P, void* ws, const int* formula, const int* lengths, float inv_ntok, const float* ntok_dev, hipStream_t st,
-                     const float* w_tok = nullptr, const float* w_row = nullptr, const float* smooth_eps = nullptr);
+                     const float* w_tok = nullptr, const float* w_row = nullptr, const float* smooth_eps = nullptr,
+                     const CeSoft* soft = nullptr);
 int lxo_impl_score_tokens(const Plan& P, void* ws, const int* formula, const int* lengths, float* logp_out, int* top1_out, float* seq_out, hipStream_t st);
 int lxo_impl_score_alternatives(const Plan& P, void* ws, const int* formula, const int* lengths, int k, const DecAllow* allow, int* ids_out, float* logp_out,
                                 int* rank_out, float* ent_out, hipStream_t st);

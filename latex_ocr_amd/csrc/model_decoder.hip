@@ -358,15 +358,16 @@ int lxo_impl_decoder_train_fwd(const Plan& P, const float* prm, const void* wp, 
 // w_tok / w_row (lxo_ce_loss_weighted; both NULL: the unweighted loss): ws region "loss" then holds {sum w CE, token count, sum w, sum CE}
 // smooth_eps (lxo_ce_loss_smoothed; NULL: one-hot targets): *smooth_eps in [0, 1) is the label smoothing, the region then {sum w L, token count, sum w,
 // sum CE (plain)} with or without weights
+// soft (lxo_ce_loss_soft; NULL: none; needs smooth_eps): the teacher's slots and lambda; lambda == 0 is the smoothed call, and takes it
 int lxo_impl_ce_loss(const Plan& P, void* ws, const int* formula, const int* lengths, float inv_ntok, const float* ntok_dev, hipStream_t st,
-                     const float* w_tok, const float* w_row, const float* smooth_eps) {
+                     const float* w_tok, const float* w_row, const float* smooth_eps, const CeSoft* soft) {
     HIPRC(hipMemsetAsync(P.ws<float>(ws, W_LOSS), 0, 64, st));
     const CeWeights wt = {w_tok, w_row};
     const CeSmooth sm = {smooth_eps ? *smooth_eps : 0.f, smooth_eps ? *smooth_eps / (float)P.s.V : 0.f};      // eps_v: ONE f32 division
     RC(lxo_k_ce_loss(P.s.dtype, P.ws<float>(ws, W_LOGITS), formula, lengths, P.ws<void>(ws, W_DLOGITS), P.ws<float>(ws, W_LOSS),
                      inv_ntok, ntok_dev, chain_err(P, ws, kChainFwd), P.s.B, P.s.T, P.s.V, P.Vp,
                      DetScratch{P.ws<float>(ws, W_DET), P.wbytes[W_DET] / 4}, st,      // every mode: per-workgroup partial statistics added in order (25 us; the atomic form measured 53)
-                     (w_tok || w_row) ? &wt : nullptr, smooth_eps ? &sm : nullptr));
+                     (w_tok || w_row) ? &wt : nullptr, smooth_eps ? &sm : nullptr, (soft && soft->lambda != 0.f) ? soft : nullptr));
     return 0;
 }
 

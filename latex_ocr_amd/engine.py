@@ -19,6 +19,7 @@ from .model import params as PP
 
 # Engine.score(alternatives=k): per position the k best token ids and their log-probs, the given token's rank and the step's entropy
 Alternatives = namedtuple("Alternatives", ["ids", "logp", "rank", "entropy"])
+_SoftDev = namedtuple("_SoftDev", ["ids", "p", "k", "lam"])          # soft targets behind their checks: device int32 / f32 [B, T, k], lambda
 Alignment = namedtuple("Alignment", ["hyp_align", "ref_align", "counts", "corpus", "confusion"])
 
 
@@ -455,8 +456,71 @@ class Engine(object):
             return t
         return t.pin_memory().to(self.device, non_blocking=True)
 
+    def _soft_dev(self, who, soft_targets, soft_weight, B, T, lengths=None):
+        """The soft targets before any launch -> _SoftDev (device ids int32 / masses f32 [B, T, k], lambda).  soft_targets: an Alternatives (its ids
+        and logp: the masses are exp(logp), taken on the device, -inf is mass 0) or a pair (ids [B, T, k], p [B, T, k]), host arrays or device
+        tensors.  A ValueError for a wrong shape, k outside 1 .. 16, soft_weight outside [0, 1] and -- host arrays only, a look at a device tensor
+        would cost a synchronisation -- for a counted mass that is negative, NaN or infinite and for a position whose counted masses exceed
+        1 + 1e-3.  A slot counts where 0 <= id < V; with host lengths only the positions t < lengths[b] are looked at, as on the device."""
+        if isinstance(soft_targets, _SoftDev):
+            return soft_targets
+        try:
+            lam = float(soft_weight)
+        except (TypeError, ValueError):
+            raise ValueError("%s: soft_weight must be a number in [0, 1], got %r" % (who, soft_weight))
+        if not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
+            raise ValueError("%s: soft_weight must be a finite number in [0, 1], got %r" % (who, soft_weight))
+        is_logp = isinstance(soft_targets, Alternatives)
+        if is_logp:
+            ids, val = soft_targets.ids, soft_targets.logp
+        else:
+            try:
+                ids, val = soft_targets
+            except (TypeError, ValueError):
+                raise ValueError("%s: soft_targets must be an Alternatives or a pair (ids [B, T, k], p [B, T, k])" % who)
+        shp = tuple(ids.shape)
+        if len(shp) != 3 or shp[:2] != (B, T) or tuple(val.shape) != shp:
+            raise ValueError("%s: soft_targets must be ids and %s of shape [B = %d, T = %d, k], got %s and %s"
+                             % (who, "logp" if is_logp else "p", B, T, list(shp), list(val.shape)))
+        k = int(shp[2])
+        if not 1 <= k <= 16:
+            raise ValueError("%s: soft_targets carry k = %d slots per position, outside 1 .. 16" % (who, k))
+        if not isinstance(ids, torch.Tensor):
+            ids = np.asarray(ids)
+            if ids.dtype.kind not in "iu":
+                raise ValueError("%s: the soft targets' ids must be integers, got %s" % (who, ids.dtype))
+            ids = np.ascontiguousarray(np.clip(ids, -1, np.iinfo(np.int32).max), dtype=np.int32)
+        if not isinstance(val, torch.Tensor):
+            val = np.asarray(val)
+            if val.dtype.kind not in "fiu":
+                raise ValueError("%s: the soft targets' %s must be real numbers, got %s" % (who, "logp" if is_logp else "p", val.dtype))
+            val = np.ascontiguousarray(val, dtype=np.float32)
+            if not isinstance(ids, torch.Tensor):
+                cnt = (ids >= 0) & (ids < self.n_tok)
+                if lengths is not None and not isinstance(lengths, torch.Tensor):
+                    cnt &= (np.arange(T)[None, :] < np.asarray(lengths).reshape(-1)[:B, None])[:, :, None]
+                with np.errstate(over="ignore", invalid="ignore"):
+                    m = np.where(cnt, np.exp(val.astype(np.float64)) if is_logp else val.astype(np.float64), 0.0)
+                if not np.isfinite(m).all() or (m < 0.0).any():
+                    raise ValueError("%s: soft_targets hold a mass that is negative, NaN or infinite" % who)
+                tot = m.sum(axis=2)
+                if tot.size and tot.max() > 1.0 + 1e-3:
+                    b, t = np.unravel_index(int(tot.argmax()), tot.shape)
+                    raise ValueError("%s: the counted masses of position (%d, %d) add up to %.6f, above 1 + 1e-3" % (who, b, t, float(tot[b, t])))
+        ids = self._to_dev(ids, torch.int32).contiguous()
+        val = self._to_dev(val, torch.float32).contiguous()
+        return _SoftDev(ids, torch.exp(val) if is_logp else val, k, lam)
+
+    def _soft_padded(self, soft, dead):
+        """slot rows of id -1 (mass 0) appended for the dead rows forward() added, as _weights_dev appends weights of 0"""
+        if dead <= 0:
+            return soft
+        tail = (dead,) + tuple(soft.ids.shape[1:])
+        return soft._replace(ids=torch.cat([soft.ids, torch.full(tail, -1, dtype=torch.int32, device=soft.ids.device)]),
+                             p=torch.cat([soft.p, torch.zeros(tail, dtype=torch.float32, device=soft.p.device)]))
+
     def loss(self, lengths, inv_ntok=None, ntok_dev=None, ntok_event=None, weights=None, row_weights=None, _padded=False, label_smoothing=0.0,
-             _bound=False):
+             _bound=False, soft_targets=None, soft_weight=0.5):
         """Loss statistics + d(logits).  Either inv_ntok (host float) or ntok_dev (device float32 [1] = the global token count,
         e.g. from DataParallel.sum_count_async; the compute stream waits for ntok_event, the host does not).
         weights [B, T] / row_weights [B] (host arrays or device tensors, either or both): the weighted loss lxo_ce_loss_weighted -- token (b, t)
@@ -464,8 +528,17 @@ class Engine(object):
         statistics are the four {sum w CE, token count, sum w, sum CE}.  Without weights: {sum CE, token count}, as ever.
         label_smoothing = eps in (0, 1): the smoothed loss lxo_ce_loss_smoothed -- a live row's target is (1 - eps) one-hot + eps / V over the
         vocabulary, its loss L = (1 - eps) CE + eps (lse - mean logit) -- with or without weights; the statistics are then the four
-        {sum w L, token count, sum w, sum CE (plain)}.  0.0: the calls above, as without the argument.  Outside [0, 1): a ValueError before any launch."""
+        {sum w L, token count, sum w, sum CE (plain)}.  0.0: the calls above, as without the argument.  Outside [0, 1): a ValueError before any launch.
+        soft_targets (an Alternatives, or a pair (ids, p) of [B, T, k] host arrays or device tensors; _soft_dev) with soft_weight = lambda in [0, 1]:
+        the soft-target loss lxo_ce_loss_soft -- a live row's target is (1 - lambda) * (the smoothed target) + lambda * (the teacher's k masses on
+        their tokens, what they leave of 1 spread over the vocabulary); a position without a counting slot keeps the smoothed target.  It combines
+        with the weights, the normaliser and label_smoothing; the statistics are the four.  None: the calls above."""
         eps = self._check_smoothing("loss", label_smoothing)
+        soft = None
+        if soft_targets is not None:
+            live = int(getattr(self, "live_B", self.shape.B))
+            soft = self._soft_padded(self._soft_dev("loss", soft_targets, soft_weight, live, int(self.shape.T), lengths), int(self.shape.B) - live)
+            self._loss_soft = soft                                 # alive until the next call
         if _bound:
             lengths = None                                         # (train_step: forward() has bound these lengths already -- no second upload)
         if weights is None and row_weights is None:
@@ -488,6 +561,11 @@ class Engine(object):
             self._ntok_dev = ntok_dev          # keep alive until the kernel has been enqueued
             if ntok_dev.is_cuda:               # allocated on the count stream, read on this one: the allocator must not hand the
                 ntok_dev.record_stream(torch.cuda.current_stream(self.device))   # block to a later upload before this kernel ran
+        if soft is not None:
+            self._ck(self.lib.lxo_ce_loss_soft(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), ctypes.c_float(eps), ctypes.c_float(soft.lam),
+                                               soft.k, _p(soft.ids), _p(soft.p), _p(wt), _p(wr),
+                                               ctypes.c_float(0.0 if ntok_dev is not None else inv_ntok), _p(ntok_dev), self._stream()), "ce_loss_soft")
+            return self.region("loss")[:4]
         if eps > 0.0:
             self._ck(self.lib.lxo_ce_loss_smoothed(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), ctypes.c_float(eps), _p(wt), _p(wr),
                                                    ctypes.c_float(0.0 if ntok_dev is not None else inv_ntok), _p(ntok_dev), self._stream()),
@@ -641,7 +719,7 @@ class Engine(object):
         self.pack()
 
     def train_step(self, img, formula, lengths, lr, clip=-1.0, dist=None, sync_loss=True, dropout=1.0, dropout_seed=None,
-                   weights=None, row_weights=None, norm=None, label_smoothing=0.0):
+                   weights=None, row_weights=None, norm=None, label_smoothing=0.0, soft_targets=None, soft_weight=0.5):
         """One optimisation step of img2seq.py:_run_train's body.  Returns the batch loss
         (token mean over the global batch) or None when sync_loss is False.  dropout = config.dropout
         (keep probability, img2seq.py:166); masks are keyed by (dropout_seed or a per-engine step counter).
@@ -649,6 +727,8 @@ class Engine(object):
         (loss()); norm = None: the global token count, as without weights (data parallel: the device-side count); norm = a float: the caller's
         own normaliser, the GLOBAL one under dist.  Returns that weighted loss.
         label_smoothing in (0, 1): the step minimises the smoothed loss (loss()), weighted or not, and returns it; 0.0: the step without the argument.
+        soft_targets / soft_weight (loss(): a teacher's top-k per position and lambda): the step minimises the soft-target loss, with or without
+        weights and smoothing, and returns it; the checks of _soft_dev run before any launch.  None: the step without the argument.
         Either way a synchronised step leaves the PLAIN token-mean CE of the batch in self.last_ce (under dist: of the global batch), what a
         perplexity is made of."""
         eps = self._check_smoothing("train_step", label_smoothing)
@@ -660,6 +740,8 @@ class Engine(object):
         wkw = dict(weights=weights, row_weights=row_weights) if weighted else {}
         if eps > 0.0:
             wkw["label_smoothing"] = eps
+        if soft_targets is not None:
+            wkw["soft_targets"] = self._soft_dev("train_step", soft_targets, soft_weight, int(img.shape[0]), int(formula.shape[1]), lengths)
         drop = None
         if dropout is not None and 0.0 < float(dropout) < 1.0:
             self.drop_step = getattr(self, "drop_step", 0) + 1
@@ -1196,6 +1278,27 @@ class Engine(object):
                     self._chain_fallback("forward", err)
                     continue
             return out
+
+    def score_alternatives_dev(self, img, formula, lengths, k):
+        """score(alternatives=k)'s ids int32 [B, T, k] and log-probs f32 [B, T, k] as DEVICE tensors, for a consumer on the device (a student's
+        train_step(soft_targets=)): the same forward and lxo_score_alternatives, in pieces of at most 64 rows, but no copy to the host and so no look
+        at a later chain's error word -- a failed forward chain leaves NaN log-probs, and the loss made of them says so.  Positions
+        t >= lengths[b]: -1 / 0."""
+        k = int(k)
+        if not 1 <= k <= min(16, self.n_tok):
+            raise ValueError("score_alternatives_dev: k must lie in 1 .. min(16, V = %d), got %d" % (self.n_tok, k))
+        ids_all, logp_all = [], []
+        for i in range(0, int(img.shape[0]), 64):
+            ln = lengths[i:i + 64]
+            self.forward(img[i:i + 64], formula[i:i + 64], lengths=ln if isinstance(ln, torch.Tensor) else np.asarray(ln, dtype=np.int32).reshape(-1))
+            B, T, live = int(self.shape.B), int(self.shape.T), int(self.live_B)
+            ids = torch.empty(B, T, k, dtype=torch.int32, device=self.device)
+            logp = torch.empty(B, T, k, dtype=torch.float32, device=self.device)
+            self._ck(self.lib.lxo_score_alternatives(self.sref(), _p(self.ws), _p(self._formula), _p(self._lengths), k, None, 0, _p(ids), _p(logp),
+                                                     None, None, self._stream()), "score_alternatives")
+            ids_all.append(ids[:live])
+            logp_all.append(logp[:live])
+        return (ids_all[0], logp_all[0]) if len(ids_all) == 1 else (torch.cat(ids_all), torch.cat(logp_all))
 
     # --------------------------------------------------------------- decode --
     def _encode_only(self, img, beam):

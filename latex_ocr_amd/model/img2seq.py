@@ -45,7 +45,8 @@ class Img2SeqModel(BaseModel):
 
     def build_train(self, config):
         """Reference: model/img2seq.py:34-40.  The training config's optional "label_smoothing" key (a number in [0, 1), default 0.0) makes every
-        cross-entropy step minimise the smoothed loss (Engine.train_step(label_smoothing=)); it does not combine with the "mrt" key."""
+        cross-entropy step minimise the smoothed loss (Engine.train_step(label_smoothing=)); it does not combine with the "mrt" key.  The optional
+        "distill" key (_distill_config) makes every batch a distill_batch; it combines with "label_smoothing" and not with "mrt"."""
         from ..engine import Engine
         self._label_smoothing = Engine._check_smoothing("training config: \"label_smoothing\"", getattr(config, "label_smoothing", 0.0))
         if self._label_smoothing > 0.0 and getattr(config, "mrt", None) is not None:
@@ -54,13 +55,61 @@ class Img2SeqModel(BaseModel):
         mrt = getattr(config, "mrt", None)
         if mrt is not None:                                      # the cost of the minimum-risk step is refused here, not at the first batch
             self._check_cost("training config: \"mrt\": \"cost\"", mrt.get("cost", "edit") if isinstance(mrt, dict) else getattr(mrt, "cost", "edit"))
+        distill = self._distill_config(getattr(config, "distill", None), mrt)
         self.logger.info("Building model...")
         self._build_engine()
+        # the optional "distill": {"teacher": <model dir or list of dirs>, "k": 5, "weight": 0.5} key: the teacher(s) are restored once, here, with this
+        # model's vocabulary and model config, for inference only; every training batch is then one distill_batch (it combines with "label_smoothing")
+        self._distill = dict(distill, teacher=[self._load_teacher(d, i) for i, d in enumerate(distill["teacher"])]) if distill else None
         self._lr_method = config.lr_method.lower()
         self.engine.set_optimizer(self._lr_method)               # img2seq.py:95-109
         self._clip = getattr(config, "clip", -1)
         self.init_session()
         self.logger.info("- done.")
+
+    DISTILL_KEYS = ("teacher", "k", "weight")
+
+    def _distill_config(self, distill, mrt):
+        """The training config's "distill" key before anything is built -> {"teacher": [dirs], "k", "weight"} or None"""
+        if distill is None:
+            return None
+        if mrt is not None:
+            raise ValueError("training config: \"distill\" and \"mrt\" do not combine -- the minimum-risk step takes no soft targets; drop one of the two keys")
+        d = dict(distill) if isinstance(distill, dict) else {k: getattr(distill, k) for k in self.DISTILL_KEYS if hasattr(distill, k)}
+        unknown = sorted(set(d) - set(self.DISTILL_KEYS))
+        if unknown:
+            raise ValueError("training config: unknown key(s) %s under \"distill\" (known: %s)" % (unknown, list(self.DISTILL_KEYS)))
+        dirs = d.get("teacher")
+        dirs = [dirs] if isinstance(dirs, str) else list(dirs or [])
+        if not dirs or not all(isinstance(x, str) for x in dirs):
+            raise ValueError("training config: \"distill\": \"teacher\" must be a model directory or a list of them, got %r" % (d.get("teacher"),))
+        k, weight = d.get("k", 5), d.get("weight", 0.5)
+        if not (isinstance(k, int) and k >= 1 and k * len(dirs) <= 16):
+            raise ValueError("training config: \"distill\": k = %r with %d teacher(s): k must be >= 1 and k * teachers <= 16" % (k, len(dirs)))
+        if not (isinstance(weight, (int, float)) and 0.0 <= float(weight) <= 1.0):
+            raise ValueError("training config: \"distill\": \"weight\" must be a number in [0, 1], got %r" % (weight,))
+        return {"teacher": dirs, "k": k, "weight": float(weight)}
+
+    def _load_teacher(self, path, i):
+        """A teacher for distill_batch: this model's vocabulary and model config, the weights of the latest checkpoint of model directory `path`
+        (or of a weights directory / checkpoint file), built for inference.  A checkpoint made for another vocabulary or model config is refused."""
+        import os
+        t = Img2SeqModel(self._config, self._dir_output + "distill_teacher_%d/" % i, self._vocab, lib=getattr(self, "_lib", None))
+        t.build_pred()
+        w = os.path.join(path, "model_weights")
+        ckpt = w if os.path.isdir(w) else path
+        if os.path.isdir(ckpt):
+            found = self.latest_checkpoint(ckpt if ckpt.endswith("/") else ckpt + "/")
+            if found is None:
+                raise IOError("training config: \"distill\": no checkpoint in %s" % ckpt)
+            ckpt = found
+        z = self._open_checkpoint(ckpt)
+        for name, shp, _ in t.engine.specs:
+            if name in z and tuple(np.shape(z[name])) != tuple(shp):
+                raise ValueError("training config: \"distill\": teacher %s holds %s of shape %s, this model's is %s -- another vocabulary or model "
+                                 "config" % (path, name, list(np.shape(z[name])), list(shp)))
+        t.restore_session(ckpt)
+        return t
 
     def build_pred(self):
         """Reference: model/img2seq.py:42-46."""
@@ -123,7 +172,11 @@ class Img2SeqModel(BaseModel):
                     fd = self._get_feed_dict(img, formula=formula)
                     yield fd["img"], fd["formula"], fd["formula_length"]
             it = sync_feed()
+        distill = getattr(self, "_distill", None)
         for i, (img, formula, lengths) in enumerate(it):
+            if distill:
+                smooth = dict(smooth, soft_targets=self._teacher_targets(distill["teacher"], distill["k"], img, formula, lengths),
+                              soft_weight=distill["weight"])
             loss_eval = self.engine.train_step(img, formula, lengths, lr_schedule.lr, clip=self._clip, dist=self.dist,
                                                dropout=keep, **smooth)
             # the loss the step optimised; the perplexity of the PLAIN cross-entropy, smoothed or not: comparable between runs
@@ -447,6 +500,42 @@ class Img2SeqModel(BaseModel):
         tok = self._vocab.id_to_tok
         return [{"rank": int(alt.rank[b, t]), "entropy": float(alt.entropy[b, t]),
                  "alternatives": [(tok[int(i)], float(lp)) for i, lp in zip(alt.ids[b, t], alt.logp[b, t]) if i >= 0]} for t in range(n)]
+
+    def _teacher_targets(self, teachers, k, img, f, ln):
+        """The soft targets of a padded batch, on the device: every teacher's k best tokens per position (Engine.score_alternatives_dev) side by side
+        along the last axis, their probabilities divided by the number of teachers -- lxo_ce_loss_soft adds up the slots that name the same token,
+        so the target is the average of the teachers' sparse distributions -> (ids [B, T, k M], p [B, T, k M])"""
+        import torch
+        M = len(teachers)
+        if not (M >= 1 and int(k) >= 1 and int(k) * M <= 16):
+            raise ValueError("distill_batch: k = %r with %d teacher(s): k must be >= 1 and k * teachers <= 16" % (k, M))
+        for t in teachers:
+            if t.engine.n_tok != self.engine.n_tok:
+                raise ValueError("distill_batch: a teacher's vocabulary has %d tokens, this model's %d" % (t.engine.n_tok, self.engine.n_tok))
+        dev = self.engine.device
+        outs = [t.engine.score_alternatives_dev(img, f, ln, int(k)) for t in teachers]
+        ids = [o[0].to(dev) for o in outs]
+        p = [torch.exp(o[1].to(dev)) / float(M) if M > 1 else torch.exp(o[1].to(dev)) for o in outs]
+        return (ids[0], p[0]) if M == 1 else (torch.cat(ids, dim=2), torch.cat(p, dim=2))
+
+    def distill_batch(self, images, formulas, lr, teacher, k=5, weight=0.5, dropout=1):
+        """One training step against a teacher's soft targets (Engine.train_step(soft_targets=, soft_weight=weight)): teacher is an Img2SeqModel or a
+        list of M of them, k * M <= 16, with this model's vocabulary size.  Each teacher scores the same padded batch teacher-forced and hands over
+        its k best tokens per position with their probabilities; what they leave of 1 is spread over the vocabulary, several teachers are averaged,
+        and the step minimises (1 - weight) * (the cross-entropy, smoothed if the training config says so) + weight * (the cross-entropy against the
+        teachers' distribution).  The targets never visit the host.  formulas: token-id lists or space-separated token strings, as score_batch takes
+        them.  -> the loss the step optimised (Engine.last_ce keeps the plain cross-entropy)."""
+        if len(images) != len(formulas):
+            raise ValueError("distill_batch: %d images but %d formulas" % (len(images), len(formulas)))
+        teachers = list(teacher) if isinstance(teacher, (list, tuple)) else [teacher]
+        prepro = self._vocab.form_prepro
+        forms = [prepro(f) if isinstance(f, str) else [int(x) for x in f] for f in formulas]
+        fd = self._get_feed_dict(images, formula=forms, dropout=dropout)
+        img, f, ln = fd["img"], fd["formula"], fd["formula_length"]
+        eps = getattr(self, "_label_smoothing", 0.0)
+        return self.engine.train_step(img, f, ln, lr, clip=getattr(self, "_clip", -1), dist=self.dist, dropout=dropout,
+                                      soft_targets=self._teacher_targets(teachers, k, img, f, ln), soft_weight=weight,
+                                      **(dict(label_smoothing=eps) if eps > 0.0 else {}))
 
     def score_batch(self, images, formulas, alternatives=0, banned=None, allowed=None):
         """Teacher-forced scores of given transcriptions (Engine.score): formulas are token-id lists or space-separated token strings
