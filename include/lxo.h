@@ -397,6 +397,45 @@ int lxo_edit_align(const int32_t* hyp, int hyp_block, long long hyp_block_stride
                    const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of, int per_ref,
                    int pairs, int id_end, int32_t* hyp_align, int32_t* ref_align, int32_t* counts_out, long long* corpus_io, long long* confusion_io,
                    int V, int accumulate, void* scratch, size_t scratch_bytes, void* stream);
+/* WHERE IN THE IMAGE a token is, on the device, shape-free: every attention map reduced to its arg-max cell, a box in feature cells, its moments and
+ * entropy, and a row's maps added up over its steps (the coverage).  The maps are read where they lie and never visit the host.
+ * ADDRESSING: alpha is device f32; position (i, t), i < rows, t < steps, reads the Hp x Wp map (row-major, R = Hp * Wp cells a[y * Wp + x]) that
+ * starts at element t * step_stride + r * row_stride, with r = src[t * rows + i] (device int32 [steps][rows]; NULL: r = i).  Workspace region "alpha"
+ * [T][B][Rp] is read with step_stride B * Rp and row_stride Rp, the alpha_out [max_steps][rows][Rp] of a decode likewise, rows [rows][steps][R] with
+ * step_stride R and row_stride steps * R; whatever lies behind a map's R cells is never read.  src is for beam search, where the token of hypothesis
+ * i at step t was read off its parent's row.
+ * A position has NO MAP when t >= len[i] (device int32 [rows]; NULL: never), when r lies outside [0, alpha_rows), or when the map's f32 sum is not a
+ * positive finite number (all zero, a NaN or an infinity in it).  Every output of such a position is its NONE value below.  Cells are weights: a map
+ * with negative cells has unspecified (in-bounds) outputs.
+ * THE DEFINITION for a map a with S = sum a:
+ *   peak_out int32 [rows][steps]: the arg-max cell index, the lower index on ties -- a comparison of f32 values, bit-defined.  NONE: -1.
+ *   box_out int32 [rows][steps][4] = (x0, y0, x1, y1), inclusive, in feature cells: the central-mass interval of each marginal.  With
+ *     px(x) = sum_y a[y * Wp + x], Cx its running sum and tail = (0.5 * (1 - mass)) * S:  x0 = min{x : Cx(x) > tail}, x1 = min{x : Cx(x) >= S - tail};
+ *     y0, y1 the same from py(y) = sum_x a[y * Wp + x].  mass = 1 gives the bounding box of the support, a one-cell map gives that cell.
+ *     x0 <= x1 ALWAYS: Cx is non-decreasing, and mass > 0 gives tail < S / 2 < S - tail, so Cx(x1) >= S - tail > tail and the first x whose Cx exceeds
+ *     tail is no later than x1.  (Where 1 - mass rounds to 1 the two thresholds meet; the kernel then takes x1 = max(x0, x1).)
+ *     WHAT THE BOX HOLDS: each marginal leaves at most tail on either side, so the box holds at least 2 * mass - 1 of S -- a union bound over
+ *     the two axes, not mass itself (a diagonal map shows the difference).
+ *     The kernel forms the cumulative sums in exact integer arithmetic on cells truncated to 2^-40 of S's binade, so they are exactly monotone and the
+ *     same in any order; on maps whose cells are multiples of 2^-12 with S <= 2 the edges are those of exact arithmetic, elsewhere they can differ
+ *     from it only where a cumulative sum lies within the cells' own f32 rounding of a threshold.  NONE: -1 four times.
+ *   stats_out f32 [rows][steps][LXO_LOCATE_STATS]: [0] S (f32 sum);  [1] cx = sum x px(x) / S, [2] cy likewise;  [3] sx = sqrt(sum px(x) (x - cx)^2 / S),
+ *     [4] sy likewise -- the CENTRED second moment, no cancellation;  [5] the entropy -sum (a/S) ln(a/S) in nats (0 ln 0 = 0);  [6] inside = the share
+ *     of S within the box;  [7] peak_share = a[peak] / S.  f32 sums in a fixed order.  NONE: eight zeros.
+ *   coverage_out f32 [rows][cov_ld], cov_ld >= R: cell r < R of row i = sum over t of a_t[r] over the row's positions that have a map, ADDED IN
+ *     ASCENDING t into one f32 accumulator from 0.f -- bit-reproducible, restatable exactly in np.float32.  Cells [R, cov_ld) are not written.
+ * Each output is nullable, not all four.  One launch of one wave per position (the map staged once in LDS; both marginals, the box and the inside
+ * pass come from that one read) and a second small launch for the coverage; no atomics, no host synchronisation, capturable into a graph, the same
+ * bytes in every run.  rows == 0 or steps == 0 launches nothing per position; the coverage of a row without steps is zeros.
+ * Refusals, with the reason in lxo_last_error, nothing written and nothing launched:
+ * -1: a NULL alpha; all four outputs NULL; mass outside (0, 1] or not finite; a stride, alpha_rows, rows or steps negative; coverage_out with cov_ld < R.
+ * -5: Hp or Wp < 1; R above LXO_LOCATE_MAX_CELLS, the kernel's staging limit (98 x 98 = 9604, the map of an 800 x 800 input, fits); more positions
+ * than a grid holds (rows * steps > 2^31 - 5). */
+#define LXO_LOCATE_STATS     8      /* f32 per position */
+#define LXO_LOCATE_MAX_CELLS 9728
+int lxo_attention_locate(const float* alpha, long long step_stride, long long row_stride, int alpha_rows, int Hp, int Wp, int rows, int steps,
+                         const int32_t* len, const int32_t* src, float mass, int32_t* peak_out, int32_t* box_out, float* stats_out,
+                         float* coverage_out, int cov_ld, void* stream);
 /* The candidate rows of a minimum-risk step, built on the device from a sampled decode: three launches, no host synchronisation.
  * ids int32 [B, max_steps, n] as lxo_sample_decode leaves them and steps = the steps it ran (0 <= steps <= max_steps, 1 <= n <= 16);
  * ref int32 [B, Tr] with ref_len [B] in pad_batch_formulas' layout (tokens, END, PAD; length = tokens + 1), 1 <= Tr <= LXO_EDIT_MAX_REF.

@@ -174,6 +174,7 @@ extern "C" int lxo_mrt_weights(const float* seq_logp, const float* cost, const i
     return 0;
 }
 #include "seqcost.h"
+#include "attloc.h"
 static_assert(LXO_EDIT_MAX_REF == kEditMaxRef, "include/lxo.h and csrc/seqcost.h disagree on the reference limit");
 extern "C" int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
                                  const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of,
@@ -225,6 +226,23 @@ extern "C" int lxo_edit_align(const int32_t* hyp, int hyp_block, long long hyp_b
     const AlignArgs a = {hyp, hyp_len, ref, ref_len, ref_of, hyp_align, ref_align, counts_out, corpus_io, confusion_io, static_cast<unsigned*>(scratch),
                          hyp_block_stride, hyp_row_stride, hyp_tok_stride, hyp_block, T, G, ref_ld, per_ref, pairs, id_end, confusion_io ? V : 1, accumulate};
     CHECK_LAUNCH(lxo_k_edit_align(a, (hipStream_t)stream), "lxo_edit_align");
+    return 0;
+}
+static_assert(LXO_LOCATE_STATS == kLocateStats && LXO_LOCATE_MAX_CELLS == kLocateMaxCells, "include/lxo.h and csrc/attloc.h disagree on the location rows");
+extern "C" int lxo_attention_locate(const float* alpha, long long step_stride, long long row_stride, int alpha_rows, int Hp, int Wp, int rows, int steps,
+                                    const int32_t* len, const int32_t* src, float mass, int32_t* peak_out, int32_t* box_out, float* stats_out,
+                                    float* coverage_out, int cov_ld, void* stream) {
+    if (!alpha) return fail(-1, "lxo_attention_locate: null alpha");
+    if (!peak_out && !box_out && !stats_out && !coverage_out) return fail(-1, "lxo_attention_locate: the four outputs are all NULL");
+    if (!(mass > 0.f && mass <= 1.f)) return fail(-1, "lxo_attention_locate: mass outside (0, 1]");
+    if (step_stride < 0 || row_stride < 0 || alpha_rows < 0 || rows < 0 || steps < 0) return fail(-1, "lxo_attention_locate: a negative count or stride");
+    if (Hp < 1 || Wp < 1) return fail(-5, "lxo_attention_locate: Hp or Wp < 1");
+    if ((long long)Hp * Wp > LXO_LOCATE_MAX_CELLS) return fail(-5, "lxo_attention_locate: Hp * Wp above LXO_LOCATE_MAX_CELLS (a map larger than the kernel's staging limit)");
+    if (coverage_out && cov_ld < Hp * Wp) return fail(-1, "lxo_attention_locate: cov_ld < Hp * Wp");
+    if ((long long)rows * steps > 0x7fffffffll - 4 || (long long)rows * ((Hp * Wp + 255) / 256) > 0x7fffffffll)
+        return fail(-5, "lxo_attention_locate: more positions than a grid holds");
+    const LocateArgs a = {alpha, len, src, peak_out, box_out, stats_out, coverage_out, step_stride, row_stride, alpha_rows, Hp, Wp, rows, steps, cov_ld, mass};
+    CHECK_LAUNCH(lxo_k_attention_locate(a, (hipStream_t)stream), "lxo_attention_locate");
     return 0;
 }
 static_assert(LXO_BLEU_COUNTS == kBleuCounts, "include/lxo.h and csrc/seqcost.h disagree on the sentence-BLEU counts");

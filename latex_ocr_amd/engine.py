@@ -21,6 +21,7 @@ from .model import params as PP
 Alternatives = namedtuple("Alternatives", ["ids", "logp", "rank", "entropy"])
 _SoftDev = namedtuple("_SoftDev", ["ids", "p", "k", "lam"])          # soft targets behind their checks: device int32 / f32 [B, T, k], lambda
 Alignment = namedtuple("Alignment", ["hyp_align", "ref_align", "counts", "corpus", "confusion"])
+Locations = namedtuple("Locations", ["peak", "box", "stats", "coverage"])        # Engine.attention_locate
 
 
 def _p(t):
@@ -1124,6 +1125,61 @@ class Engine(object):
                                          self._stream()), what)
         return ha, ra, counts, corpus, confusion
 
+    def attention_locate(self, alpha, lengths=None, src=None, mass=0.9, coverage=False):
+        """WHERE in the image each token is (lxo_attention_locate; include/lxo.h holds the definition): every attention map reduced on the device
+        to its arg-max cell, the central-mass box of its marginals and eight statistics.  alpha: the maps [rows, steps, H', W'] f32, a host array
+        or a device tensor -- a strided view (a decode's [max_steps, rows, Rp] buffer permuted, a slice) is read in place as long as each map's
+        H' W' cells are contiguous.  lengths [rows] (None: every step): positions t >= lengths[i] have no map.  src int32 [steps, rows2] (None:
+        row i reads its own maps): position (i, t) reads alpha[src[t, i], t]; an index outside [0, rows) gives no map.  mass in (0, 1]: the box
+        leaves (1 - mass) / 2 of each marginal outside on either side.
+        -> Locations(peak int32 [rows, steps] (-1: no map), box int32 [rows, steps, 4] = x0, y0, x1, y1 inclusive in feature cells (-1),
+        stats f32 [rows, steps, 8] = S, cx, cy, sx, sy, entropy, inside, peak_share (0), coverage f32 [rows, H', W'] = the row's maps added
+        in ascending step (None without coverage=True)), host arrays.  attention_locate_dev leaves them on the device."""
+        return Locations(*[None if a is None else a.cpu().numpy() for a in self.attention_locate_dev(alpha, lengths, src, mass, coverage)])
+
+    def attention_locate_dev(self, alpha, lengths=None, src=None, mass=0.9, coverage=False):
+        """attention_locate with its outputs left on the device"""
+        a = alpha.to(self.device) if isinstance(alpha, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(alpha, dtype=np.float32)).to(self.device)
+        if a.dim() != 4 or a.dtype != torch.float32:
+            raise ValueError("attention_locate: alpha must be f32 [rows, steps, H', W'], got %s %s" % (a.dtype, tuple(a.shape)))
+        AR, steps, Hp, Wp = (int(v) for v in a.shape)
+        if Hp < 1 or Wp < 1 or Hp * Wp > _abi.LXO_LOCATE_MAX_CELLS:
+            raise ValueError("attention_locate: a map of %d x %d cells; 1 .. %d cells are taken" % (Hp, Wp, _abi.LXO_LOCATE_MAX_CELLS))
+        if (Wp > 1 and a.stride(3) != 1) or (Hp > 1 and a.stride(2) != Wp):
+            a = a.contiguous()                                     # a map's cells must lie together; rows and steps may be strided
+        rows = AR
+        if src is not None:
+            src = self._to_dev(src, torch.int32)
+            if src.dim() != 2 or int(src.shape[0]) != steps:
+                raise ValueError("attention_locate: src must be int32 [steps = %d, rows], got %s" % (steps, tuple(src.shape)))
+            src, rows = src.contiguous(), int(src.shape[1])
+        if lengths is not None:
+            lengths = self._to_dev(lengths, torch.int32).reshape(-1).contiguous()
+            if int(lengths.shape[0]) != rows:
+                raise ValueError("attention_locate: lengths must be [rows = %d], got %s" % (rows, tuple(lengths.shape)))
+        return self._locate(a, a.stride(1) if steps > 1 else 0, a.stride(0) if AR > 1 else 0, AR, Hp, Wp, rows, steps, lengths, src, mass, coverage)
+
+    def _locate(self, alpha, step_stride, row_stride, alpha_rows, Hp, Wp, rows, steps, len_dev, src_dev, mass, coverage):
+        """The lxo_attention_locate call on maps where they lie (strides in floats): -> Locations of device tensors"""
+        mass = float(mass)
+        if not 0.0 < mass <= 1.0:
+            raise ValueError("mass must lie in (0, 1], got %r" % mass)
+        peak = torch.empty(rows, steps, dtype=torch.int32, device=self.device)
+        box = torch.empty(rows, steps, 4, dtype=torch.int32, device=self.device)
+        stats = torch.empty(rows, steps, _abi.LXO_LOCATE_STATS, dtype=torch.float32, device=self.device)
+        cov = torch.empty(rows, Hp, Wp, dtype=torch.float32, device=self.device) if coverage else None
+        self._ck(self.lib.lxo_attention_locate(_p(alpha), int(step_stride), int(row_stride), int(alpha_rows), Hp, Wp, rows, steps, _p(len_dev), _p(src_dev),
+                                               mass, _p(peak), _p(box), _p(stats), _p(cov), Hp * Wp, self._stream()), "attention_locate")
+        return Locations(peak, box, stats, cov)
+
+    def _end_lengths(self, ids, id_end):
+        """ids [rows, steps] (device) -> int32 [rows]: the steps through each row's first id_end, all of them without one"""
+        if int(ids.shape[1]) == 0:
+            return torch.zeros(int(ids.shape[0]), dtype=torch.int32, device=self.device)
+        hit = ids == int(id_end)
+        first = hit.to(torch.int32).argmax(1).to(torch.int32) + 1
+        return torch.where(hit.any(1), first, torch.full_like(first, int(ids.shape[1]))).contiguous()
+
     def sentence_bleu(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None, return_counts=False):
         """Sentence-level BLEU-4 per pair on the device (lxo_sentence_bleu; include/lxo.h holds the definition: add-one smoothing on the orders
         2 .. 4, 1 exactly for an equal pair, 0 without a common unigram): -> f32 [pairs], and with return_counts also int32 [pairs, 10] = the
@@ -1200,7 +1256,7 @@ class Engine(object):
         s = self.loss(lengths, 1.0 / max(n, 1)).cpu().numpy()
         return float(s[0]), n
 
-    def score(self, img, formula, lengths, return_top1=False, alternatives=0, allowed=None):
+    def score(self, img, formula, lengths, return_top1=False, alternatives=0, allowed=None, locate=False, mass=0.9, coverage=False, return_attention=False):
         """Teacher-forced scoring of given formulas (lxo_score_tokens): -> (logp f32 [B, T], seq f32 [B]) or (logp, top1 int32 [B, T], seq),
         host arrays.  logp[b, t] = log_softmax(logits of step t)[formula[b, t]] for t < lengths[b], 0 after; top1[b, t] = the model's
         arg-max at step t (lower id on ties, the greedy rule), -1 after; seq[b] = the f32 sum of logp[b, :lengths[b]] in ascending t
@@ -1212,7 +1268,15 @@ class Engine(object):
         id on ties) with their log-probs, the rank of the given token (0 = the model's top-1) and the entropy of the step in nats; positions
         t >= lengths[b]: -1 / 0 / -1 / 0.  allowed (with alternatives only): a boolean / 0-1 array [V] or [B, V] as the decode calls take it;
         the alternatives then run over each row's allowed tokens (renormalised log-probs, rank -1 for a banned given token, id -1 / logp -inf
-        where fewer than k are allowed) while logp / top1 / seq stay the unconstrained values."""
+        where fewer than k are allowed) while logp / top1 / seq stay the unconstrained values.
+        locate=True: the tuple gains the Locations (attention_locate) of the given formula -- peak [B, T], box [B, T, 4], stats [B, T, 8] and, with
+        coverage=True, coverage [B, H', W'] -- computed from workspace region `alpha` of each piece's forward before anything is copied: the maps
+        themselves stay on the device.  Positions t >= lengths[b] have no map (-1 / -1 / 0).  mass: the box's central mass, in (0, 1].
+        return_attention=True: the maps themselves, f32 [B, T, H', W'], as the last element (what lies at t >= lengths[b] means nothing)."""
+        if locate and not 0.0 < float(mass) <= 1.0:
+            raise ValueError("score: mass must lie in (0, 1], got %r" % (mass,))
+        if coverage and not locate:
+            raise ValueError("score: coverage=True needs locate=True")
         f = formula.detach().cpu().numpy() if isinstance(formula, torch.Tensor) else np.asarray(formula)
         ln = lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
         f = np.ascontiguousarray(f, dtype=np.int64)
@@ -1231,15 +1295,21 @@ class Engine(object):
         if k != 0 and not 1 <= k <= min(16, self.n_tok):
             raise ValueError("score: alternatives must lie in 1 .. min(16, V = %d), got %d" % (self.n_tok, k))
         al = self._allow_host(allowed, B, None, 1) if allowed is not None else None
+        loc = (float(mass), bool(coverage)) if locate else None
         parts = [self._score_piece(img[i:i + 64], f[i:i + 64], ln[i:i + 64], return_top1, k,
-                                   al if al is None or al.shape[0] == 1 else al[i:i + 64]) for i in range(0, B, 64)]
+                                   al if al is None or al.shape[0] == 1 else al[i:i + 64], loc, return_attention) for i in range(0, B, 64)]
         logp, seq = np.concatenate([p[0] for p in parts]), np.concatenate([p[2] for p in parts])
         out = (logp, np.concatenate([p[1] for p in parts]), seq) if return_top1 else (logp, seq)
         if k:
             out += (Alternatives(*[np.concatenate([p[3][j] for p in parts]) for j in range(4)]),)
+        if locate:
+            out += (Locations(*[None if parts[0][4][j] is None else np.concatenate([p[4][j] for p in parts]) for j in range(4)]),)
+        if return_attention:
+            out += (np.concatenate([p[5] for p in parts]),)
         return out
 
-    def _score_piece(self, img, formula, lengths, top1_on, k=0, al=None):
+    def _score_piece(self, img, formula, lengths, top1_on, k=0, al=None, loc=None, want_maps=False):
+        """-> (logp, top1 or None, seq, the four alternatives arrays or None, the Locations' four host arrays or None, the maps or None)"""
         while True:
             self.forward(img, formula, lengths=np.asarray(lengths, dtype=np.int32).reshape(-1))      # (scoring reads t < lengths[b] only)
             B, T = int(self.shape.B), int(self.shape.T)
@@ -1260,6 +1330,17 @@ class Engine(object):
                                                          _p(buf[na:na + n * k]), _p(buf[na + n * k:na + 2 * n * k].view(torch.float32)),
                                                          _p(buf[na + 2 * n * k:na + 2 * n * k + n]), _p(buf[na + 2 * n * k + n:ns].view(torch.float32)),
                                                          self._stream()), "score_alternatives")
+            where = maps = None
+            if loc is not None or want_maps:
+                # region `alpha` [T][B][Rp] read where it lies; the dead fill-up rows lie behind the live ones and are simply not asked for
+                from .model.utils.image import encoder_out_hw
+                Hp, Wp = encoder_out_hw(int(img.shape[1]), int(img.shape[2]))
+                Rp = (Hp * Wp + 7) // 8 * 8
+                alpha = self.region("alpha", "f32", (T, B, Rp))
+                if loc is not None:
+                    where = self._locate(alpha, B * Rp, Rp, B, Hp, Wp, live, T, ln_dev, None, loc[0], loc[1])
+                if want_maps:
+                    maps = alpha[:, :live, :Hp * Wp].permute(1, 0, 2).reshape(live, T, Hp, Wp)
             if chain:
                 buf[ns:].copy_(self.region("xdec_sync", "i32")[:XDEC_STATUS_WORDS])
             h = buf.cpu().numpy()
@@ -1269,6 +1350,9 @@ class Engine(object):
                 a = h[na:ns]
                 out += ((a[:n * k].reshape(B, T, k)[:live].copy(), a[n * k:2 * n * k].view(np.float32).reshape(B, T, k)[:live].copy(),
                          a[2 * n * k:2 * n * k + n].reshape(B, T)[:live].copy(), a[2 * n * k + n:].view(np.float32).reshape(B, T)[:live].copy()),)
+            else:
+                out += (None,)
+            out += (None if where is None else tuple(None if a is None else a.cpu().numpy() for a in where), None if maps is None else maps.cpu().numpy())
             if chain:
                 # a chain that did not assemble (forward() checks the first one itself): the launch-per-step kernels from now on, and
                 # this piece again
@@ -1494,7 +1578,7 @@ class Engine(object):
         return L.lxo_greedy_decode, "greedy_decode", (_p(ids),)
 
     def greedy_decode(self, img, id_end, max_iter=151, return_attention=False, return_scores=False, prefix=None, prefix_lengths=None, allowed=None,
-                      grammar=None, return_depth=False):
+                      grammar=None, return_depth=False, return_boxes=False, mass=0.9, coverage=False):
         """ids int32 [B, T'] as pred_test.ids of the greedy graph (decoder.py:64,70).  With return_attention also the
         attention maps alpha f32 [B, T', H', W'] (what the reference collects through its py_func hook,
         attention_mechanism.py:96-105, for visualize_attention.py).
@@ -1516,12 +1600,19 @@ class Engine(object):
         everything by max_iter -- so every row ends balanced.  Combines with the other arguments; runs the launch-per-step kernels (the
         persistent chain holds no grammar).  return_depth (with grammar): one more output, last: depth int32 [B, T'], the row's open
         delimiters after each step.  A ValueError before any launch for a grammar of another vocabulary size, END not plain, a closer that
-        `allowed` bans, a prefix that breaks the grammar."""
+        `allowed` bans, a prefix that breaks the grammar.
+        return_boxes: one more output, last: the Locations (attention_locate: peak [B, T'], box [B, T', 4], stats [B, T', 8], with coverage=True
+        coverage [B, H', W']) of every emitted token, reduced on the device from the alpha_out buffer; a row's steps behind its first END have no
+        map.  Like return_attention this selects the launch-per-step path (the persistent chain exports no maps); the maps are copied to the host
+        only with return_attention."""
         if return_depth and grammar is None:
             raise ValueError("return_depth needs grammar=")
+        if return_boxes and not 0.0 < float(mass) <= 1.0:
+            raise ValueError("mass must lie in (0, 1], got %r" % (mass,))
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
+        want_maps, return_attention = return_attention, return_attention or return_boxes
         Bp = B0 if return_attention or grammar is not None else self._decode_chain_batch(B0)
         al = self._allow_host(allowed, B0, id_end, 1) if allowed is not None else None
         pfx = self._prefix_args(prefix, prefix_lengths, B0, Bp, id_end, max_iter, al) if prefix is not None else None
@@ -1537,13 +1628,17 @@ class Engine(object):
         gram = self._grammar_args(g, B, ids) if g is not None else None
         n = self._run_decode(self._greedy_entry(pfx, ids, logp, alpha, alw, gram), id_end, max_iter)
         out = [ids[:B0, :n]]
-        if return_attention:
+        if want_maps:
             out.append(alpha[:n, :B0, :R].permute(1, 0, 2).reshape(B0, n, Hp, Wp))
         if return_scores:
             out.append(logp[:B0, :n])
         if return_depth:
             out.append(gram[1][:B0, :n])
+        if return_boxes:
+            where = self._locate(alpha, B * alpha.shape[2], alpha.shape[2], B, Hp, Wp, B0, n, self._end_lengths(ids[:B0, :n], id_end), None, mass, coverage)
         out = tuple(a.cpu().numpy() for a in out)
+        if return_boxes:
+            out += (Locations(*[None if a is None else a.cpu().numpy() for a in where]),)
         return out if len(out) > 1 else out[0]
 
     def _check_beam(self, beam_size):
@@ -1643,7 +1738,8 @@ class Engine(object):
         return L.lxo_beam_decode, "beam_decode", (_p(ids), _p(par))
 
     def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False,
-                    return_scores=False, prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False):
+                    return_scores=False, prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False, return_boxes=False, mass=0.9,
+                    coverage=False):
         """ids int32 [B, T', k] as pred_test.ids of the beam graph before the transpose at img2seq.py:241.
         div_gamma / div_prob: add_div_penalty of beam_search_decoder_cell.py:258-287 (off at 1 / 0, the shipped values).
         return_attention: -> (ids, parents, alpha f32 [B, T', k, H', W']): alpha[b, t, j] = the map decoder row j of image b attended with at
@@ -1656,10 +1752,18 @@ class Engine(object):
         never selected, the diversity penalty ranks among the allowed columns.  Every row must allow at least beam_size tokens.
         grammar / return_depth: as in greedy_decode (lxo_beam_decode_grammar), one state per hypothesis slot, continued from the slot's parent:
         every back-traced hypothesis ends balanced.  depth int32 [B, T', k] (last output; the parents are returned with it).  The first free
-        step must leave at least beam_size tokens."""
+        step must leave at least beam_size tokens.
+        return_boxes: one more output, last (the parents are returned with it): the Locations of the BACK-TRACED hypotheses -- peak [B, k, T'],
+        box [B, k, T', 4], stats [B, k, T', 8], coverage [B, k, H', W'] with coverage=True; entry [b, i] belongs to the hypothesis that ends in
+        slot i (utils/text.beam_backtrace's out[b, :, i]).  Its token at step t was read off the row of its parent, so position (b k + i, t)
+        reads the map of row b k + parents[b, t, slots[b, t, i]] (beam_slots' rule); that src array is built ON THE HOST from the copied parents
+        and the reduction then runs on the device on the alpha_out buffer.  Steps behind a hypothesis' first END have no map."""
         self._check_beam(beam_size)
         if return_depth and grammar is None:
             raise ValueError("return_depth needs grammar=")
+        if return_boxes and not 0.0 < float(mass) <= 1.0:
+            raise ValueError("mass must lie in (0, 1], got %r" % (mass,))
+        want_maps, return_attention = return_attention, return_attention or return_boxes
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
@@ -1678,13 +1782,22 @@ class Engine(object):
         out = [ids[:, :n]]
         if return_parents or return_attention or return_scores or return_depth:
             out.append(par[:, :n])
-        if return_attention:
+        if want_maps:
             out.append(alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
         if return_scores:
             out.append(sc[:, :n])
         if return_depth:
             out.append(gram[1][:, :n])
         out = tuple(a.cpu().numpy() for a in out)
+        if return_boxes:
+            from .model.utils.text import beam_backtrace, beam_parent_rows
+            k = int(beam_size)
+            hyp, src = beam_backtrace(out[0], out[1]), beam_parent_rows(out[1])          # [B, n, k] both
+            hit = hyp == int(id_end)
+            ln = np.where(hit.any(1), hit.argmax(1) + 1, n).astype(np.int32)             # [B, k]
+            where = self._locate(alpha, B * k * alpha.shape[2], alpha.shape[2], B * k, Hp, Wp, B * k, n, self._to_dev(ln.reshape(-1), torch.int32),
+                                 self._to_dev(np.ascontiguousarray(src.transpose(1, 0, 2).reshape(n, B * k)), torch.int32), mass, coverage)
+            out += (Locations(*[None if a is None else a.cpu().numpy().reshape((B, k) + tuple(a.shape[1:])) for a in where]),)
         return out if len(out) > 1 else out[0]
 
     def _sample_opts(self, n, temperature, top_k, top_p, seed):
@@ -1708,7 +1821,8 @@ class Engine(object):
         return _abi.LxoSampleOpts(temperature, top_k, top_p, int(seed) & 0xFFFFFFFF)
 
     def sample_decode(self, img, id_end, n=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, max_iter=151, return_scores=False, return_attention=False,
-                      prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False, return_consensus=False, consensus_normalize=True, consensus_cost="edit"):
+                      prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False, return_consensus=False, consensus_normalize=True, consensus_cost="edit",
+                      return_boxes=False, mass=0.9, coverage=False):
         """n independent DRAWS of the whole sequence per image (lxo_sample_decode): ids int32 [B, T', n].  Every step draws from the model's
         distribution at `temperature`, cut to the top_k most likely tokens (0: off) and then to the smallest set of renormalised mass >= top_p
         (1: off); temperature = 0 means top_k = 1, the arg-max.  Draw (b, j) depends only on seed, b, j and the step: the same seed repeats bit for
@@ -1722,9 +1836,14 @@ class Engine(object):
         step's effective set, so every draw ends balanced.  depth int32 [B, T', n] (last output).
         return_consensus: the minimum-risk choice among each image's draws (consensus(), uniform weights, consensus_normalize its normalize),
         computed on the ids where the decode left them on the device: best int32 [B] and risk f32 [B, n] are appended as the last two outputs.
-        consensus_cost: consensus()'s cost, "edit" or "bleu" (with "bleu" consensus_normalize must be left at its default)."""
+        consensus_cost: consensus()'s cost, "edit" or "bleu" (with "bleu" consensus_normalize must be left at its default).
+        return_boxes: the very last output: the Locations of every draw -- peak [B, n, T'], box [B, n, T', 4], stats [B, n, T', 8], coverage
+        [B, n, H', W'] with coverage=True -- reduced on the device from the alpha_out buffer; steps behind a draw's first END have no map."""
         if return_depth and grammar is None:
             raise ValueError("return_depth needs grammar=")
+        if return_boxes and not 0.0 < float(mass) <= 1.0:
+            raise ValueError("mass must lie in (0, 1], got %r" % (mass,))
+        want_maps, return_attention = return_attention, return_attention or return_boxes
         _cost_kind("sample_decode: consensus_cost", consensus_cost)
         if consensus_cost == "bleu" and consensus_normalize is not True:
             raise ValueError("sample_decode: consensus_cost = \"bleu\" has no normalisation; leave consensus_normalize at its default")
@@ -1735,7 +1854,7 @@ class Engine(object):
                                                                  prefix, prefix_lengths, allowed, grammar, box)
         B, n, R, Hp, Wp = geo
         out = [ids[:, :steps]]
-        if return_attention:
+        if want_maps:
             out.append(alpha[:steps, :, :R].reshape(steps, B, n, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
         if return_scores:
             out += [logp[:, :steps], logq[:, :steps]]
@@ -1743,7 +1862,12 @@ class Engine(object):
             out.append(box[0][:, :steps])
         if return_consensus:
             out += self._consensus_device(ids[:, :steps], id_end, None, consensus_normalize, consensus_cost)[:2]
+        if return_boxes:
+            ln = self._end_lengths(ids[:, :steps].permute(0, 2, 1).reshape(B * n, steps), id_end)
+            where = self._locate(alpha, B * n * alpha.shape[2], alpha.shape[2], B * n, Hp, Wp, B * n, steps, ln, None, mass, coverage)
         out = tuple(a.cpu().numpy() for a in out)
+        if return_boxes:
+            out += (Locations(*[None if a is None else a.cpu().numpy().reshape((B, n) + tuple(a.shape[1:])) for a in where]),)
         return out if len(out) > 1 else out[0]
 
     def _sample_device(self, img, id_end, n, temperature, top_k, top_p, seed, max_iter, return_scores=False, return_attention=False,

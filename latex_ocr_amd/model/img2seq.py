@@ -667,6 +667,54 @@ class Img2SeqModel(BaseModel):
                 out[-1].update(consensus=k, expected_cost=hyps[k]["risk"])
         return out
 
+    def locate_batch(self, images, formulas=None, mass=0.9):
+        """WHERE in its image each token is (Engine.attention_locate, reduced on the device: the attention maps never visit the host).
+        formulas given (token-id lists or token strings, as score_batch takes them): teacher-forced, the given transcription's tokens with the
+        appended END (Engine.score(locate=True)).  Without: the tokens of what config.decoding decodes, through the first END -- greedy, or the
+        back-traced best beam hypothesis (Engine greedy_decode / beam_decode with return_boxes=True).
+        -> per image {"tokens": [{"token", "box": (left, top, right, bottom) in pixels of the network's input (the padded batch canvas), right
+        and bottom exclusive (utils/image.feature_box_to_pixels), "centre": (x, y) and "spread": (sx, sy) in pixels (the feature cell's core is 8
+        pixels wide and starts at 8 (c + 1)), "inside": the share of the map within the box, "peak_share"}, ...], "coverage": f32 [H', W'], the
+        token maps added up, "max_coverage": its largest cell -- above 1 a region was attended for more than one token's worth, the mark of a
+        loop -- and "uncovered": the share of its cells below 1 / R^2, R = H' W'}.  The geometry is the default encoder's; encoder_cnn = "cnn" raises."""
+        from .utils.image import feature_box_to_pixels
+        enc = getattr(self._config, "encoder_cnn", "vanilla")
+        feature_box_to_pixels((0, 0, 0, 0), 8, 8, enc)              # refuses the geometry it does not know before anything runs
+        cfg, end = self._config, self._vocab.id_end
+        if formulas is not None:
+            if len(images) != len(formulas):
+                raise ValueError("locate_batch: %d images but %d formulas" % (len(images), len(formulas)))
+            prepro = self._vocab.form_prepro
+            forms = [prepro(f) if isinstance(f, str) else [int(x) for x in f] for f in formulas]
+            fd = self._get_feed_dict(images, formula=forms, dropout=1)
+            ids = fd["formula"]
+            loc = self.engine.score(fd["img"], ids, fd["formula_length"], locate=True, mass=mass, coverage=True)[-1]
+            peak, box, stats, cov = loc
+        else:
+            fd = self._get_feed_dict(images, dropout=1)
+            max_iter = getattr(cfg, "max_length_formula", 150) + 1
+            if getattr(cfg, "decoding", "greedy") == "beam_search":
+                from .utils.text import beam_backtrace
+                out = self.engine.beam_decode(fd["img"], end, cfg.beam_size, max_iter=max_iter, return_boxes=True, mass=mass, coverage=True,
+                                              **self._beam_kwargs())
+                ids = beam_backtrace(out[0], out[1])[:, :, 0]
+                peak, box, stats, cov = (a[:, 0] for a in out[-1])
+            else:
+                ids, loc = self.engine.greedy_decode(fd["img"], end, max_iter=max_iter, return_boxes=True, mass=mass, coverage=True)
+                peak, box, stats, cov = loc
+        H, W = int(fd["img"].shape[1]), int(fd["img"].shape[2])
+        res = []
+        for b in range(len(images)):
+            toks = []
+            for t in np.flatnonzero(peak[b] >= 0):
+                s = stats[b, t]
+                toks.append({"token": self._vocab.id_to_tok[int(ids[b, t])], "box": feature_box_to_pixels(box[b, t], H, W, enc),
+                             "centre": (8.0 * (float(s[1]) + 1.5), 8.0 * (float(s[2]) + 1.5)), "spread": (8.0 * float(s[3]), 8.0 * float(s[4])),
+                             "inside": float(s[6]), "peak_share": float(s[7])})
+            R = cov[b].size
+            res.append({"tokens": toks, "coverage": cov[b], "max_coverage": float(cov[b].max()), "uncovered": float((cov[b] < 1.0 / (R * R)).mean())})
+        return res
+
     def predict(self, img):
         """Reference: model/img2seq.py:278-285."""
         return [hyp[0] for hyp in self.predict_batch([img])]

@@ -41,3 +41,18 @@ def encoder_out_hw(H, W):
     VALID 3x3 conv (model/encoder.py:37-59; the same arithmetic as visualize_attention.py:22-31 getWH)."""
     c = lambda n: -(-n // 2)
     return c(c(c(H))) - 2, c(c(c(W))) - 2
+
+
+def feature_box_to_pixels(box, H, W, encoder_cnn="vanilla"):
+    """A box (x0, y0, x1, y1), inclusive, in cells of the encoder's feature map (Engine.attention_locate) -> (left, top, right, bottom) in pixels of
+    the H x W network input, right and bottom EXCLUSIVE.  The default encoder halves each axis three times (SAME) and ends in a VALID 3 x 3
+    convolution, so feature cell x is produced by a window over the /8 cells x .. x + 2 and its core -- the middle one -- is the pixels
+    [8 (x + 1), 8 (x + 2)).  A box therefore maps to [8 (x0 + 1), 8 (x1 + 2)) x [8 (y0 + 1), 8 (y1 + 2)), clipped to the image.  The "cnn" encoder has
+    another geometry, which is not guessed at: ValueError."""
+    if encoder_cnn != "vanilla":
+        raise ValueError("feature_box_to_pixels knows the geometry of the \"vanilla\" encoder only, got encoder_cnn = %r" % (encoder_cnn,))
+    x0, y0, x1, y1 = (int(v) for v in box)
+    if x0 < 0 or y0 < 0 or x1 < x0 or y1 < y0:
+        raise ValueError("feature_box_to_pixels: not a box: %r" % (tuple(box),))
+    clip = lambda v, n: max(0, min(int(n), v))
+    return clip(8 * (x0 + 1), W), clip(8 * (y0 + 1), H), clip(8 * (x1 + 2), W), clip(8 * (y1 + 2), H)

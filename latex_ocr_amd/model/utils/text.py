@@ -103,6 +103,16 @@ def beam_backtrace(ids, parents):
     return np.take_along_axis(np.asarray(ids), beam_slots(parents), axis=2)
 
 
+def beam_parent_rows(parents):
+    """parents int [B, T, k] -> rows int [B, T, k]: rows[b, t, i] = the decoder row, among the B * k rows of the beam, whose attention map produced the
+    token at step t of the hypothesis that ends in slot i: b * k + parents[b, t, slots[b, t, i]] (beam_slots' rule).  Transposed to [T, B * k] it is
+    the src of Engine.attention_locate over a beam decode's maps."""
+    import numpy as np
+    parents = np.asarray(parents)
+    B, _, k = parents.shape
+    return np.take_along_axis(parents, beam_slots(parents), axis=2) + (np.arange(B, dtype=parents.dtype) * k)[:, None, None]
+
+
 def beam_slots(parents):
     """The slot walk behind beam_backtrace: parents int [B, T, k] -> slots int [B, T, k], slots[b, t, i] = the beam slot at step t of
     the hypothesis that ends in slot i at the last step.  Its token at step t is ids[b, t, slots[b, t, i]]; the decoder row that step

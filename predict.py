@@ -19,7 +19,10 @@ the least expected edit distance to the draws and that cost, every hypothesis li
 --balanced decodes under the delimiter grammar of the vocabulary (latex_ocr_amd.grammar.Grammar.latex: { }, \\left / \\right, \\begin{X} / \\end{X};
 --pairs "OPEN:CLOSE ..." names the pairs instead, each side a comma-separated token list): every hypothesis closes what it opens.  It
 combines with everything but --formula.  Without the flag, where the vocabulary has delimiters, a line "  balanced: yes / no" behind each
-printed hypothesis says whether it does."""
+printed hypothesis says whether it does.
+--boxes prints, per token of the decoded hypothesis (or, with --formula, of that transcription), its box in pixels of the image (left top right
+bottom, the last two exclusive) and the share of its attention inside the box, behind a head line with the coverage map's largest cell and the share
+of cells never attended (Img2SeqModel.locate_batch; --mass M sets the central mass the box keeps).  It combines with --formula only."""
 import argparse
 
 import numpy as np
@@ -49,8 +52,14 @@ def main(argv=None):
                     help="--sample N --consensus: the cost the consensus minimises, the edit distance (default) or 1 - sentence BLEU")
     ap.add_argument("--balanced", action="store_true", help="decode under the delimiter grammar: every hypothesis closes what it opens")
     ap.add_argument("--pairs", default=None, help='delimiter pairs "OPEN:CLOSE ..." (each side comma-separated tokens) instead of those read off the vocabulary')
+    ap.add_argument("--boxes", action="store_true", help="per token: its box in the image (pixels) and the share of its attention inside it; with --formula: of that transcription")
+    ap.add_argument("--mass", type=float, default=0.9, help="--boxes: the central mass of each attention marginal the box keeps, in (0, 1]")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
+    if a.boxes and (a.prefix is not None or a.sample or a.alternatives or a.ban is not None or a.allow_file is not None or a.balanced or a.pairs):
+        ap.error("--boxes locates a plain decode or, with --formula, that transcription; it combines with nothing else")
+    if a.boxes and not 0.0 < a.mass <= 1.0:
+        ap.error("--mass lies in (0, 1]")
     if a.formula is not None and len(a.images) != 1:
         ap.error("--formula scores one image")
     if a.prefix is not None and (len(a.images) != 1 or a.formula is not None):
@@ -108,6 +117,14 @@ def main(argv=None):
     out = []
     for path in a.images:
         img = np.asarray(Image.open(path).convert("RGB"))
+        if a.boxes:
+            res = model.locate_batch([greyscale(img)], None if a.formula is None else [a.formula], mass=a.mass)[0]
+            print(path, "<=" if a.formula is not None else "=>", " ".join(e["token"] for e in res["tokens"]),
+                  "\tmax coverage %.3f\tuncovered %.3f" % (res["max_coverage"], res["uncovered"]))
+            for t, e in enumerate(res["tokens"]):
+                print("  %3d %-12s box %4d %4d %4d %4d  inside %.3f" % ((t, e["token"]) + tuple(e["box"]) + (e["inside"],)))
+            out.append(res)
+            continue
         if a.formula is not None:
             res = model.score_batch([greyscale(img)], [a.formula], **dict(alt, **sets))[0]
             lp, toks, first = res[:3]
