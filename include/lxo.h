@@ -519,6 +519,56 @@ int lxo_sentence_bleu(const int32_t* hyp, int hyp_block, long long hyp_block_str
  * 1 .. LXO_CONSENSUS_MAX_N; T outside 0 .. LXO_EDIT_MAX_REF; a negative stride; more than 2^31 - 16 pairs B * n * (n - 1) / 2. */
 int lxo_consensus_bleu(const int32_t* ids, long long image_stride, long long draw_stride, long long tok_stride, int B, int n, int T, int id_end,
                        const float* weights, int32_t* match_out, float* cost_out, float* risk_out, int32_t* best_out, void* stream);
+/* THE FINISH OF A BEAM SEARCH on the device: the k hypotheses of every image back-traced from what the beam decodes leave, without a copy or a
+ * synchronisation.  The search itself is not touched.
+ * INPUTS (device): ids, parents int32 and scores f32 (nullable), each [B][ld_t][k] as lxo_beam_decode* write them with ld_t = max_steps; steps <= ld_t
+ * is the number of valid steps -- what lies at or behind step `steps` is never read.
+ * THE DEFINITION (utils/text.beam_slots' rule), with P[b][t][j] = min(max(parents[b][t][j], 0), k - 1) -- a parent outside [0, k) is clamped into
+ * it, so no content can fault:
+ *   slot[b][steps - 1][i] = i,  slot[b][t - 1][i] = P[b][t][slot[b][t][i]]        the beam slot at step t of the hypothesis that ends in slot i
+ *   tok[b][t][i] = ids[b][t][slot[b][t][i]],  run[b][t][i] = scores[b][t][slot[b][t][i]]
+ *   len_out int32 [B][k]: 1 + the first t with tok[b][t][i] == id_end, steps if there is none: the tokens through the path's first id_end.  An
+ *     id_end in a slot that is not on the path does not count.  1 <= len <= steps.
+ *   hyp_out int32 [B][steps][k]: tok[b][t][i] for t < len[b][i], id_end behind.  The layout of the input, so lxo_consensus, lxo_consensus_bleu,
+ *     lxo_text_stats, lxo_edit_align and lxo_sentence_bleu read the hypotheses in place (image stride steps k, draw stride 1, token stride k).
+ *   src_out int32 [steps][B k]: src[t][b k + i] = b k + P[b][t][slot[b][t][i]], the decoder row whose attention map produced the token (the parent's
+ *     row): utils/text.beam_parent_rows transposed to the src of lxo_attention_locate.  Written for every t < steps.
+ *   tok_logp_out f32 [B][steps][k]: run[t] - run[t - 1] as ONE f32 subtraction, run[-1] = 0.f, for t < len; 0.f behind.
+ *   seq_logp_out f32 [B][k]: run[len - 1], the frozen score of the hypothesis.
+ * Each output is nullable (not all five); the last two need scores.  One launch, one workgroup per image: the parents are staged in LDS a byte
+ * each, one lane per slot walks them back there, then ids and scores are gathered and every output element is written once.  No atomics, no host
+ * synchronisation, capturable into a graph, the same bytes in every run.  B == 0 launches nothing.
+ * -1, with the reason in lxo_last_error, nothing written and nothing launched: a NULL ids or parents; all outputs NULL; tok_logp_out or seq_logp_out
+ * without scores; B < 0; id_end < 0; ld_t < steps; B * k above 2^31 - 1.
+ * -5: k outside 1 .. LXO_BEAM_MAX_K; steps outside 1 .. LXO_BEAM_MAX_STEPS (the LDS stage; the limit lxo_consensus has). */
+#define LXO_BEAM_MAX_K     16
+#define LXO_BEAM_MAX_STEPS 1024
+int lxo_beam_finalize(const int32_t* ids, const int32_t* parents, const float* scores, int B, int ld_t, int steps, int k, int id_end,
+                      int32_t* hyp_out, int32_t* len_out, int32_t* src_out, float* tok_logp_out, float* seq_logp_out, void* stream);
+/* THE RERANK of a finished beam: GNMT's length and coverage normalisation applied to the k hypotheses the search returned -- the search is as the
+ * reference runs it, the penalties only reorder its result.
+ * INPUTS (device): len int32 [B][k] and seq_logp f32 [B][k] (finite) as lxo_beam_finalize writes them; coverage f32 [B k][cov_ld] (nullable), R <= cov_ld
+ * cells read per row: the coverage_out of lxo_attention_locate given lxo_beam_finalize's src_out and len_out.  alpha, beta >= 0; cov_floor in (0, 1].
+ * THE DEFINITION, per image over its slots i < k:
+ *   lp_i = ((5 + max(len_i, 0)) / 6)^alpha
+ *   cp_i = sum_{r < R} log(min(max(cov_i[r], cov_floor), 1)), 0 without coverage          (a NaN cell counts as cov_floor)
+ *   score_out f32 [B][k] = seq_logp_i / lp_i + beta * cp_i
+ *   post_out  f32 [B][k] = exp(seq_logp_i - m) / sum_j exp(seq_logp_j - m), m = max_j seq_logp_j: the softmax of the frozen scores, the weights of a
+ *     consensus over the beam
+ *   order_out int32 [B][k]: the slots by descending score_out -- the f32 values written -- equal scores by ascending slot (scores with a NaN:
+ *     unspecified, in bounds).
+ * The cells of one image are the same for all its hypotheses: cells that belong to the padding of a batch canvas are attended by none of them, each
+ * adds log(cov_floor) to every cp_i of the image, and so they shift an image's scores TOGETHER -- the order within an image does not see them,
+ * scores of different images are comparable only at equal padding.
+ * ARITHMETIC: logf per cell, its sum over the cells in double in a fixed order; lp, the quotient, the product with beta, the sum and the softmax in
+ * double, each output rounded to f32 once.  So alpha = 0 without coverage gives score_out = seq_logp BIT FOR BIT (x^0 = 1, x / 1 = x, nothing added),
+ * and equal (len, seq_logp) without coverage give equal scores bit for bit.
+ * Each output is nullable (not all three).  One launch, one wave per image; no atomics, no host synchronisation, graph-capturable, the same bytes
+ * in every run.  B == 0 launches nothing.
+ * -1: a NULL len or seq_logp; all outputs NULL; B < 0; B * k above 2^31 - 1; alpha or beta negative or not finite; cov_floor outside (0, 1]; with
+ * coverage, R < 0 or cov_ld < R.  -5: k outside 1 .. LXO_BEAM_MAX_K. */
+int lxo_beam_rerank(const int32_t* len, const float* seq_logp, const float* coverage, int cov_ld, int R, int B, int k, float alpha, float beta,
+                    float cov_floor, float* score_out, float* post_out, int32_t* order_out, void* stream);
 /* lxo_mrt_candidates with the cost chosen: cost_kind = LXO_COST_EDIT is that call bit for bit (it forwards here); with LXO_COST_BLEU the third
  * launch is lxo_sentence_bleu's kernel and cost f32 [R] = 1 - sBLEU of the row against its image's reference -- 0 exactly for the reference's own
  * row (the equality override) and for the dead rows.  Then the rows are a side of that kernel: steps + 1 <= LXO_EDIT_MAX_REF as well.

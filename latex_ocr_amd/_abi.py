@@ -23,6 +23,7 @@ LXO_CONSENSUS_MAX_N = 64  # include/lxo.h: the most draws per image lxo_consensu
 LXO_TEXT_STATS, LXO_TEXT_CORPUS = 12, 14  # include/lxo.h: int32 per pair / int64 per corpus of lxo_text_stats
 LXO_ALIGN_COUNTS, LXO_ALIGN_CORPUS = 6, 8  # include/lxo.h: int32 per pair / int64 per corpus of lxo_edit_align
 LXO_LOCATE_STATS, LXO_LOCATE_MAX_CELLS = 8, 9728  # include/lxo.h: f32 per position of lxo_attention_locate's stats_out / the most cells of a map
+LXO_BEAM_MAX_K, LXO_BEAM_MAX_STEPS = 16, 1024  # include/lxo.h: the widest beam / the most steps lxo_beam_finalize takes
 LXO_BLEU_COUNTS = 10  # include/lxo.h: int32 per pair of lxo_sentence_bleu's counts_out
 LXO_COST_EDIT, LXO_COST_BLEU = 0, 1  # include/lxo.h: the cost_kind of lxo_mrt_candidates_cost
 
@@ -92,6 +93,8 @@ def bind(lib):
         "lxo_edit_align_scratch_bytes": (c_size, [c_int, c_int, c_int]),
         "lxo_edit_align": (c_int, [c_void, c_int, c_ll, c_ll, c_ll, c_int, c_void, c_void, c_int, c_int, c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_void, c_size, c_void]),
         "lxo_attention_locate": (c_int, [c_void, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, c_void, c_void, c_float, c_void, c_void, c_void, c_void, c_int, c_void]),
+        "lxo_beam_finalize": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_void]),
+        "lxo_beam_rerank": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void, c_void, c_void, c_void]),
         "lxo_mrt_candidates": (c_int, [c_void, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_void]),
         "lxo_sentence_bleu": (c_int, [c_void, c_int, c_ll, c_ll, c_ll, c_int, c_void, c_void, c_int, c_int, c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_void]),
         "lxo_mrt_candidates_cost": (c_int, [c_void, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_void]),
@@ -154,7 +157,7 @@ def bind(lib):
 ENTRY_POINTS = ["lxo_last_error", "lxo_version", "lxo_shape_size", "lxo_ws_region_dtype", "lxo_timing_enable", "lxo_timing_count", "lxo_timing_get", "lxo_gemm_nt", "lxo_gemm_tn", "lxo_conv3x3", "lxo_conv3x3_ex", "lxo_conv3x3_wgrad", "lxo_gemm_slab", "lxo_attention_fwd", "lxo_param_num", "lxo_param_name", "lxo_param_name_for",
                 "lxo_param_total", "lxo_param_info", "lxo_wpack_bytes", "lxo_workspace_bytes", "lxo_ws_region",
                 "lxo_pack_weights", "lxo_encoder_fwd", "lxo_encoder_bwd", "lxo_encoder_bwd_ready", "lxo_train_bwd", "lxo_set_side_stream", "lxo_set_encoder_side_stream", "lxo_decoder_train_fwd", "lxo_decoder_train_fwd_live",
-                "lxo_ce_loss_fwd_bwd", "lxo_ce_loss_fwd_bwd_dev", "lxo_ce_loss_weighted", "lxo_ce_loss_smoothed", "lxo_ce_loss_soft", "lxo_mrt_weights", "lxo_edit_distance", "lxo_text_stats", "lxo_edit_align_scratch_bytes", "lxo_edit_align", "lxo_attention_locate", "lxo_mrt_candidates", "lxo_consensus", "lxo_sentence_bleu", "lxo_consensus_bleu", "lxo_mrt_candidates_cost", "lxo_decoder_train_bwd", "lxo_decoder_train_bwd_part", "lxo_global_norm_scale", "lxo_adam_step", "lxo_optimizer_step",
+                "lxo_ce_loss_fwd_bwd", "lxo_ce_loss_fwd_bwd_dev", "lxo_ce_loss_weighted", "lxo_ce_loss_smoothed", "lxo_ce_loss_soft", "lxo_mrt_weights", "lxo_edit_distance", "lxo_text_stats", "lxo_edit_align_scratch_bytes", "lxo_edit_align", "lxo_attention_locate", "lxo_beam_finalize", "lxo_beam_rerank", "lxo_mrt_candidates", "lxo_consensus", "lxo_sentence_bleu", "lxo_consensus_bleu", "lxo_mrt_candidates_cost", "lxo_decoder_train_bwd", "lxo_decoder_train_bwd_part", "lxo_global_norm_scale", "lxo_adam_step", "lxo_optimizer_step",
                 "lxo_greedy_decode", "lxo_greedy_decode_attn", "lxo_beam_decode", "lxo_beam_decode_attn", "lxo_greedy_decode_scores", "lxo_beam_decode_scores", "lxo_score_tokens", "lxo_score_alternatives", "lxo_greedy_decode_prefix", "lxo_beam_decode_prefix", "lxo_greedy_decode_constrained", "lxo_beam_decode_constrained", "lxo_sample_decode", "lxo_sample_tokens",
                 "lxo_grammar_scratch_bytes", "lxo_greedy_decode_grammar", "lxo_beam_decode_grammar", "lxo_sample_decode_grammar", "lxo_grammar_step", "lxo_decode_begin", "lxo_decode_step",
                 "lxo_chain_guard", "lxo_decode_state_get", "lxo_decode_state_set", "lxo_decode_cell_step",

@@ -175,6 +175,7 @@ extern "C" int lxo_mrt_weights(const float* seq_logp, const float* cost, const i
 }
 #include "seqcost.h"
 #include "attloc.h"
+#include "beamfin.h"
 static_assert(LXO_EDIT_MAX_REF == kEditMaxRef, "include/lxo.h and csrc/seqcost.h disagree on the reference limit");
 extern "C" int lxo_edit_distance(const int32_t* hyp, int hyp_block, long long hyp_block_stride, long long hyp_row_stride, long long hyp_tok_stride, int T,
                                  const int32_t* hyp_len, const int32_t* ref, int G, int ref_ld, const int32_t* ref_len, const int32_t* ref_of,
@@ -303,6 +304,35 @@ extern "C" int lxo_consensus_bleu(const int32_t* ids, long long image_stride, lo
     if ((long long)B * n * (n - 1) / 2 > 0x7ffffff0ll) return fail(-1, "lxo_consensus_bleu: B n (n - 1) / 2 pairs exceed one launch");
     const ConsBleuArgs a = {ids, weights, match_out, cost_out, risk_out, best_out, image_stride, draw_stride, tok_stride, B, n, T, id_end};
     CHECK_LAUNCH(lxo_k_consensus_bleu(a, (hipStream_t)stream), "lxo_consensus_bleu");
+    return 0;
+}
+static_assert(LXO_BEAM_MAX_K == kBeamFinMaxK && LXO_BEAM_MAX_STEPS == kBeamFinMaxSteps, "include/lxo.h and csrc/beamfin.h disagree on the beam limits");
+extern "C" int lxo_beam_finalize(const int32_t* ids, const int32_t* parents, const float* scores, int B, int ld_t, int steps, int k, int id_end,
+                                 int32_t* hyp_out, int32_t* len_out, int32_t* src_out, float* tok_logp_out, float* seq_logp_out, void* stream) {
+    if (!ids || !parents) return fail(-1, "lxo_beam_finalize: null ids or parents");
+    if (!hyp_out && !len_out && !src_out && !tok_logp_out && !seq_logp_out) return fail(-1, "lxo_beam_finalize: the five outputs are all NULL");
+    if ((tok_logp_out || seq_logp_out) && !scores) return fail(-1, "lxo_beam_finalize: tok_logp_out or seq_logp_out without scores");
+    if (B < 0 || id_end < 0) return fail(-1, "lxo_beam_finalize: B or id_end negative");
+    if (k < 1 || k > LXO_BEAM_MAX_K) return fail(-5, "lxo_beam_finalize: k outside 1 .. LXO_BEAM_MAX_K");
+    if (steps < 1 || steps > LXO_BEAM_MAX_STEPS) return fail(-5, "lxo_beam_finalize: steps outside 1 .. LXO_BEAM_MAX_STEPS (the kernel's LDS stage)");
+    if (ld_t < steps) return fail(-1, "lxo_beam_finalize: ld_t < steps");
+    if ((long long)B * k > 0x7fffffffll) return fail(-1, "lxo_beam_finalize: B * k above 2^31 - 1");
+    const BeamFinArgs a = {ids, parents, scores, hyp_out, len_out, src_out, tok_logp_out, seq_logp_out, B, ld_t, steps, k, id_end};
+    CHECK_LAUNCH(lxo_k_beam_finalize(a, (hipStream_t)stream), "lxo_beam_finalize");
+    return 0;
+}
+extern "C" int lxo_beam_rerank(const int32_t* len, const float* seq_logp, const float* coverage, int cov_ld, int R, int B, int k, float alpha, float beta,
+                               float cov_floor, float* score_out, float* post_out, int32_t* order_out, void* stream) {
+    if (!len || !seq_logp) return fail(-1, "lxo_beam_rerank: null len or seq_logp");
+    if (!score_out && !post_out && !order_out) return fail(-1, "lxo_beam_rerank: the three outputs are all NULL");
+    if (B < 0) return fail(-1, "lxo_beam_rerank: B negative");
+    if (k < 1 || k > LXO_BEAM_MAX_K) return fail(-5, "lxo_beam_rerank: k outside 1 .. LXO_BEAM_MAX_K");
+    if ((long long)B * k > 0x7fffffffll) return fail(-1, "lxo_beam_rerank: B * k above 2^31 - 1");
+    if (!(alpha >= 0.f && __builtin_isfinite(alpha)) || !(beta >= 0.f && __builtin_isfinite(beta))) return fail(-1, "lxo_beam_rerank: alpha or beta negative or not finite");
+    if (!(cov_floor > 0.f && cov_floor <= 1.f)) return fail(-1, "lxo_beam_rerank: cov_floor outside (0, 1]");
+    if (coverage && (R < 0 || cov_ld < R)) return fail(-1, "lxo_beam_rerank: R < 0 or cov_ld < R");
+    const BeamRerankArgs a = {len, seq_logp, coverage, score_out, post_out, order_out, B, k, coverage ? R : 0, cov_ld, alpha, beta, cov_floor};
+    CHECK_LAUNCH(lxo_k_beam_rerank(a, (hipStream_t)stream), "lxo_beam_rerank");
     return 0;
 }
 extern "C" int lxo_score_tokens(const lxo_shape* s, void* ws, const int32_t* formula, const int32_t* lengths,

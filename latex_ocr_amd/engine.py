@@ -22,6 +22,8 @@ Alternatives = namedtuple("Alternatives", ["ids", "logp", "rank", "entropy"])
 _SoftDev = namedtuple("_SoftDev", ["ids", "p", "k", "lam"])          # soft targets behind their checks: device int32 / f32 [B, T, k], lambda
 Alignment = namedtuple("Alignment", ["hyp_align", "ref_align", "counts", "corpus", "confusion"])
 Locations = namedtuple("Locations", ["peak", "box", "stats", "coverage"])        # Engine.attention_locate
+BeamPaths = namedtuple("BeamPaths", ["hyp", "lengths", "src", "tok_logp", "seq_logp"])                     # Engine.beam_finalize
+NBest = namedtuple("NBest", ["hyp", "lengths", "tok_logp", "seq_logp", "score", "post", "order"])         # Engine.beam_decode(return_nbest=True)
 
 
 def _p(t):
@@ -1159,14 +1161,15 @@ class Engine(object):
                 raise ValueError("attention_locate: lengths must be [rows = %d], got %s" % (rows, tuple(lengths.shape)))
         return self._locate(a, a.stride(1) if steps > 1 else 0, a.stride(0) if AR > 1 else 0, AR, Hp, Wp, rows, steps, lengths, src, mass, coverage)
 
-    def _locate(self, alpha, step_stride, row_stride, alpha_rows, Hp, Wp, rows, steps, len_dev, src_dev, mass, coverage):
-        """The lxo_attention_locate call on maps where they lie (strides in floats): -> Locations of device tensors"""
+    def _locate(self, alpha, step_stride, row_stride, alpha_rows, Hp, Wp, rows, steps, len_dev, src_dev, mass, coverage, per_position=True):
+        """The lxo_attention_locate call on maps where they lie (strides in floats): -> Locations of device tensors.  per_position=False: the
+        coverage alone (peak, box and stats None)"""
         mass = float(mass)
         if not 0.0 < mass <= 1.0:
             raise ValueError("mass must lie in (0, 1], got %r" % mass)
-        peak = torch.empty(rows, steps, dtype=torch.int32, device=self.device)
-        box = torch.empty(rows, steps, 4, dtype=torch.int32, device=self.device)
-        stats = torch.empty(rows, steps, _abi.LXO_LOCATE_STATS, dtype=torch.float32, device=self.device)
+        peak = torch.empty(rows, steps, dtype=torch.int32, device=self.device) if per_position else None
+        box = torch.empty(rows, steps, 4, dtype=torch.int32, device=self.device) if per_position else None
+        stats = torch.empty(rows, steps, _abi.LXO_LOCATE_STATS, dtype=torch.float32, device=self.device) if per_position else None
         cov = torch.empty(rows, Hp, Wp, dtype=torch.float32, device=self.device) if coverage else None
         self._ck(self.lib.lxo_attention_locate(_p(alpha), int(step_stride), int(row_stride), int(alpha_rows), Hp, Wp, rows, steps, _p(len_dev), _p(src_dev),
                                                mass, _p(peak), _p(box), _p(stats), _p(cov), Hp * Wp, self._stream()), "attention_locate")
@@ -1179,6 +1182,70 @@ class Engine(object):
         hit = ids == int(id_end)
         first = hit.to(torch.int32).argmax(1).to(torch.int32) + 1
         return torch.where(hit.any(1), first, torch.full_like(first, int(ids.shape[1]))).contiguous()
+
+    def beam_finalize(self, ids, parents, scores=None, id_end=None, steps=None):
+        """The hypotheses of a beam decode, back-traced on the device (lxo_beam_finalize; include/lxo.h holds the definition).  ids, parents
+        int32 and scores f32 (optional) [B, T, k]: what beam_decode returns, as host arrays, or device tensors of its buffers -- a slice
+        buf[:, :n] of a [B, max_steps, k] buffer is read in place.  steps (None: T): the valid steps; what lies behind is not read.
+        -> BeamPaths(hyp int32 [B, steps, k]: hyp[b, :, i] = the token path that ends in slot i, id_end behind its first id_end
+        (utils/text.beam_backtrace, cut); lengths int32 [B, k]: its tokens through the first id_end; src int32 [steps, B k]: the decoder row each
+        token was read off (utils/text.beam_parent_rows transposed: attention_locate's src); tok_logp f32 [B, steps, k]: the differences of the
+        running scores along the path, 0 behind its end; seq_logp f32 [B, k]: its frozen score -- the last two None without scores), host arrays.
+        A ValueError before any launch for a wrong rank or shape, k outside 1 .. 16, steps outside 1 .. min(T, 1024), and for HOST parents
+        outside [0, k) (on the device such a parent is clamped into the range).  beam_finalize_dev leaves the outputs on the device."""
+        return BeamPaths(*[None if a is None else a.cpu().numpy() for a in self.beam_finalize_dev(ids, parents, scores, id_end, steps)])
+
+    def beam_finalize_dev(self, ids, parents, scores=None, id_end=None, steps=None):
+        """beam_finalize with its outputs left on the device"""
+        if id_end is None or int(id_end) < 0:
+            raise ValueError("beam_finalize: id_end must be a token id >= 0, got %r" % (id_end,))
+        shp = tuple(int(v) for v in ids.shape)
+        for name, a in (("parents", parents), ("scores", scores)):
+            if a is not None and tuple(int(v) for v in a.shape) != shp:
+                raise ValueError("beam_finalize: %s must have the shape of ids %s, got %s" % (name, list(shp), list(a.shape)))
+        if len(shp) != 3:
+            raise ValueError("beam_finalize: ids must be [B, T, k], got %s" % list(shp))
+        B, T, k = shp
+        if not 1 <= k <= _abi.LXO_BEAM_MAX_K:
+            raise ValueError("beam_finalize: k = %d outside 1 .. %d" % (k, _abi.LXO_BEAM_MAX_K))
+        steps = T if steps is None else int(steps)
+        if not 1 <= steps <= min(T, _abi.LXO_BEAM_MAX_STEPS):
+            raise ValueError("beam_finalize: steps = %d outside 1 .. min(T = %d, %d)" % (steps, T, _abi.LXO_BEAM_MAX_STEPS))
+        if not isinstance(parents, torch.Tensor):
+            p = np.asarray(parents)[:, :steps]
+            if p.size and (p.min() < 0 or p.max() >= k):
+                raise ValueError("beam_finalize: a parent outside [0, k = %d)" % k)
+        t = [None if a is None else (a if isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == dt else self._to_dev(a, dt))
+             for a, dt in ((ids, torch.int32), (parents, torch.int32), (scores, torch.float32))]
+        # a [B, ld_t, k] buffer seen through buf[:, :T]: rows of k words, ld_t rows per image; anything else is copied
+        lds = {(x.stride(0) // k if B > 1 else T) if (k == 1 or x.stride(2) == 1) and (T == 1 or x.stride(1) == k) and (B == 1 or x.stride(0) % k == 0) else -1
+               for x in t if x is not None}
+        ld = lds.pop() if len(lds) == 1 else -1
+        if ld < T:
+            t, ld = [None if x is None else x.contiguous() for x in t], T
+        return self._beam_finalize(t[0], t[1], t[2], B, ld, steps, k, int(id_end))
+
+    def _beam_finalize(self, ids, par, sc, B, ld_t, steps, k, id_end):
+        """The lxo_beam_finalize call on device buffers [B][ld_t][k]: -> BeamPaths of device tensors"""
+        hyp = torch.empty(B, steps, k, dtype=torch.int32, device=self.device)
+        ln = torch.empty(B, k, dtype=torch.int32, device=self.device)
+        src = torch.empty(steps, B * k, dtype=torch.int32, device=self.device)
+        tok = torch.empty(B, steps, k, dtype=torch.float32, device=self.device) if sc is not None else None
+        seq = torch.empty(B, k, dtype=torch.float32, device=self.device) if sc is not None else None
+        self._ck(self.lib.lxo_beam_finalize(_p(ids), _p(par), _p(sc), B, ld_t, steps, k, id_end, _p(hyp), _p(ln), _p(src), _p(tok), _p(seq), self._stream()),
+                 "beam_finalize")
+        return BeamPaths(hyp, ln, src, tok, seq)
+
+    def _beam_rerank(self, lengths, seq_logp, coverage, alpha, beta, cov_floor):
+        """The lxo_beam_rerank call: lengths / seq_logp [B, k] and coverage [B k, R...] (None) on the device -> (score, post, order) [B, k], on the device"""
+        B, k = (int(v) for v in seq_logp.shape)
+        score = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        post = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        order = torch.empty(B, k, dtype=torch.int32, device=self.device)
+        R = 0 if coverage is None else int(coverage[0].numel())
+        self._ck(self.lib.lxo_beam_rerank(_p(lengths), _p(seq_logp), _p(coverage), R, R, B, k, float(alpha), float(beta), float(cov_floor),
+                                          _p(score), _p(post), _p(order), self._stream()), "beam_rerank")
+        return score, post, order
 
     def sentence_bleu(self, hyp, ref, hyp_lengths=None, ref_lengths=None, id_end=None, ref_index=None, return_counts=False):
         """Sentence-level BLEU-4 per pair on the device (lxo_sentence_bleu; include/lxo.h holds the definition: add-one smoothing on the orders
@@ -1739,7 +1806,8 @@ class Engine(object):
 
     def beam_decode(self, img, id_end, beam_size, max_iter=151, return_parents=False, div_gamma=1.0, div_prob=0.0, div_seed=0, return_attention=False,
                     return_scores=False, prefix=None, prefix_lengths=None, allowed=None, grammar=None, return_depth=False, return_boxes=False, mass=0.9,
-                    coverage=False):
+                    coverage=False, return_nbest=False, length_penalty=0.0, coverage_penalty=0.0, cov_floor=0.01, return_consensus=False,
+                    consensus_cost="edit"):
         """ids int32 [B, T', k] as pred_test.ids of the beam graph before the transpose at img2seq.py:241.
         div_gamma / div_prob: add_div_penalty of beam_search_decoder_cell.py:258-287 (off at 1 / 0, the shipped values).
         return_attention: -> (ids, parents, alpha f32 [B, T', k, H', W']): alpha[b, t, j] = the map decoder row j of image b attended with at
@@ -1757,13 +1825,39 @@ class Engine(object):
         box [B, k, T', 4], stats [B, k, T', 8], coverage [B, k, H', W'] with coverage=True; entry [b, i] belongs to the hypothesis that ends in
         slot i (utils/text.beam_backtrace's out[b, :, i]).  Its token at step t was read off the row of its parent, so position (b k + i, t)
         reads the map of row b k + parents[b, t, slots[b, t, i]] (beam_slots' rule); that src array is built ON THE HOST from the copied parents
-        and the reduction then runs on the device on the alpha_out buffer.  Steps behind a hypothesis' first END have no map."""
+        and the reduction then runs on the device on the alpha_out buffer.  Steps behind a hypothesis' first END have no map.
+        return_nbest: the beam FINISHED ON THE DEVICE (lxo_beam_finalize, lxo_beam_rerank) before anything is copied; the outputs above are what
+        they are without the flag, and one NBest follows them: hyp int32 [B, T', k] (hyp[b, :, i] = the back-traced path that ends in slot i, END
+        behind its first END), lengths int32 [B, k], tok_logp f32 [B, T', k] and seq_logp f32 [B, k] (the path's token log-probs and its frozen
+        score), score f32 [B, k] = seq_logp / ((5 + length) / 6)^length_penalty + coverage_penalty * sum_cells log(min(max(coverage, cov_floor), 1))
+        (GNMT's normalisation, applied to the k hypotheses the search returned -- the search itself is the reference's), post f32 [B, k] = the
+        softmax of seq_logp over the image's slots, order int32 [B, k] = the slots by descending score.  length_penalty = coverage_penalty = 0:
+        score is seq_logp.  coverage_penalty > 0 exports the attention maps and sums each hypothesis' coverage (attention_locate's) with the src
+        and lengths built on the device; the cells of the batch canvas' padding shift an image's scores together.  With return_nbest,
+        return_boxes takes that device-built src too.
+        return_consensus (with return_nbest): best int32 [B] and risk f32 [B, k] follow the NBest: the minimum-risk choice among the k
+        hypotheses (consensus(); consensus_cost "edit" or "bleu"), read from hyp in place with post as the weights.  The Locations of
+        return_boxes stay the very last output."""
         self._check_beam(beam_size)
         if return_depth and grammar is None:
             raise ValueError("return_depth needs grammar=")
         if return_boxes and not 0.0 < float(mass) <= 1.0:
             raise ValueError("mass must lie in (0, 1], got %r" % (mass,))
-        want_maps, return_attention = return_attention, return_attention or return_boxes
+        if return_nbest:
+            _cost_kind("beam_decode: consensus_cost", consensus_cost)
+            lp, cpw, fl = float(length_penalty), float(coverage_penalty), float(cov_floor)
+            if not (0.0 <= lp < float("inf") and 0.0 <= cpw < float("inf")):
+                raise ValueError("beam_decode: length_penalty and coverage_penalty must be finite and >= 0, got %r, %r" % (length_penalty, coverage_penalty))
+            if not 0.0 < fl <= 1.0:
+                raise ValueError("beam_decode: cov_floor must lie in (0, 1], got %r" % (cov_floor,))
+            if max_iter > _abi.LXO_BEAM_MAX_STEPS:
+                raise ValueError("beam_decode: return_nbest takes at most %d steps, got max_iter = %d" % (_abi.LXO_BEAM_MAX_STEPS, max_iter))
+        elif return_consensus or float(length_penalty) != 0.0 or float(coverage_penalty) != 0.0:
+            raise ValueError("beam_decode: length_penalty, coverage_penalty and return_consensus need return_nbest=True")
+        with_parents = return_parents or return_attention or return_boxes or return_scores or return_depth
+        want_maps, want_scores = return_attention, return_scores
+        return_attention = return_attention or return_boxes or (return_nbest and cpw > 0.0)
+        return_scores = return_scores or return_nbest
         if self.max_steps < max_iter + 1:
             self.max_steps, self.ws = max_iter + 1, None
         B0 = int(img.shape[0])
@@ -1780,14 +1874,17 @@ class Engine(object):
         gram = self._grammar_args(g, B * int(beam_size), ids) if g is not None else None
         n = self._run_decode(self._beam_entry(pfx, ids, par, sc, alpha, alw, gram), id_end, max_iter)
         out = [ids[:, :n]]
-        if return_parents or return_attention or return_scores or return_depth:
+        if with_parents:
             out.append(par[:, :n])
         if want_maps:
             out.append(alpha[:n, :, :R].reshape(n, B, beam_size, Hp, Wp).permute(1, 0, 2, 3, 4).contiguous())
-        if return_scores:
+        if want_scores:
             out.append(sc[:, :n])
         if return_depth:
             out.append(gram[1][:, :n])
+        if return_nbest:
+            return self._beam_nbest(out, ids, par, sc, alpha, (B, int(beam_size), n, Hp, Wp), id_end, lp, cpw, fl, return_consensus, consensus_cost,
+                                    (mass, coverage) if return_boxes else None)
         out = tuple(a.cpu().numpy() for a in out)
         if return_boxes:
             from .model.utils.text import beam_backtrace, beam_parent_rows
@@ -1799,6 +1896,27 @@ class Engine(object):
                                  self._to_dev(np.ascontiguousarray(src.transpose(1, 0, 2).reshape(n, B * k)), torch.int32), mass, coverage)
             out += (Locations(*[None if a is None else a.cpu().numpy().reshape((B, k) + tuple(a.shape[1:])) for a in where]),)
         return out if len(out) > 1 else out[0]
+
+    def _beam_nbest(self, lead, ids, par, sc, alpha, geo, id_end, length_penalty, coverage_penalty, cov_floor, consensus, consensus_cost, boxes):
+        """beam_decode's finish on the device: lead (device tensors) + NBest (+ best, risk) (+ Locations), host arrays.  Everything is enqueued
+        before the first copy."""
+        B, k, n, Hp, Wp = geo
+        fin = self._beam_finalize(ids, par, sc, B, int(ids.shape[1]), n, k, int(id_end))
+        where = cov = None
+        if boxes is not None or coverage_penalty > 0.0:
+            Rp = int(alpha.shape[2])
+            where = self._locate(alpha, B * k * Rp, Rp, B * k, Hp, Wp, B * k, n, fin.lengths.reshape(-1), fin.src, boxes[0] if boxes is not None else 0.9,
+                                 coverage_penalty > 0.0 or boxes[1], per_position=boxes is not None)
+            cov = where.coverage if coverage_penalty > 0.0 else None
+        score, post, order = self._beam_rerank(fin.lengths, fin.seq_logp, cov, length_penalty, coverage_penalty, cov_floor)
+        tail = list(self._consensus_device(fin.hyp, id_end, post, True, consensus_cost)[:2]) if consensus else []
+        out = tuple(a.cpu().numpy() for a in lead)
+        out += (NBest(*[a.cpu().numpy() for a in (fin.hyp, fin.lengths, fin.tok_logp, fin.seq_logp, score, post, order)]),)
+        out += tuple(a.cpu().numpy() for a in tail)
+        if boxes is not None:
+            loc = Locations(where.peak, where.box, where.stats, where.coverage if boxes[1] else None)
+            out += (Locations(*[None if a is None else a.cpu().numpy().reshape((B, k) + tuple(a.shape[1:])) for a in loc]),)
+        return out
 
     def _sample_opts(self, n, temperature, top_k, top_p, seed):
         """Checks the sampling options before any launch: -> lxo_sample_opts.  temperature = 0 means top_k = 1 (the arg-max)."""

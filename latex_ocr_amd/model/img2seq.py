@@ -667,6 +667,46 @@ class Img2SeqModel(BaseModel):
                 out[-1].update(consensus=k, expected_cost=hyps[k]["risk"])
         return out
 
+    def nbest_batch(self, images, length_penalty=0.0, coverage_penalty=0.0, consensus=False, consensus_cost="edit", banned=None, allowed=None,
+                    grammar=None):
+        """The beam's k hypotheses per image, finished on the device and reranked (Engine.beam_decode(return_nbest=True): the back-trace, the cut
+        at END, the scores and the rerank run before anything is copied).  config.decoding must be "beam_search".  -> one dict per image,
+        {"hypotheses": [{"text", "slot": the beam slot the path ends in, "length": its tokens through END, "logp": its frozen beam score,
+        "token_logp": [...], "score": logp / ((5 + length) / 6)^length_penalty + coverage_penalty * sum over the feature cells of
+        log(min(max(coverage, floor), 1)) (GNMT's normalisation of the finished beam; the search itself is the reference's), "posterior": the
+        softmax of logp over the image's k slots}, ...] in descending score}.  length_penalty = coverage_penalty = 0: the order of logp.
+        consensus: every hypothesis gains "risk", its expected cost (consensus_cost "edit": edit distance over the other side's length, "bleu":
+        1 - sentence BLEU) against the k hypotheses weighted with their posteriors, and every image "consensus", the index into "hypotheses" of the
+        one of least risk, and "expected_cost", that risk.  banned / allowed / grammar: as in predict_batch."""
+        cfg = self._config
+        if getattr(cfg, "decoding", "greedy") != "beam_search":
+            raise ValueError("nbest_batch needs config.decoding = \"beam_search\", got %r" % (getattr(cfg, "decoding", "greedy"),))
+        self._check_cost("nbest_batch: consensus_cost", consensus_cost)
+        fd = self._get_feed_dict(images, dropout=1)
+        id_end = self._vocab.id_end
+        res = self.engine.beam_decode(fd["img"], id_end, cfg.beam_size, max_iter=getattr(cfg, "max_length_formula", 150) + 1, return_nbest=True,
+                                      length_penalty=length_penalty, coverage_penalty=coverage_penalty, return_consensus=bool(consensus),
+                                      consensus_cost=consensus_cost, allowed=self._token_sets(len(images), banned, allowed),
+                                      **dict(self._beam_kwargs(), **self._grammar(grammar)))
+        nb = res[1]
+        best, risk = res[2:4] if consensus else (None, None)
+        out = []
+        for b in range(nb.hyp.shape[0]):
+            hyps = []
+            for i in (int(x) for x in nb.order[b]):
+                n = int(nb.lengths[b, i])
+                h = {"text": " ".join(self._vocab.id_to_tok[int(t)] for t in truncate_end(nb.hyp[b, :n, i], id_end)), "slot": i, "length": n,
+                     "logp": float(nb.seq_logp[b, i]), "token_logp": [float(x) for x in nb.tok_logp[b, :n, i]], "score": float(nb.score[b, i]),
+                     "posterior": float(nb.post[b, i])}
+                if consensus:
+                    h["risk"] = float(risk[b, i])
+                hyps.append(h)
+            out.append({"hypotheses": hyps})
+            if consensus:
+                j = [x["slot"] for x in hyps].index(int(best[b]))
+                out[-1].update(consensus=j, expected_cost=hyps[j]["risk"])
+        return out
+
     def locate_batch(self, images, formulas=None, mass=0.9):
         """WHERE in its image each token is (Engine.attention_locate, reduced on the device: the attention maps never visit the host).
         formulas given (token-id lists or token strings, as score_batch takes them): teacher-forced, the given transcription's tokens with the

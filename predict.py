@@ -22,7 +22,12 @@ combines with everything but --formula.  Without the flag, where the vocabulary 
 printed hypothesis says whether it does.
 --boxes prints, per token of the decoded hypothesis (or, with --formula, of that transcription), its box in pixels of the image (left top right
 bottom, the last two exclusive) and the share of its attention inside the box, behind a head line with the coverage map's largest cell and the share
-of cells never attended (Img2SeqModel.locate_batch; --mass M sets the central mass the box keeps).  It combines with --formula only."""
+of cells never attended (Img2SeqModel.locate_batch; --mass M sets the central mass the box keeps).  It combines with --formula only.
+--nbest (config.decoding = "beam_search") prints the beam's hypotheses, back-traced and reranked on the device (Img2SeqModel.nbest_batch): one line
+per hypothesis in rerank order with its score, log-prob, posterior, length and beam slot.  --length-penalty A and --coverage-penalty B are GNMT's
+normalisation of the finished beam (0: the order of the log-probs); --consensus marks with a * the hypothesis of least expected cost against the
+others weighted with their posteriors and prints every risk (--consensus-cost bleu: 1 - sentence BLEU).  It combines with --ban / --allow-file and
+--balanced."""
 import argparse
 
 import numpy as np
@@ -54,6 +59,9 @@ def main(argv=None):
     ap.add_argument("--pairs", default=None, help='delimiter pairs "OPEN:CLOSE ..." (each side comma-separated tokens) instead of those read off the vocabulary')
     ap.add_argument("--boxes", action="store_true", help="per token: its box in the image (pixels) and the share of its attention inside it; with --formula: of that transcription")
     ap.add_argument("--mass", type=float, default=0.9, help="--boxes: the central mass of each attention marginal the box keeps, in (0, 1]")
+    ap.add_argument("--nbest", action="store_true", help="beam search: every hypothesis of the beam, reranked, with score, log-prob and posterior")
+    ap.add_argument("--length-penalty", type=float, default=0.0, metavar="A", help="--nbest: score = logp / ((5 + length) / 6)^A")
+    ap.add_argument("--coverage-penalty", type=float, default=0.0, metavar="B", help="--nbest: score += B * sum over the feature cells of log(min(coverage, 1))")
     ap.add_argument("images", nargs="+")
     a = ap.parse_args(argv)
     if a.boxes and (a.prefix is not None or a.sample or a.alternatives or a.ban is not None or a.allow_file is not None or a.balanced or a.pairs):
@@ -66,10 +74,16 @@ def main(argv=None):
         ap.error("--prefix completes one image and does not combine with --formula")
     if a.sample and (a.formula is not None or a.prefix is not None or a.alternatives or not 1 <= a.sample <= 16):
         ap.error("--sample takes 1 .. 16 and does not combine with --formula, --prefix or --alternatives")
-    if a.consensus and not a.sample:
-        ap.error("--consensus chooses among the draws of --sample N")
-    if a.consensus_cost is not None and not (a.sample and a.consensus):
-        ap.error("--consensus-cost names the cost of --sample N --consensus")
+    if a.nbest and (a.formula is not None or a.prefix is not None or a.sample or a.alternatives or a.boxes or a.scores):
+        ap.error("--nbest lists a beam decode's hypotheses; it combines with --ban, --allow-file, --balanced and --consensus only")
+    if (a.length_penalty or a.coverage_penalty) and not a.nbest:
+        ap.error("--length-penalty and --coverage-penalty rerank the hypotheses of --nbest")
+    if a.length_penalty < 0 or a.coverage_penalty < 0:
+        ap.error("--length-penalty and --coverage-penalty are >= 0")
+    if a.consensus and not (a.sample or a.nbest):
+        ap.error("--consensus chooses among the draws of --sample N or the hypotheses of --nbest")
+    if a.consensus_cost is not None and not ((a.sample or a.nbest) and a.consensus):
+        ap.error("--consensus-cost names the cost of --sample N --consensus or --nbest --consensus")
     d = a.results
     config_vocab, config_model = Config(d + "vocab.json"), Config(d + "model.json")
     vocab = Vocab(config_vocab)
@@ -123,6 +137,22 @@ def main(argv=None):
                   "\tmax coverage %.3f\tuncovered %.3f" % (res["max_coverage"], res["uncovered"]))
             for t, e in enumerate(res["tokens"]):
                 print("  %3d %-12s box %4d %4d %4d %4d  inside %.3f" % ((t, e["token"]) + tuple(e["box"]) + (e["inside"],)))
+            out.append(res)
+            continue
+        if a.nbest:
+            more = {"consensus": True, "consensus_cost": a.consensus_cost or "edit"} if a.consensus else {}
+            try:
+                res = model.nbest_batch([greyscale(img)], length_penalty=a.length_penalty, coverage_penalty=a.coverage_penalty, **dict(dec, **more))[0]
+            except ValueError as e:
+                ap.error("--nbest: %s" % e)
+            print(path, "=>", res["hypotheses"][0]["text"], "\tscore %.4f" % res["hypotheses"][0]["score"])
+            if a.consensus:
+                print(path, "=> consensus:", res["hypotheses"][res["consensus"]]["text"], "\texpected cost %.4f" % res["expected_cost"])
+            for k, h in enumerate(res["hypotheses"]):
+                risk = "  risk %.4f" % h["risk"] if a.consensus else ""
+                print("%s slot %2d  score %9.4f  logp %9.4f  post %.4f  len %3d%s  %s" % ("*" if a.consensus and k == res["consensus"] else " ", h["slot"], h["score"],
+                                                                                          h["logp"], h["posterior"], h["length"], risk, h["text"]))
+                report(h["text"])
             out.append(res)
             continue
         if a.formula is not None:
